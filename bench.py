@@ -1,6 +1,6 @@
 """bench.py -- simulated worker-steps/s of the FL server loop (BASELINE.json metric).
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
   (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1
            --master-port P bench.py --gpus N --steps K --warmup W)
 
@@ -11,10 +11,22 @@ schedule, every computing worker's fwd/bwd (worker-batched HIP kernels), [one RC
 fused cascade-mean + Adam.  value = executed worker-steps (128-sample fwd+bwd units, summed over
 the job) / wall time of the K timed epochs (max over ranks).
 
-Extra objects on the JSON line: roofline (dominant GEMM kernel, HIP events recorded by
-libflsim.so on its launch stream over the timed region), aggregation (the fused
-rule()+Adam kernel's algorithmic HBM GB/s), cpu_baseline (the oracle's CPU port of the
-reference loop on this host, bounded sample, rank 0 at N = 1 only).
+A plain run sets up, pre-rolls and warms up, times the K epochs, writes its outputs when
+--dump-outputs is given and prints the JSON line.  Extra objects on that line, all read off the
+timed epochs themselves: roofline (dominant GEMM kernel, HIP events recorded by libflsim.so on
+its launch stream over the timed region), aggregation (the fused rule()+Adam kernel's algorithmic
+HBM GB/s), window / steady_state (the timed epochs one by one).
+
+--full adds the measurements that take runs of their own after the timed window (null on the
+line without it): cpu_baseline and gpu_vs_cpu (the oracle's CPU port of the reference loop on this
+host, bounded sample, rank 0 at N = 1 only; over a minute) and aggregation_stream (the
+post-all-reduce server step timed alone at N = 1).
+
+--dump-outputs DIR writes what the last timed epoch left with its caller as DIR/<name>.npy
+(float32): theta, adam_m, adam_v (the model and optimizer state after the epoch's fused rule() +
+Adam) and losses (the per-worker-step losses of that epoch's computing workers).  An array of more
+than DUMP_CAP elements is stored as a fixed seeded sample of DUMP_CAP of them (in index order), so
+the whole dump stays under 64 MB.  The inputs are seeded: the same arguments give the same arrays.
 """
 import argparse
 import json
@@ -42,6 +54,7 @@ X6_KERNELS = {f"conv{i}_fwd" for i in range(2, 7)} | {"linear1_fwd", "linear1_wg
 VGG_X6_KERNELS = {f"vgg_conv{i}_fwd" for i in range(1, 9)} | \
     {f"vgg_linear{i}_{p}" for i in (1, 2) for p in ("fwd", "wgrad")}
 HBM_PEAK_GBPS = 8000.0           # MI355X_MICROARCH.md: HBM3E spec
+DUMP_CAP = 1 << 22               # elements per dumped array: 16 MB of float32 each
 
 
 def _load_traffic():
@@ -89,10 +102,17 @@ def parse():
     ap.add_argument("--model_file", type=str, default=None,
                     help="warm start (main.py:98-100): a models.py state_dict, e.g. configs[1]'s "
                          "warm_start.pt from tools/make_warm_start.py")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need, after the timed "
+                         "window: the CPU baseline and the post-all-reduce server step (N = 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write theta / adam_m / adam_v / losses of the last timed epoch as "
+                         "DIR/<name>.npy (float32; seeded samples of arrays over DUMP_CAP elements)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baseline")
     ap.add_argument("--no-stream", action="store_true",
-                    help="skip timing the post-all-reduce server step (k_agg_stream) after the "
-                         "timed window at N = 1")
+                    help="with --full: skip timing the post-all-reduce server step (k_agg_stream) "
+                         "after the timed window at N = 1")
     ap.add_argument("--no-probe", action="store_true")
     ap.add_argument("--force-dist", action="store_true",
                     help="run the N > 1 code path at world size 1 (launch under torchrun "
@@ -238,8 +258,27 @@ def stream_step_probe(sim, iters=20):
                 bound="hbm", peak=HBM_PEAK_GBPS, **out) if out else None
 
 
+def dump_outputs(path, arrays):
+    """--dump-outputs: each array flattened, as path/<name>.npy in float32.  Arrays of more than
+    DUMP_CAP elements keep a sample of DUMP_CAP indices drawn without replacement from
+    RandomState(0) and sorted: the same indices in every run of the same arguments."""
+    os.makedirs(path, exist_ok=True)
+    picks = {}
+    for name, t in arrays.items():
+        a = t.detach().reshape(-1)
+        n = a.numel()
+        if n > DUMP_CAP:
+            if n not in picks:
+                idx = np.sort(np.random.RandomState(0).choice(n, DUMP_CAP, replace=False))
+                picks[n] = torch.from_numpy(idx).to(a.device)
+            a = a[picks[n]]
+        np.save(os.path.join(path, name + ".npy"), a.to(torch.float32).cpu().numpy())
+
+
 def main():
     args = parse()
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     # stdout carries exactly ONE line, the JSON result: RCCL prints a version banner on stdout when
     # its communicator starts (profiles/r05/bench_forcedist.json), so the process's stdout goes to
     # stderr and the result line is written to a saved copy of the original stdout
@@ -315,6 +354,9 @@ def main():
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dict(theta=sim.theta, adam_m=sim.m, adam_v=sim.v,
+                                             losses=sim.loss_log[-1][0]))
     losses = sim.losses()
     rank_ws_all = [rank_ws]
     if dist_on:
@@ -429,12 +471,13 @@ def main():
                           "(aggregation.alg_bytes_per_launch); this is the rule()+Adam share "
                           "priced at the whole launch time")
     agg_stream = None
-    if not dist_on and probe is not None and args.model == "PerformantNet1" and not args.no_stream:
+    if args.full and not dist_on and probe is not None and args.model == "PerformantNet1" and \
+            not args.no_stream:
         agg_stream = stream_step_probe(sim)
 
     value = ws / elapsed
     cpu = None
-    if rank == 0 and not dist_on and not args.no_cpu_baseline:
+    if args.full and rank == 0 and not dist_on and not args.no_cpu_baseline:
         cpu = cpu_baseline(args.n_workers, args.delay, throttle, args.model, args.configs0_epochs)
     if rank == 0:
         line = {

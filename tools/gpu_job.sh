@@ -4,8 +4,8 @@
 # Usage (repo root, on the GPU box):  bash tools/gpu_job.sh <tag> <step> [<step> ...]
 #   smoke             __graft_entry__.smoke()
 #   tests[:<k-expr>]  pytest -m gpu (error census in flips.jsonl / tol.jsonl; -k <k-expr> if given)
-#   bench             the default bench line (with its CPU baseline) + tools/bench_summary.py
-#   benchq            the default bench line without the CPU baseline
+#   bench             the bench line with --full (CPU baseline, stream step) + tools/bench_summary.py
+#   benchq            the plain bench line (no CPU baseline, no stream step)
 #   ab:<lib>          bench line of an alternative libflsim.so (FLSIM_LIB=<lib>) beside benchq
 #   abvgg:<lib>       configs[4] (vgg11, n = 4096, d = 1000) with an alternative libflsim.so, B A B A
 #   bl:<name>:<lib>  one bench line on another libflsim.so build (FLSIM_LIB)
@@ -76,7 +76,7 @@ for STEP in "$@"; do
         tail -2 $OUT/pytest_gpu.txt; grep -E "^FAILED" $OUT/pytest_gpu.txt | head
         [ $rc -le 1 ] || { echo "pytest rc $rc: stopping"; exit $rc; } ;;
     bench)
-        timeout -k 10 400 python3 -u bench.py > $OUT/bench.json 2> $OUT/bench.err \
+        timeout -k 10 400 python3 -u bench.py --full > $OUT/bench.json 2> $OUT/bench.err \
             || { echo "bench failed $?"; tail -5 $OUT/bench.err; exit 1; }
         python3 tools/bench_summary.py $OUT/bench.json > $OUT/bench.txt
         head -3 $OUT/bench.txt ;;

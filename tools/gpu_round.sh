@@ -11,6 +11,6 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout
 tail -3 gpurun_out/pytest_gpu_$TAG.log
 bash tools/gpu_profile.sh $TAG || exit 1
 python3 tools/pmc_traffic.py gpurun_out/prof_$TAG gpurun_out/prof_$TAG/traffic.json profiles/traffic.json || exit 1
-timeout -k 10 400 python -u bench.py > gpurun_out/bench_$TAG.json 2> gpurun_out/bench_$TAG.err \
-    || { echo "bench failed $?"; tail -20 gpurun_out/bench_$TAG.err; exit 1; }
-cat gpurun_out/bench_$TAG.json
+# the full bench line (bench.py --full: with the CPU baseline and the stream step) and its summary,
+# written by the bench step of tools/gpu_job.sh into its <tag> folder
+bash tools/gpu_job.sh $TAG bench || exit 1
