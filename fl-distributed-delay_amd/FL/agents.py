@@ -9,8 +9,9 @@ Same classes, signatures and aliasing semantics; the arithmetic runs in libflsim
                                tensors, as in the reference)
   Agg(rule)                    agents.py:43-45; use FL.agents.rule (== main.py:23-25's mean) to
                                get the fused path: it returns a lazy mean that Central consumes
-  Central.update_model(ups)    agents.py:9-21 -> flsim_aggregate_adam_rule (cascade mean over the
-                               entries in any order + Adam with the optimizer's lr/betas/eps);
+  Central.update_model(ups)    agents.py:9-21 -> flsim_aggregate_optim_rule_push (cascade mean over
+                               the entries in any order + the optimizer's step: torch.optim.Adam,
+                               AdamW or SGD with the hyper-parameters of its param_groups[0]);
                                parameters live in one flat device buffer, model.parameters() are
                                views of it
 
@@ -39,8 +40,9 @@ worker-batched pass when a loss, a .grad view or a BatchNorm buffer is read, or 
 (FLSIM_FACADE_LAZY_LOSS=0: a call's forward runs at once).
 
 Requirements (raise otherwise): the model is FL.models.PerformantNet1, vgg11() or vgg11_bn() on
-a HIP device, the optimizer is torch.optim.Adam without weight decay / amsgrad / maximize.
-There is no CPU fallback.
+a HIP device, the optimizer is torch.optim.Adam (weight_decay allowed), torch.optim.AdamW or
+torch.optim.SGD (momentum, dampening, weight_decay, nesterov) with one param group and without
+amsgrad / maximize.  There is no CPU fallback.
 """
 from __future__ import annotations
 
@@ -50,7 +52,7 @@ import weakref
 import numpy as np
 import torch
 
-from flsim.engine import (ProgramStager, Rule, engine_for_parameters, padded, split_views,
+from flsim.engine import (Optim, ProgramStager, Rule, engine_for_parameters, padded, split_views,
                           worker_table)
 
 _CONTEXTS = weakref.WeakKeyDictionary()    # model -> _ModelContext (dies with the model)
@@ -434,15 +436,40 @@ class Central:
         self.model = model
         self.optim = optim
         g = optim.param_groups[0]
-        if not isinstance(optim, torch.optim.Adam) or g.get("weight_decay", 0) != 0 or \
-                g.get("amsgrad", False) or g.get("maximize", False):
-            raise NotImplementedError("fused update implements torch.optim.Adam "
-                                      "(main.py:106: Adam(lr), no weight decay / amsgrad)")
+        if not isinstance(optim, (torch.optim.Adam, torch.optim.SGD)) or \
+                len(optim.param_groups) != 1 or g.get("amsgrad", False) or \
+                g.get("maximize", False):
+            raise NotImplementedError("fused update implements torch.optim.Adam (weight_decay "
+                                      "allowed), torch.optim.AdamW and torch.optim.SGD with one "
+                                      "param group (main.py:106: Adam(lr)), no amsgrad / maximize")
+        self._optim()                # torch's constructor has validated the hyper-parameters
         self.ctx = _context(model)
         _NEXT_WORKER[0] = 0          # main.py:112-113: the workers built next are 0 .. n-1
 
-    def _sync_optimizer_state(self):
+    def _optim(self):
+        """The optimizer's param_groups[0] as the engine's Optim (read at every step: a scheduler
+        may have changed lr)."""
+        g = self.optim.param_groups[0]
+        if isinstance(self.optim, torch.optim.SGD):
+            return Optim(kind="sgd", lr=g["lr"], weight_decay=g["weight_decay"],
+                         momentum=g["momentum"], dampening=g["dampening"],
+                         nesterov=bool(g["nesterov"]))
+        decoupled = isinstance(self.optim, torch.optim.AdamW) or \
+            g.get("decoupled_weight_decay", False)
+        return Optim(kind="adamw" if decoupled else "adam", lr=g["lr"], betas=tuple(g["betas"]),
+                     eps=g["eps"], weight_decay=g.get("weight_decay", 0))
+
+    def _sync_optimizer_state(self, o):
+        """optim.state as torch itself would hold it: step / exp_avg / exp_avg_sq for the Adam
+        family, momentum_buffer for SGD with momentum, nothing for plain SGD (views of the
+        engine's buffers, so optim.state_dict() loads into a stock torch optimizer)."""
         ctx = self.ctx
+        if o.kind == "sgd":
+            if o.n_state:
+                for p, mv in zip(self.model.parameters(),
+                                 split_views(ctx.m[:ctx.P], ctx.shapes)):
+                    self.optim.state[p] = {"momentum_buffer": mv}
+            return
         for p, mv, vv in zip(self.model.parameters(), split_views(ctx.m[:ctx.P], ctx.shapes),
                              split_views(ctx.v[:ctx.P], ctx.shapes)):
             self.optim.state[p] = {"step": torch.tensor(float(ctx.step)), "exp_avg": mv,
@@ -484,7 +511,11 @@ class Central:
             S = torch.nn.functional.pad(S, (0, padded(ctx.P) - ctx.P))
             r = Rule(1, [], c=1)
         ctx.step += 1
-        hp = dict(lr=g["lr"], betas=g["betas"], eps=g["eps"])
+        o = self._optim()
+        if o.kind == "adam" and o.weight_decay == 0:
+            hp = dict(lr=g["lr"], betas=g["betas"], eps=g["eps"])
+        else:
+            hp = dict(optim=o)
         if isinstance(ups, _LazyMean) and ctx.G is not None and ctx.carry is None and \
                 not ctx.touched and hasattr(eng, "server_step"):
             # fused: this epoch's slabs -> S_t (also written into G, which the FIFO entries of
@@ -497,7 +528,7 @@ class Central:
             eng.aggregate_rule(S, r, ctx.theta, ctx.m, ctx.v, ctx.step, **hp)
         for p in self.model.parameters():        # optim.zero_grad() (set_to_none, torch >= 2)
             p.grad = None
-        self._sync_optimizer_state()
+        self._sync_optimizer_state(o)
         ctx.new_epoch()
 
     def init_adv(self, model):

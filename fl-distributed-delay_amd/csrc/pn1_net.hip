@@ -1166,15 +1166,26 @@ int flsim_pn1_end_epoch(void* gradstate, float* grad_out, hipStream_t stream) {
 int flsim_pn1_server_step(void* gradstate, float* S_out, const flsim_rule* rule, float* p,
                           float* m, float* v, long step, double lr, double beta1, double beta2,
                           double eps, hipStream_t stream) {
-    FLSIM_REQUIRE(gradstate && rule && p && m && v, "null pointer");
+    const flsim_optim o = adam_optim(lr, beta1, beta2, eps);
+    return flsim_pn1_server_step_optim(gradstate, S_out, rule, p, m, v, step, &o, stream);
+}
+
+// ... with the update rule of `optim` (include/flsim.h: SGD, Adam with weight decay, AdamW)
+int flsim_pn1_server_step_optim(void* gradstate, float* S_out, const flsim_rule* rule, float* p,
+                                float* m, float* v, long step, const flsim_optim* optim,
+                                hipStream_t stream) {
+    RC(check_optim(optim));
+    const int nstate = optim->kind == FLSIM_OPT_SGD ? (optim->momentum != 0.0 ? 1 : 0) : 2;
+    FLSIM_REQUIRE(gradstate && rule && p && (m || nstate < 1) && (v || nstate < 2),
+                  "null pointer");
     RC(pipe_join(gradstate, stream));
     GradState g = gs_layout((float*)gradstate);
     RuleProg R;
     RC(make_rule(rule, &R));
-    AdamConst ac;
-    RC(make_adam_const(rule->k, step, lr, beta1, beta2, eps, &ac));
-    return slab_step_launch((float*)gradstate, plan_in_use(g, gradstate), g.cnt_off, g.part_off,
-                            S_out, &R, &ac, p, m, v, P_TOTAL, stream);
+    OptLaunch ol;
+    RC(make_opt_launch(optim, rule->k, step, &ol));
+    return slab_step_launch_optim((float*)gradstate, plan_in_use(g, gradstate), g.cnt_off,
+                                  g.part_off, S_out, &R, ol, p, m, v, P_TOTAL, stream);
 }
 
 }  // extern "C"

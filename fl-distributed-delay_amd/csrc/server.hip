@@ -10,6 +10,9 @@
 // sum / (float)k; Adam m = fma(1-b1, g-m, m), v = fma((1-b2)*g, g, v*b2),
 // den = sqrt(v)/sqrt(bc2) + eps, p += (-lr/bc1 * m) / den (correctly rounded sqrt; torch CPU's
 // sqrt is not).  Compiled with -ffp-contract=off: the only fmas are explicit.
+// Central(model, optim) takes other optimizers too: the kernels are instantiated per update rule
+// (OptKind, slabstep.h: Adam, Adam with weight decay / AdamW, SGD with and without momentum; see
+// opt_elem), each streaming only the state arrays its rule owns.
 //
 // Two kernels:
 //   k_agg_stream  S_t already in a buffer (after the all-reduce at world > 1, or the facade):
@@ -68,9 +71,9 @@ __device__ __forceinline__ float div_const(float a, float b, float rb) {
     return (aq >= 0x1p-124f && aq <= 0x1p+124f) ? q : __fdiv_rn(a, b);
 }
 
-__device__ __forceinline__ void adam_elem(const AdamConst& A, float s, float& p, float& m,
-                                          float& v) {
-    const float g = div_const(s, A.fk, A.rk);               // rule(): mean = sum / k
+// torch.optim.Adam's update for the gradient g (_single_tensor_adam, no weight decay)
+__device__ __forceinline__ void adam_update(const AdamConst& A, float g, float& p, float& m,
+                                            float& v) {
     const float mi = __fmaf_rn(A.w1, g - m, m);
     float vi = v * A.b2;
     vi = __fmaf_rn(A.w2 * g, g, vi);
@@ -78,6 +81,44 @@ __device__ __forceinline__ void adam_elem(const AdamConst& A, float s, float& p,
     p = p + __fdiv_rn(A.neg_ss * mi, den);
     m = mi;
     v = vi;
+}
+
+__device__ __forceinline__ void adam_elem(const AdamConst& A, float s, float& p, float& m,
+                                          float& v) {
+    const float g = div_const(s, A.fk, A.rk);               // rule(): mean = sum / k
+    adam_update(A, g, p, m, v);
+}
+
+// The other update rules, in torch 2.10's CPU op order (every add(x, alpha=a) there is one fma):
+//   Adam, weight_decay w  g = fma(p, w, g), then Adam                  (_single_tensor_adam)
+//   AdamW                 p = p * f32(1 - lr * w), then Adam on g
+//   SGD                   g = fma(p, w, g) if w != 0;                  (_single_tensor_sgd)
+//                         momentum mu != 0: buf = g at step 1, else fma(g, 1 - dampening, buf * mu);
+//                                           g = nesterov ? fma(buf, mu, g) : buf;
+//                         p = fma(g, -lr, p)
+// The flags are launch-uniform (scalar branches).  m is SGD's momentum buffer; a kind never
+// touches an argument it does not own (the callers pass dummies).
+template <int OK>
+__device__ __forceinline__ void opt_elem(const AdamConst& A, const OptConst& X, float s, float& p,
+                                         float& m, float& v) {
+    if constexpr (OK == OK_ADAM) {
+        adam_elem(A, s, p, m, v);
+    } else {
+        float g = div_const(s, A.fk, A.rk);                 // rule(): mean = sum / k
+        if constexpr (OK == OK_ADAMD) {
+            if (X.flags & OF_DECOUPLED) p = p * X.wd;
+            else g = __fmaf_rn(p, X.wd, g);
+            adam_update(A, g, p, m, v);
+        } else {
+            if (X.flags & OF_WD) g = __fmaf_rn(p, X.wd, g);
+            if constexpr (OK == OK_SGDM) {
+                const float buf = (X.flags & OF_FIRST) ? g : __fmaf_rn(g, X.omd, m * X.mu);
+                g = (X.flags & OF_NESTEROV) ? __fmaf_rn(buf, X.mu, g) : buf;
+                m = buf;
+            }
+            p = __fmaf_rn(g, X.neg_lr, p);
+        }
+    }
 }
 
 // Program access.  The interpreter reads one macro word (two dwords) per step at a uniform address,
@@ -132,6 +173,7 @@ struct AggArgs {
     long edge_lo[MAX_EDGE];
     AdamConst ac;
     RuleProg R;
+    OptConst oc;                    // last: the OK_ADAM kernels' argument offsets stay as they were
 };
 static_assert(sizeof(AggArgs) <= 4096, "kernel argument block");
 
@@ -157,8 +199,9 @@ __device__ __forceinline__ bool block_touch(const AggArgs& A, long blo, long spa
 // per thread; a streaming block that is also an edge block returns at once.  Every load of a
 // thread (S_t, the staged entry arrays, p, m, v) is issued before the arithmetic; loads and
 // stores are non-temporal (each byte is touched once).
-template <bool INL>
+template <bool INL, int OK = OK_ADAM>
 __global__ void __launch_bounds__(256) k_agg_stream(AggArgs A) {
+    constexpr bool HAS_M = opt_n_state(OK) >= 1, HAS_V = opt_n_state(OK) == 2;
     __shared__ f32x4 ys_lds[NYR * 256];
     const ProgRef<INL> prog{A.R};
     const int tid = threadIdx.x;
@@ -166,17 +209,19 @@ __global__ void __launch_bounds__(256) k_agg_stream(AggArgs A) {
         const long e = A.edge_lo[blockIdx.x] + tid;
         if (e < A.lo || e >= A.hi) return;
         const float x = A.S[e];
-        float p = A.p[e], m = A.m[e], v = A.v[e];
+        float p = A.p[e], m = 0.f, v = 0.f;
+        if constexpr (HAS_M) m = A.m[e];
+        if constexpr (HAS_V) v = A.v[e];
         auto yf = [&](int q) -> float { return A.R.arr[q] ? A.R.arr[q][e] : 0.f; };
         const CascVals<float> cv = casc_values(x, A.R.info.need, A.R.info.lp);
         const bool tail = in_tail(A, e);
         float s = 0.f;
         if (!tail) s = casc_run_macro(prog, 0, cv, yf);
         if (tail) s = casc_run_macro(prog, A.R.info.tail_off, cv, yf);
-        adam_elem(A.ac, s, p, m, v);
+        opt_elem<OK>(A.ac, A.oc, s, p, m, v);
         A.p[e] = p;
-        A.m[e] = m;
-        A.v[e] = v;
+        if constexpr (HAS_M) A.m[e] = m;
+        if constexpr (HAS_V) A.v[e] = v;
         if (A.S_out) A.S_out[e] = x;
         return;
     }
@@ -194,7 +239,9 @@ __global__ void __launch_bounds__(256) k_agg_stream(AggArgs A) {
     for (int q = 0; q < NYR; ++q)
         ys[q] = (q < nst && A.R.arr[q]) ? ld(A.R.arr[q] + e0) : f32x4{0.f, 0.f, 0.f, 0.f};
     const f32x4 x = ld(A.S + e0);
-    f32x4 p = ld(A.p + e0), m = ld(A.m + e0), v = ld(A.v + e0);
+    f32x4 p = ld(A.p + e0), m = {0.f, 0.f, 0.f, 0.f}, v = m;
+    if constexpr (HAS_M) m = ld(A.m + e0);
+    if constexpr (HAS_V) v = ld(A.v + e0);
 #pragma unroll
     for (int q = 0; q < NYR; ++q)
         if (q < nst) ys_lds[q * 256 + tid] = ys[q];
@@ -207,14 +254,14 @@ __global__ void __launch_bounds__(256) k_agg_stream(AggArgs A) {
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
         float pp = p[u], mm = m[u], vv = v[u];
-        adam_elem(A.ac, sum[u], pp, mm, vv);
+        opt_elem<OK>(A.ac, A.oc, sum[u], pp, mm, vv);
         p[u] = pp;
         m[u] = mm;
         v[u] = vv;
     }
     st(A.p + e0, p);
-    st(A.m + e0, m);
-    st(A.v + e0, v);
+    if constexpr (HAS_M) st(A.m + e0, m);
+    if constexpr (HAS_V) st(A.v + e0, v);
     if (A.S_out) st(A.S_out + e0, x);
 }
 
@@ -232,8 +279,9 @@ struct AggVec<1> { typedef float T __attribute__((ext_vector_type(4))); };
 template <>
 struct AggVec<2> { typedef float T __attribute__((ext_vector_type(8))); };
 
-template <int G, int NY>
+template <int G, int NY, int OK = OK_ADAM>
 __global__ void __launch_bounds__(256) k_agg_stream_reg(AggArgs A) {
+    constexpr bool HAS_M = opt_n_state(OK) >= 1, HAS_V = opt_n_state(OK) == 2;
     typedef typename AggVec<G>::T T;
     const ProgRef<true> prog{A.R};
     const int tid = threadIdx.x;
@@ -241,17 +289,19 @@ __global__ void __launch_bounds__(256) k_agg_stream_reg(AggArgs A) {
         const long e = A.edge_lo[blockIdx.x] + tid;
         if (e < A.lo || e >= A.hi) return;
         const float x = A.S[e];
-        float p = A.p[e], m = A.m[e], v = A.v[e];
+        float p = A.p[e], m = 0.f, v = 0.f;
+        if constexpr (HAS_M) m = A.m[e];
+        if constexpr (HAS_V) v = A.v[e];
         auto yf = [&](int q) -> float { return A.R.arr[q] ? A.R.arr[q][e] : 0.f; };
         const CascVals<float> cv = casc_values(x, A.R.info.need, A.R.info.lp);
         const bool tail = in_tail(A, e);
         float s = 0.f;
         if (!tail) s = casc_run_macro(prog, 0, cv, yf);
         if (tail) s = casc_run_macro(prog, A.R.info.tail_off, cv, yf);
-        adam_elem(A.ac, s, p, m, v);
+        opt_elem<OK>(A.ac, A.oc, s, p, m, v);
         A.p[e] = p;
-        A.m[e] = m;
-        A.v[e] = v;
+        if constexpr (HAS_M) A.m[e] = m;
+        if constexpr (HAS_V) A.v[e] = v;
         if (A.S_out) A.S_out[e] = x;
         return;
     }
@@ -276,8 +326,10 @@ __global__ void __launch_bounds__(256) k_agg_stream_reg(AggArgs A) {
     for (int j = 0; j < G; ++j) {
         xs[j] = ld(A.S + e[j]);
         ps[j] = ld(A.p + e[j]);
-        ms[j] = ld(A.m + e[j]);
-        vs[j] = ld(A.v + e[j]);
+        if constexpr (HAS_M) ms[j] = ld(A.m + e[j]);
+        else ms[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        if constexpr (HAS_V) vs[j] = ld(A.v + e[j]);
+        else vs[j] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
     auto widen = [](const f32x4 (&a)[G]) -> T {
         T t;
@@ -302,14 +354,14 @@ __global__ void __launch_bounds__(256) k_agg_stream_reg(AggArgs A) {
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             float pp = ps[j][u], mm = ms[j][u], vv = vs[j][u];
-            adam_elem(A.ac, sum[4 * j + u], pp, mm, vv);
+            opt_elem<OK>(A.ac, A.oc, sum[4 * j + u], pp, mm, vv);
             ps[j][u] = pp;
             ms[j][u] = mm;
             vs[j][u] = vv;
         }
         st(A.p + e[j], ps[j]);
-        st(A.m + e[j], ms[j]);
-        st(A.v + e[j], vs[j]);
+        if constexpr (HAS_M) st(A.m + e[j], ms[j]);
+        if constexpr (HAS_V) st(A.v + e[j], vs[j]);
         if (A.S_out) st(A.S_out + e[j], xs[j]);
     }
 }
@@ -330,6 +382,7 @@ struct StepArgs {
     AdamConst ac;
     RuleProg R;
     SlabSeg seg[STEP_MAX_SEG];
+    OptConst oc;                    // last: the OK_ADAM kernels' argument offsets stay as they were
 };
 static_assert(sizeof(StepArgs) <= 4096, "kernel argument block");
 
@@ -432,9 +485,10 @@ __device__ __forceinline__ bool col_to_param(const SlabSeg& g, long col, long& t
 // Identity-layout segments (the linear layers): tiles of 1024 elements, thread t owns the float4
 // column 4t; it sums its Z slab rows itself (small Z, four accumulators) and finishes with 16-B
 // parameter-side loads and stores; the parameter loads are issued before the slab reads.
-template <bool ADAM, bool INL>
+template <bool ADAM, bool INL, int OK>
 __device__ __forceinline__ void slab_step_wide(const StepArgs& A, const SlabSeg& g, int u, int ul,
                                                float* lds) {
+    constexpr bool HAS_M = opt_n_state(OK) >= 1, HAS_V = opt_n_state(OK) == 2;
     // entry arrays held in registers (the rest load on demand): all of a general-order program's
     // arrays up to 8 (configs[3] uses 6), so no Y word of the interpreter waits on a global load
     constexpr int NYW = 8;
@@ -467,8 +521,10 @@ __device__ __forceinline__ void slab_step_wide(const StepArgs& A, const SlabSeg&
             for (int q = 0; q < NYW; ++q)
                 ys[q] = (q < A.R.narr && A.R.arr[q]) ? ld(A.R.arr[q] + e) : f32x4{0.f, 0.f, 0.f, 0.f};
             p = ld(A.p + e);
-            m = ld(A.m + e);
-            v = ld(A.v + e);
+            if constexpr (HAS_M) m = ld(A.m + e);
+            else m = f32x4{0.f, 0.f, 0.f, 0.f};
+            if constexpr (HAS_V) v = ld(A.v + e);
+            else v = f32x4{0.f, 0.f, 0.f, 0.f};
         };
         // reference order: the parameter side is loaded ahead of the slab rows (both round trips
         // overlap); general order: after them, so the registers are free during the reduction and
@@ -562,14 +618,14 @@ __device__ __forceinline__ void slab_step_wide(const StepArgs& A, const SlabSeg&
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 float pp = p[k], mm = m[k], vv = v[k];
-                adam_elem(A.ac, sum[k], pp, mm, vv);
+                opt_elem<OK>(A.ac, A.oc, sum[k], pp, mm, vv);
                 p[k] = pp;
                 m[k] = mm;
                 v[k] = vv;
             }
             __builtin_nontemporal_store(p, reinterpret_cast<f32x4*>(A.p + e));
-            __builtin_nontemporal_store(m, reinterpret_cast<f32x4*>(A.m + e));
-            __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(A.v + e));
+            if constexpr (HAS_M) __builtin_nontemporal_store(m, reinterpret_cast<f32x4*>(A.m + e));
+            if constexpr (HAS_V) __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(A.v + e));
         }
     }
 }
@@ -579,8 +635,9 @@ __device__ __forceinline__ void slab_step_wide(const StepArgs& A, const SlabSeg&
 // loads, whose cost does not depend on which XCD the last arriver sits on.  Each thread's
 // parameter-side loads (p, m, v, staged entry arrays) are issued before the slab reduction (whole
 // tiles) or together with the partial loads (split tiles), so the two memory round trips overlap.
-template <bool ADAM, bool INL>
+template <bool ADAM, bool INL, int OK>
 __device__ __forceinline__ void slab_step_body(const StepArgs& A, float* lds) {
+    constexpr bool HAS_M = opt_n_state(OK) >= 1, HAS_V = opt_n_state(OK) == 2;
     const int tid = threadIdx.x;
     // runs of XG consecutive units (a tile's z-units, neighbouring tiles: one parameter region)
     // share an XCD (blocks b and b + 8 do), the runs themselves go round-robin over the XCDs so
@@ -604,7 +661,7 @@ __device__ __forceinline__ void slab_step_body(const StepArgs& A, float* lds) {
     const SlabSeg& g = A.seg[si];
     const int ul = u - g.unit0;
     if (g.wide) {
-        slab_step_wide<ADAM, INL>(A, g, u, ul, lds);
+        slab_step_wide<ADAM, INL, OK>(A, g, u, ul, lds);
         return;
     }
     int tile, t_end, j;
@@ -633,8 +690,8 @@ __device__ __forceinline__ void slab_step_body(const StepArgs& A, float* lds) {
             for (int q = 0; q < NYR; ++q)
                 ys[q] = (q < nst && A.R.arr[q]) ? A.R.arr[q][e] : 0.f;
             p = A.p[e];
-            m = A.m[e];
-            v = A.v[e];
+            if constexpr (HAS_M) m = A.m[e];
+            if constexpr (HAS_V) v = A.v[e];
         };
         if (ADAM && valid && g.nz == 1) load_param_side();
         __syncthreads();                       // LDS reuse across the unit's tiles
@@ -688,8 +745,8 @@ __device__ __forceinline__ void slab_step_body(const StepArgs& A, float* lds) {
             const bool tail = valid && tl >= (long)(g.numel / 32) * 32;
             lds[L_S + tid] = valid ? s : 0.f;
             lds[L_P + tid] = p;
-            lds[L_M + tid] = m;
-            lds[L_V + tid] = v;
+            if constexpr (HAS_M) lds[L_M + tid] = m;
+            if constexpr (HAS_V) lds[L_V + tid] = v;
 #pragma unroll
             for (int q = 0; q < NYR; ++q)
                 if (q < nst) lds[L_Y + q * 256 + tid] = valid ? ys[q] : 0.f;
@@ -704,18 +761,19 @@ __device__ __forceinline__ void slab_step_body(const StepArgs& A, float* lds) {
                     auto yf4 = [&](int q) -> f32x4 { return l4[(L_Y + q * 256) / 4 + tid]; };
                     const f32x4 sum = casc_run_macro<true>(
                         prog, 0, casc_values(l4[L_S / 4 + tid], A.R.info.need, A.R.info.lp), yf4);
-                    const f32x4 pp = l4[L_P / 4 + tid], mm = l4[L_M / 4 + tid],
-                                vv = l4[L_V / 4 + tid];
+                    const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+                    const f32x4 pp = l4[L_P / 4 + tid], mm = HAS_M ? l4[L_M / 4 + tid] : zero4,
+                                vv = HAS_V ? l4[L_V / 4 + tid] : zero4;
 #pragma unroll
                     for (int k = 0; k < 4; ++k) {
                         long tk;
                         if (!col_to_param(g, (long)tile * 256 + 4 * tid + k, tk)) continue;
                         float p1 = pp[k], m1 = mm[k], v1 = vv[k];
-                        adam_elem(A.ac, sum[k], p1, m1, v1);
+                        opt_elem<OK>(A.ac, A.oc, sum[k], p1, m1, v1);
                         const long ek = g.toff + tk;
                         A.p[ek] = p1;
-                        A.m[ek] = m1;
-                        A.v[ek] = v1;
+                        if constexpr (HAS_M) A.m[ek] = m1;
+                        if constexpr (HAS_V) A.v[ek] = v1;
                     }
                     return;
                 }
@@ -725,25 +783,27 @@ __device__ __forceinline__ void slab_step_body(const StepArgs& A, float* lds) {
                     auto yf4 = [&](int q) -> f32x4 { return l4[(L_Y + q * 256) / 4 + tid]; };
                     const f32x4 sum = casc_run_macro<true>(
                         prog, 0, casc_values(l4[L_S / 4 + tid], A.R.info.need, A.R.info.lp), yf4);
-                    f32x4 pp = l4[L_P / 4 + tid], mm = l4[L_M / 4 + tid], vv = l4[L_V / 4 + tid];
+                    const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+                    f32x4 pp = l4[L_P / 4 + tid], mm = HAS_M ? l4[L_M / 4 + tid] : zero4,
+                          vv = HAS_V ? l4[L_V / 4 + tid] : zero4;
 #pragma unroll
                     for (int k = 0; k < 4; ++k) {
                         float p1 = pp[k], m1 = mm[k], v1 = vv[k];
-                        adam_elem(A.ac, sum[k], p1, m1, v1);
+                        opt_elem<OK>(A.ac, A.oc, sum[k], p1, m1, v1);
                         pp[k] = p1;
                         mm[k] = m1;
                         vv[k] = v1;
                     }
                     f32x4* w4 = reinterpret_cast<f32x4*>(lds);
                     w4[L_P / 4 + tid] = pp;
-                    w4[L_M / 4 + tid] = mm;
-                    w4[L_V / 4 + tid] = vv;
+                    if constexpr (HAS_M) w4[L_M / 4 + tid] = mm;
+                    if constexpr (HAS_V) w4[L_V / 4 + tid] = vv;
                 }
                 __syncthreads();
                 if (valid) {
                     A.p[e] = lds[L_P + tid];
-                    A.m[e] = lds[L_M + tid];
-                    A.v[e] = lds[L_V + tid];
+                    if constexpr (HAS_M) A.m[e] = lds[L_M + tid];
+                    if constexpr (HAS_V) A.v[e] = lds[L_V + tid];
                 }
                 continue;
             }
@@ -763,18 +823,18 @@ __device__ __forceinline__ void slab_step_body(const StepArgs& A, float* lds) {
             float sum = 0.f;
             if (!tail) sum = casc_run_macro(prog, 0, cv, yf);
             if (tail) sum = casc_run_macro(prog, A.R.info.tail_off, cv, yf);
-            adam_elem(A.ac, sum, p, m, v);
+            opt_elem<OK>(A.ac, A.oc, sum, p, m, v);
             A.p[e] = p;
-            A.m[e] = m;
-            A.v[e] = v;
+            if constexpr (HAS_M) A.m[e] = m;
+            if constexpr (HAS_V) A.v[e] = v;
         }
     }
 }
 
-template <bool ADAM, bool INL>
+template <bool ADAM, bool INL, int OK = OK_ADAM>
 __global__ void __launch_bounds__(256) k_slab_step(StepArgs A) {
     __shared__ float lds[L_Y + NYR * 256];
-    slab_step_body<ADAM, INL>(A, lds);
+    slab_step_body<ADAM, INL, OK>(A, lds);
 }
 
 // General-order programs: the interpreter's chains of dependent adds want many resident waves to
@@ -782,10 +842,11 @@ __global__ void __launch_bounds__(256) k_slab_step(StepArgs A) {
 #ifndef SEQ_WAVES
 #define SEQ_WAVES 4
 #endif
+template <int OK = OK_ADAM>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SEQ_WAVES, 8)))
 k_slab_step_seq(StepArgs A) {
     __shared__ float lds[L_END];
-    slab_step_body<true, false>(A, lds);
+    slab_step_body<true, false, OK>(A, lds);
 }
 
 // ================================================================================================
@@ -812,6 +873,53 @@ int make_adam_const(int divisor, long step, double lr, double beta1, double beta
     }
     ac->eps = (float)eps;
     ac->neg_ss = (float)(-(lr / bc1));
+    return 0;
+}
+
+int check_optim(const flsim_optim* o) {
+    FLSIM_REQUIRE(o, "null optimizer");
+    FLSIM_REQUIRE(o->kind == FLSIM_OPT_ADAM || o->kind == FLSIM_OPT_ADAMW ||
+                  o->kind == FLSIM_OPT_SGD, "unknown optimizer kind %d", o->kind);
+    // negated comparisons: a NaN is refused too
+    FLSIM_REQUIRE(o->lr >= 0.0, "Invalid learning rate: %g", o->lr);
+    FLSIM_REQUIRE(o->weight_decay >= 0.0, "Invalid weight_decay value: %g", o->weight_decay);
+    // (momentum, dampening and nesterov act for FLSIM_OPT_SGD only; they are checked for every kind)
+    FLSIM_REQUIRE(o->momentum >= 0.0, "Invalid momentum value: %g", o->momentum);
+    FLSIM_REQUIRE(!o->nesterov || (o->momentum > 0.0 && o->dampening == 0.0),
+                  "Nesterov momentum requires a momentum and zero dampening");
+    return 0;
+}
+
+int make_opt_launch(const flsim_optim* o, int divisor, long step, OptLaunch* ol) {
+    RC(check_optim(o));
+    memset(ol, 0, sizeof(*ol));
+    if (o->kind == FLSIM_OPT_SGD) {
+        FLSIM_REQUIRE(divisor > 0 && divisor < (1 << 24), "divisor %d out of range", divisor);
+        FLSIM_REQUIRE(step >= 1, "step must be >= 1");
+        ol->ok = o->momentum != 0.0 ? OK_SGDM : OK_SGD;
+        ol->ac.fk = (float)divisor;                      // rule(): mean = sum / k
+        {
+            volatile float one = 1.f, fk = (float)divisor;   // RN(1/k) in fp32, not via double
+            ol->ac.rk = one / fk;
+        }
+        ol->oc.wd = (float)o->weight_decay;
+        ol->oc.mu = (float)o->momentum;
+        ol->oc.omd = (float)(1.0 - o->dampening);
+        ol->oc.neg_lr = (float)(-o->lr);
+        ol->oc.flags = (o->weight_decay != 0.0 ? OF_WD : 0) | (o->nesterov ? OF_NESTEROV : 0) |
+                       (step == 1 ? OF_FIRST : 0);
+        return 0;
+    }
+    RC(make_adam_const(divisor, step, o->lr, o->beta1, o->beta2, o->eps, &ol->ac));
+    // no decay: the Adam kernels as they were (AdamW's p * f32(1 - lr * 0) = p exactly)
+    ol->ok = o->weight_decay != 0.0 ? OK_ADAMD : OK_ADAM;
+    if (o->kind == FLSIM_OPT_ADAMW) {
+        ol->oc.wd = (float)(1.0 - o->lr * o->weight_decay);
+        ol->oc.flags = OF_DECOUPLED | OF_WD;
+    } else {
+        ol->oc.wd = (float)o->weight_decay;
+        ol->oc.flags = OF_WD;
+    }
     return 0;
 }
 
@@ -859,6 +967,32 @@ int make_rule(const flsim_rule* r, RuleProg* R) {
 int slab_step_launch(float* gradstate, const StepPlan& plan, long cnt_off, long part_off,
                      float* S_out, const RuleProg* rule, const AdamConst* ac, float* p, float* m,
                      float* v, long P, hipStream_t stream) {
+    OptLaunch ol{};
+    ol.ok = OK_ADAM;
+    if (rule) {
+        FLSIM_REQUIRE(ac, "null pointer");
+        ol.ac = *ac;
+    }
+    return slab_step_launch_optim(gradstate, plan, cnt_off, part_off, S_out, rule, ol, p, m, v, P,
+                                  stream);
+}
+
+// the fused step's two rule() + update launches of one kind
+template <int OK>
+static void launch_slab_rule(bool seq, unsigned nblk, hipStream_t stream, const ProbeSlot& ps,
+                             const StepArgs& A) {
+    if (!seq)
+        hipExtLaunchKernelGGL((k_slab_step<true, true, OK>), dim3(nblk), dim3(256), 0, stream,
+                              ps.start, ps.stop, 0, A);
+    else
+        hipExtLaunchKernelGGL((k_slab_step_seq<OK>), dim3(nblk), dim3(256), 0, stream, ps.start,
+                              ps.stop, 0, A);
+}
+
+int slab_step_launch_optim(float* gradstate, const StepPlan& plan, long cnt_off, long part_off,
+                           float* S_out, const RuleProg* rule, const OptLaunch& ol, float* p,
+                           float* m, float* v, long P, hipStream_t stream) {
+    const int nstate = opt_n_state(ol.ok);
     StepArgs A{};
     A.base = gradstate;
     A.cnt_off = cnt_off;
@@ -871,9 +1005,10 @@ int slab_step_launch(float* gradstate, const StepPlan& plan, long cnt_off, long 
     A.units = plan.units;
     for (int i = 0; i < plan.nseg; ++i) A.seg[i] = plan.seg[i];
     if (rule) {
-        FLSIM_REQUIRE(p && m && v && ac, "null pointer");
+        FLSIM_REQUIRE(p && (m || nstate < 1) && (v || nstate < 2), "null pointer");
         A.R = *rule;
-        A.ac = *ac;
+        A.ac = ol.ac;
+        A.oc = ol.oc;
     }
     // FLSIM_STEP_UNITS="lo,hi" (measurement only): run units [lo, hi) of the plan -- whole
     // segments, so every split tile completes and resets its counter
@@ -895,29 +1030,52 @@ int slab_step_launch(float* gradstate, const StepPlan& plan, long cnt_off, long 
     if (const char* env = lab_env("FLSIM_STEP_NO_INTERLEAVE"))
         if (atoi(env)) A.il_n = 0;
     const unsigned nblk = (unsigned)(u_hi - A.u_lo);
-    // algorithmic HBM bytes: every slab byte once; S_out written; p, m, v read + written; each
-    // distinct entry array read once
+    // algorithmic HBM bytes: every slab byte once; S_out written; p and the kind's state arrays
+    // (m, v: 2, 1 or 0 of them) read + written; each distinct entry array read once
     double slab_read = 0.0;
     for (int i = 0; i < plan.nseg; ++i)
         slab_read += (double)(plan.seg[i].zlim < plan.seg[i].Z ? plan.seg[i].zlim : plan.seg[i].Z) *
                      plan.seg[i].n;
     double bytes = 4.0 * slab_read + (S_out ? 4.0 * P : 0.0);
-    if (rule) bytes += 4.0 * (double)P * (6 + rule->distinct);
+    if (rule) bytes += 4.0 * (double)P * (2 + 2 * nstate + rule->distinct);
     const ProbeSlot ps = probe_begin();
     if (!rule) {
         hipExtLaunchKernelGGL(k_slab_step<false, true>, dim3(nblk), dim3(256), 0, stream, ps.start,
                               ps.stop, 0, A);
-    } else if (rule->prog == nullptr) {
-        hipExtLaunchKernelGGL(k_slab_step<true, true>, dim3(nblk), dim3(256), 0, stream, ps.start,
-                              ps.stop, 0, A);
     } else {
-        RC(stage_program(*rule, stream));
-        hipExtLaunchKernelGGL(k_slab_step_seq, dim3(nblk), dim3(256), 0, stream, ps.start,
-                              ps.stop, 0, A);
+        const bool seq = rule->prog != nullptr;
+        if (seq) RC(stage_program(*rule, stream));
+        switch (ol.ok) {
+            case OK_ADAM: launch_slab_rule<OK_ADAM>(seq, nblk, stream, ps, A); break;
+            case OK_ADAMD: launch_slab_rule<OK_ADAMD>(seq, nblk, stream, ps, A); break;
+            case OK_SGDM: launch_slab_rule<OK_SGDM>(seq, nblk, stream, ps, A); break;
+            default: launch_slab_rule<OK_SGD>(seq, nblk, stream, ps, A); break;
+        }
     }
     FLSIM_LAUNCH_CHECK();
     const int kid = !rule ? K_SLABSUM : (rule->prog == nullptr ? K_STEP : K_STEP_SEQ);
     return probe_end(ps, kid, bytes);
+}
+
+// the streaming launch of one kind: the register-array form (reference order, <= 2 entry arrays,
+// G groups per thread) or the LDS-staged one (inline or staged program)
+template <int OK>
+static void launch_agg(bool reg, int G, dim3 grid, hipStream_t stream, const ProbeSlot& ps,
+                       const AggArgs& A) {
+    if (reg) {
+        auto k = G == 2 ? (A.R.narr == 0 ? k_agg_stream_reg<2, 0, OK>
+                           : A.R.narr == 1 ? k_agg_stream_reg<2, 1, OK>
+                                           : k_agg_stream_reg<2, 2, OK>)
+                        : (A.R.narr == 0 ? k_agg_stream_reg<1, 0, OK>
+                           : A.R.narr == 1 ? k_agg_stream_reg<1, 1, OK>
+                                           : k_agg_stream_reg<1, 2, OK>);
+        hipExtLaunchKernelGGL(k, grid, dim3(256), 0, stream, ps.start, ps.stop, 0, A);
+    } else if (A.R.prog == nullptr)
+        hipExtLaunchKernelGGL((k_agg_stream<true, OK>), grid, dim3(256), 0, stream, ps.start,
+                              ps.stop, 0, A);
+    else
+        hipExtLaunchKernelGGL((k_agg_stream<false, OK>), grid, dim3(256), 0, stream, ps.start,
+                              ps.stop, 0, A);
 }
 
 }  // namespace flsim
@@ -942,7 +1100,23 @@ int flsim_aggregate_adam_rule_push(const float* S, float* S_out, const flsim_rul
                                    float* m, float* v, long P, const long* tensor_sizes,
                                    int n_tensors, long step, double lr, double beta1, double beta2,
                                    double eps, hipStream_t stream) {
-    FLSIM_REQUIRE(S && p && m && v && tensor_sizes && rule, "null pointer");
+    const flsim_optim o = adam_optim(lr, beta1, beta2, eps);
+    return flsim_aggregate_optim_rule_push(S, S_out, rule, p, m, v, P, tensor_sizes, n_tensors,
+                                           step, &o, stream);
+}
+
+// rule() + the update rule of `optim` (include/flsim.h); m / v may be null where the kind does
+// not own them
+int flsim_aggregate_optim_rule_push(const float* S, float* S_out, const flsim_rule* rule, float* p,
+                                    float* m, float* v, long P, const long* tensor_sizes,
+                                    int n_tensors, long step, const flsim_optim* optim,
+                                    hipStream_t stream) {
+    RC(check_optim(optim));
+    const int nstate = optim->kind == FLSIM_OPT_SGD ? (optim->momentum != 0.0 ? 1 : 0) : 2;
+    FLSIM_REQUIRE(S && p && (m || nstate < 1) && (v || nstate < 2) && tensor_sizes && rule,
+                  "null pointer");
+    if (nstate < 2) v = nullptr;
+    if (nstate < 1) m = nullptr;
     FLSIM_REQUIRE(P > 0 && P < (1L << 31), "P = %ld out of range", P);
     const uintptr_t al = (uintptr_t)S | (uintptr_t)p | (uintptr_t)m | (uintptr_t)v |
                          (uintptr_t)S_out;
@@ -951,7 +1125,10 @@ int flsim_aggregate_adam_rule_push(const float* S, float* S_out, const flsim_rul
     RC(make_rule(rule, &A.R));
     for (int q = 0; q < A.R.narr; ++q)
         FLSIM_REQUIRE(((uintptr_t)A.R.arr[q] & 15) == 0, "entry arrays must be 16-byte aligned");
-    RC(make_adam_const(rule->k, step, lr, beta1, beta2, eps, &A.ac));
+    OptLaunch ol;
+    RC(make_opt_launch(optim, rule->k, step, &ol));
+    A.ac = ol.ac;
+    A.oc = ol.oc;
     // the register-array stream for the reference order with <= 2 entry arrays: 2 float4 groups
     // per thread without a stale array, 1 with (tools/agg_bench.py, profiles/r03a/agg_bench.txt:
     // 28.2 vs 28.4 us for k = 512; 32.0 vs 33.1 us for k = 513 with the stale S_{t-d});
@@ -1016,24 +1193,18 @@ int flsim_aggregate_adam_rule_push(const float* S, float* S_out, const flsim_rul
             const long b1 = ((A.tail_hi[j] - 1) / 4 - A.g0) / gpb;
             for (long b = b0; b <= b1; ++b) add_block(b);
         }
-        // algorithmic HBM bytes: read S_t + the distinct entry arrays + p, m, v; write p, m, v
-        // [+ S_out]
-        const double bytes = 4.0 * (double)(hi - lo) * (7 + A.R.distinct + (S_out ? 1 : 0));
+        // algorithmic HBM bytes: read S_t + the distinct entry arrays + p and the kind's state
+        // arrays (m, v: 2, 1 or 0 of them); write p and the state arrays [+ S_out]
+        const double bytes =
+            4.0 * (double)(hi - lo) * (3 + 2 * nstate + A.R.distinct + (S_out ? 1 : 0));
         const ProbeSlot ps = probe_begin();
         const dim3 grid((unsigned)(nblk + A.nedge));
-        if (reg) {
-            auto k = G == 2 ? (A.R.narr == 0 ? k_agg_stream_reg<2, 0>
-                               : A.R.narr == 1 ? k_agg_stream_reg<2, 1> : k_agg_stream_reg<2, 2>)
-                            : (A.R.narr == 0 ? k_agg_stream_reg<1, 0>
-                               : A.R.narr == 1 ? k_agg_stream_reg<1, 1> : k_agg_stream_reg<1, 2>);
-            hipExtLaunchKernelGGL(k, grid, dim3(256), 0, stream, ps.start, ps.stop, 0, A);
-        } else if (A.R.prog == nullptr)
-            hipExtLaunchKernelGGL(k_agg_stream<true>, grid, dim3(256),
-                                  0, stream, ps.start, ps.stop, 0, A);
-        else {
-            RC(stage_program(A.R, stream));
-            hipExtLaunchKernelGGL(k_agg_stream<false>, grid, dim3(256),
-                                  0, stream, ps.start, ps.stop, 0, A);
+        if (!reg && A.R.prog != nullptr) RC(stage_program(A.R, stream));
+        switch (ol.ok) {
+            case OK_ADAM: launch_agg<OK_ADAM>(reg, G, grid, stream, ps, A); break;
+            case OK_ADAMD: launch_agg<OK_ADAMD>(reg, G, grid, stream, ps, A); break;
+            case OK_SGDM: launch_agg<OK_SGDM>(reg, G, grid, stream, ps, A); break;
+            default: launch_agg<OK_SGD>(reg, G, grid, stream, ps, A); break;
         }
         FLSIM_LAUNCH_CHECK();
         if (probe_end(ps, A.R.prog == nullptr ? K_AGG : K_AGG_SEQ, bytes)) return 2;

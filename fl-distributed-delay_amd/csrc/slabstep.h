@@ -133,6 +133,24 @@ struct AdamConst {
     float w1, b2, w2, bc2s, rbc2s, eps, neg_ss, fk, rk;
 };
 
+// The update rule a launch applies (compile-time: the kinds differ in the arrays they stream).
+//   OK_ADAM   torch.optim.Adam, no weight decay: p, m, v
+//   OK_ADAMD  Adam with weight_decay (coupled L2) or AdamW (decoupled): p, m, v
+//   OK_SGDM   torch.optim.SGD with momentum != 0: p and the momentum buffer in m; v untouched
+//   OK_SGD    torch.optim.SGD with momentum == 0: p only; m and v untouched
+enum OptKind { OK_ADAM = 0, OK_ADAMD = 1, OK_SGDM = 2, OK_SGD = 3 };
+constexpr int opt_n_state(int ok) { return ok <= OK_ADAMD ? 2 : (ok == OK_SGDM ? 1 : 0); }
+
+// what the kinds other than OK_ADAM need besides AdamConst (whose fk, rk every kind uses)
+enum { OF_DECOUPLED = 1, OF_WD = 2, OF_NESTEROV = 4, OF_FIRST = 8 };
+struct OptConst {
+    float wd;       // weight_decay; OK_ADAMD decoupled: f32(1 - lr * weight_decay)
+    float mu;       // momentum
+    float omd;      // f32(1 - dampening)
+    float neg_lr;   // f32(-lr)
+    int flags;      // OF_*: decoupled decay, weight_decay != 0, nesterov, step 1 (buf = g)
+};
+
 // rule(): which program and which arrays (host side, see flsim_rule in include/flsim.h)
 struct RuleProg {
     const int32_t* prog;            // device program, or nullptr: iprog
@@ -153,9 +171,32 @@ int slab_step_launch(float* gradstate, const StepPlan& plan, long cnt_off, long 
                      float* S_out, const RuleProg* rule, const AdamConst* ac, float* p, float* m,
                      float* v, long P, hipStream_t stream);
 
+// a validated flsim_optim in launch form: the kernel kind and its constants
+struct OptLaunch {
+    int ok;         // OptKind
+    AdamConst ac;
+    OptConst oc;
+};
+// the same with a chosen update rule; m / v may be null where the kind does not own them
+int slab_step_launch_optim(float* gradstate, const StepPlan& plan, long cnt_off, long part_off,
+                           float* S_out, const RuleProg* rule, const OptLaunch& ol, float* p,
+                           float* m, float* v, long P, hipStream_t stream);
+
 // host helpers shared with server.hip's C-ABI
 int make_rule(const flsim_rule* r, RuleProg* out);
 int make_adam_const(int divisor, long step, double lr, double beta1, double beta2, double eps,
                     AdamConst* ac);
+// hyper-parameter checks (the cases where torch raises ValueError); before any pointer check
+int check_optim(const flsim_optim* o);
+int make_opt_launch(const flsim_optim* o, int divisor, long step, OptLaunch* ol);
+inline flsim_optim adam_optim(double lr, double beta1, double beta2, double eps) {
+    flsim_optim o{};
+    o.kind = FLSIM_OPT_ADAM;
+    o.lr = lr;
+    o.beta1 = beta1;
+    o.beta2 = beta2;
+    o.eps = eps;
+    return o;
+}
 
 }  // namespace flsim

@@ -596,17 +596,28 @@ static int vgg_end_epoch(void* gradstate, float* grad_out, hipStream_t stream) {
 
 // the same reduction fused with rule() + Adam (world = 1)
 template <bool BN>
-static int vgg_server_step(void* gradstate, float* S_out, const flsim_rule* rule, float* p,
-                           float* m, float* v, long step, double lr, double beta1, double beta2,
-                           double eps, hipStream_t stream) {
-    FLSIM_REQUIRE(gradstate && rule && p && m && v, "null pointer");
+static int vgg_server_step_optim(void* gradstate, float* S_out, const flsim_rule* rule, float* p,
+                                 float* m, float* v, long step, const flsim_optim* optim,
+                                 hipStream_t stream) {
+    RC(check_optim(optim));
+    const int nstate = optim->kind == FLSIM_OPT_SGD ? (optim->momentum != 0.0 ? 1 : 0) : 2;
+    FLSIM_REQUIRE(gradstate && rule && p && (m || nstate < 1) && (v || nstate < 2),
+                  "null pointer");
     VGrad g = vgs_layout((float*)gradstate, BN);
     RuleProg R;
     RC(make_rule(rule, &R));
-    AdamConst ac;
-    RC(make_adam_const(rule->k, step, lr, beta1, beta2, eps, &ac));
-    return slab_step_launch((float*)gradstate, g.plan, g.cnt_off, g.part_off, S_out, &R, &ac, p,
-                            m, v, voff(BN).total, stream);
+    OptLaunch ol;
+    RC(make_opt_launch(optim, rule->k, step, &ol));
+    return slab_step_launch_optim((float*)gradstate, g.plan, g.cnt_off, g.part_off, S_out, &R, ol,
+                                  p, m, v, voff(BN).total, stream);
+}
+
+template <bool BN>
+static int vgg_server_step(void* gradstate, float* S_out, const flsim_rule* rule, float* p,
+                           float* m, float* v, long step, double lr, double beta1, double beta2,
+                           double eps, hipStream_t stream) {
+    const flsim_optim o = adam_optim(lr, beta1, beta2, eps);
+    return vgg_server_step_optim<BN>(gradstate, S_out, rule, p, m, v, step, &o, stream);
 }
 
 }  // namespace flsim
@@ -707,6 +718,12 @@ int flsim_vgg11_server_step(void* gradstate, float* S_out, const flsim_rule* rul
                                   stream);
 }
 
+int flsim_vgg11_server_step_optim(void* gradstate, float* S_out, const flsim_rule* rule, float* p,
+                                  float* m, float* v, long step, const flsim_optim* optim,
+                                  hipStream_t stream) {
+    return vgg_server_step_optim<false>(gradstate, S_out, rule, p, m, v, step, optim, stream);
+}
+
 // ---- vgg11_bn -------------------------------------------------------------------------------
 long flsim_vgg11_bn_param_count(void) { return voff(true).total; }
 
@@ -773,6 +790,12 @@ int flsim_vgg11_bn_server_step(void* gradstate, float* S_out, const flsim_rule* 
                                double beta2, double eps, hipStream_t stream) {
     return vgg_server_step<true>(gradstate, S_out, rule, p, m, v, step, lr, beta1, beta2, eps,
                                  stream);
+}
+
+int flsim_vgg11_bn_server_step_optim(void* gradstate, float* S_out, const flsim_rule* rule,
+                                     float* p, float* m, float* v, long step,
+                                     const flsim_optim* optim, hipStream_t stream) {
+    return vgg_server_step_optim<true>(gradstate, S_out, rule, p, m, v, step, optim, stream);
 }
 
 int flsim_vgg11_bn_update_running(float* running, const float* bn_stats, int n_workers,

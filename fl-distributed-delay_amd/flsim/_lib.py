@@ -41,6 +41,8 @@ EXPORTS = [
     "flsim_vgg11_bn_fwd_bwd_loaded_rows",
     "flsim_comm_unique_id", "flsim_comm_create", "flsim_comm_size", "flsim_comm_rank",
     "flsim_allreduce_sum", "flsim_comm_destroy",
+    "flsim_aggregate_optim_rule_push", "flsim_pn1_server_step_optim",
+    "flsim_vgg11_server_step_optim", "flsim_vgg11_bn_server_step_optim",
 ]
 COMM_ID_BYTES = 128      # FLSIM_COMM_ID_BYTES
 
@@ -57,6 +59,17 @@ class FlsimRule(ctypes.Structure):
     _fields_ = [("k", ctypes.c_int32), ("c", ctypes.c_int32), ("prog", ctypes.c_void_p),
                 ("info", ctypes.c_int32 * 4), ("n_arrays", ctypes.c_int32),
                 ("arrays", ctypes.c_void_p * MAX_ARRAYS)]
+
+
+OPT_KINDS = {"adam": 0, "adamw": 1, "sgd": 2}      # FLSIM_OPT_ADAM / _ADAMW / _SGD
+
+
+class FlsimOptim(ctypes.Structure):
+    """flsim_optim (include/flsim.h): the update rule of a server step."""
+    _fields_ = [("kind", ctypes.c_int32), ("nesterov", ctypes.c_int32), ("lr", ctypes.c_double),
+                ("beta1", ctypes.c_double), ("beta2", ctypes.c_double), ("eps", ctypes.c_double),
+                ("weight_decay", ctypes.c_double), ("momentum", ctypes.c_double),
+                ("dampening", ctypes.c_double)]
 
 
 class WorkerRec(ctypes.Structure):
@@ -103,6 +116,7 @@ def lib():
         f("eval_input").argtypes = [vp, vp, ctypes.c_int, vp, vp, ctypes.c_int] + bn + [vp, vp]
         f("server_step").argtypes = [vp, vp, vp, vp, vp, vp, ctypes.c_long, ctypes.c_double,
                                      ctypes.c_double, ctypes.c_double, ctypes.c_double, vp]
+        f("server_step_optim").argtypes = [vp, vp, vp, vp, vp, vp, ctypes.c_long, vp, vp]
         f("eval_pool").argtypes = [vp, vp, ctypes.c_int, vp, vp, ctypes.c_int, ctypes.c_int,
                                    vp] + bn + [vp, vp]
     L.flsim_pn1_workspace_split_part.argtypes = [ctypes.c_int]
@@ -148,6 +162,8 @@ def lib():
     L.flsim_aggregate_adam_rule_push.argtypes = [
         vp, vp, vp, vp, vp, vp, ctypes.c_long, vp, ctypes.c_int,
         ctypes.c_long, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, vp]
+    L.flsim_aggregate_optim_rule_push.argtypes = [
+        vp, vp, vp, vp, vp, vp, ctypes.c_long, vp, ctypes.c_int, ctypes.c_long, vp, vp]
     L.flsim_cascade_program.argtypes = [ctypes.c_int, vp, vp, ctypes.c_int, vp, ctypes.c_int, vp]
     L.flsim_cascade_eval_host.argtypes = [vp, vp, vp, vp, ctypes.c_int, vp, ctypes.c_long, vp]
     L.flsim_probe_enable.argtypes = [ctypes.c_int]

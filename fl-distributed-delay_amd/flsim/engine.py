@@ -13,11 +13,13 @@ keeps its BatchNorm running buffers.  Both entry-point families share one contra
 from __future__ import annotations
 
 import ctypes
+import dataclasses
 
 import numpy as np
 import torch
 
-from ._lib import MAX_ARRAYS, FlsimRule, WorkerRec, check, lib, ptr, stream_ptr
+from ._lib import (MAX_ARRAYS, OPT_KINDS, FlsimOptim, FlsimRule, WorkerRec, check, lib, ptr,
+                   stream_ptr)
 
 # named_parameters() order of models.py:PerformantNet1 (models.py:13-25)
 PN1_SHAPES = [
@@ -62,6 +64,60 @@ VGG11_BN_BUFFERS = [(f"features.{i + 1}", int(shp[0]))
 PN1_SIZES = [int(np.prod(s)) for _, s in PN1_SHAPES]
 VGG11_SIZES = [int(np.prod(s)) for _, s in VGG11_SHAPES]
 SAMPLES_PER_WORKER = 128
+
+
+@dataclasses.dataclass(frozen=True)
+class Optim:
+    """flsim_optim (include/flsim.h): the update rule of a server step, torch's hyper-parameter
+    names.  kind "adam" = torch.optim.Adam (weight_decay: coupled L2), "adamw" = torch.optim.AdamW
+    (decoupled), "sgd" = torch.optim.SGD (momentum, dampening, weight_decay, nesterov)."""
+    kind: str = "adam"
+    lr: float = 1e-3
+    betas: tuple = (0.9, 0.999)
+    eps: float = 1e-8
+    weight_decay: float = 0.0
+    momentum: float = 0.0
+    dampening: float = 0.0
+    nesterov: bool = False
+
+    @property
+    def n_state(self):
+        """State arrays the kind owns: 2 (m, v), 1 (the momentum buffer in m) or 0."""
+        if self.kind != "sgd":
+            return 2
+        return 1 if self.momentum != 0 else 0
+
+    def validate(self):
+        """The ValueErrors torch's constructors raise (the library refuses the same cases)."""
+        if self.kind not in OPT_KINDS:
+            raise ValueError(f"optimizer {self.kind!r} (supported: {sorted(OPT_KINDS)})")
+        if not self.lr >= 0:
+            raise ValueError(f"Invalid learning rate: {self.lr}")
+        if not self.weight_decay >= 0:
+            raise ValueError(f"Invalid weight_decay value: {self.weight_decay}")
+        # (momentum, dampening and nesterov act for "sgd" only; they are checked for every kind)
+        if not self.momentum >= 0:
+            raise ValueError(f"Invalid momentum value: {self.momentum}")
+        if self.nesterov and (self.momentum <= 0 or self.dampening != 0):
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        return self
+
+    def c_struct(self):
+        o = FlsimOptim()
+        o.kind = OPT_KINDS.get(self.kind, -1)
+        o.nesterov = int(bool(self.nesterov))
+        o.lr = float(self.lr)
+        o.beta1, o.beta2 = float(self.betas[0]), float(self.betas[1])
+        o.eps = float(self.eps)
+        o.weight_decay = float(self.weight_decay)
+        o.momentum = float(self.momentum)
+        o.dampening = float(self.dampening)
+        return o
+
+
+def as_optim(optim):
+    """An Optim from an Optim or a dict of its fields."""
+    return optim if isinstance(optim, Optim) else Optim(**dict(optim))
 
 
 def padded(n, q=64):
@@ -258,9 +314,18 @@ class NetEngine:
     def end_epoch(self, grad_out):
         check(self._fn("end_epoch")(ptr(self.gradstate), ptr(grad_out), stream_ptr()))
 
-    def server_step(self, S_out, rule, theta, m, v, step, lr=1e-3, betas=(0.9, 0.999), eps=1e-8):
+    def server_step(self, S_out, rule, theta, m, v, step, lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
+                    optim=None):
         """world = 1: the epoch's slabs -> S_t [-> S_out] -> rule() + Adam in one launch
-        (flsim_<net>_server_step).  rule: a Rule."""
+        (flsim_<net>_server_step).  rule: a Rule.  optim (an Optim or a dict of its fields): that
+        update rule instead (flsim_<net>_server_step_optim); m / v may be None where the kind
+        owns no such array."""
+        if optim is not None:
+            o = as_optim(optim).c_struct()
+            check(self._fn("server_step_optim")(
+                ptr(self.gradstate), ptr(S_out), ctypes.byref(rule.c_rule), ptr(theta), ptr(m),
+                ptr(v), int(step), ctypes.byref(o), stream_ptr()))
+            return
         check(self._fn("server_step")(
             ptr(self.gradstate), ptr(S_out), ctypes.byref(rule.c_rule), ptr(theta), ptr(m), ptr(v),
             int(step), float(lr), float(betas[0]), float(betas[1]), float(eps), stream_ptr()))
@@ -314,18 +379,20 @@ class NetEngine:
 
     # -- server step ------------------------------------------------------------------------------
     def aggregate_adam(self, S, c, stale, theta, m, v, step, lr=1e-3, betas=(0.9, 0.999),
-                       eps=1e-8):
+                       eps=1e-8, optim=None):
         """stale: list of device tensors (or None = zero entry)."""
-        aggregate_adam(S, c, stale, theta, m, v, step, self.SIZES, lr, betas, eps)
+        aggregate_adam(S, c, stale, theta, m, v, step, self.SIZES, lr, betas, eps, optim=optim)
 
-    def aggregate_adam_sum(self, S, k, theta, m, v, step, lr=1e-3, betas=(0.9, 0.999), eps=1e-8):
-        aggregate_adam_sum(S, k, theta, m, v, step, self.SIZES, lr, betas, eps)
+    def aggregate_adam_sum(self, S, k, theta, m, v, step, lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
+                           optim=None):
+        aggregate_adam_sum(S, k, theta, m, v, step, self.SIZES, lr, betas, eps, optim=optim)
 
     def aggregate_rule(self, S, rule, theta, m, v, step, lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
-                       S_out=None):
-        """rule() + Adam from S_t in a buffer; S_out (optional): S_t is also written there in
-        the same pass (the FIFO slot of a tick epoch at world > 1)."""
-        aggregate_rule(S, rule, theta, m, v, step, self.SIZES, lr, betas, eps, S_out=S_out)
+                       S_out=None, optim=None):
+        """rule() + Adam (or the update rule `optim`) from S_t in a buffer; S_out (optional): S_t
+        is also written there in the same pass (the FIFO slot of a tick epoch at world > 1)."""
+        aggregate_rule(S, rule, theta, m, v, step, self.SIZES, lr, betas, eps, S_out=S_out,
+                       optim=optim)
 
 
 class PN1Engine(NetEngine):
@@ -442,10 +509,19 @@ def engine_for_parameters(names):
                               "vgg11_bn")
 
 
-def aggregate_adam(S, c, stale, theta, m, v, step, sizes, lr=1e-3, betas=(0.9, 0.999), eps=1e-8):
+def aggregate_adam(S, c, stale, theta, m, v, step, sizes, lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
+                   optim=None):
     """Fused rule() + Adam (main.py:23-25 + agents.py:9-21) over a flat parameter vector whose
-    tensors have numel `sizes` (named_parameters order).  stale: device tensors or None (zeros)."""
+    tensors have numel `sizes` (named_parameters order).  stale: device tensors or None (zeros).
+    optim: the update rule instead of Adam(lr, betas, eps) (see aggregate_rule)."""
     ns = len(stale)
+    if optim is not None:
+        if not (c >= 0 and ns <= 8):
+            raise ValueError(f"bad entry counts c={c} ns={ns}")
+        if c + ns == 0:
+            raise IndexError("empty weight_ups (reference: IndexError in rule, main.py:25)")
+        aggregate_rule(S, Rule(c + ns, stale, c=c), theta, m, v, step, sizes, optim=optim)
+        return
     arr = (ctypes.c_void_p * max(1, ns))(*[(t.data_ptr() if t is not None else None)
                                            for t in stale])
     csz = (ctypes.c_long * len(sizes))(*[int(n) for n in sizes])
@@ -454,9 +530,15 @@ def aggregate_adam(S, c, stale, theta, m, v, step, sizes, lr=1e-3, betas=(0.9, 0
         int(step), float(lr), float(betas[0]), float(betas[1]), float(eps), stream_ptr()))
 
 
-def aggregate_adam_sum(S, k, theta, m, v, step, sizes, lr=1e-3, betas=(0.9, 0.999), eps=1e-8):
+def aggregate_adam_sum(S, k, theta, m, v, step, sizes, lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
+                       optim=None):
     """Independent-entry semantics: S = the sum of the k distinct weight_ups entries; mean = S / k
-    then the same Adam step (flsim_aggregate_adam_sum)."""
+    then the same Adam step (flsim_aggregate_adam_sum), or the update rule `optim`."""
+    if optim is not None:
+        if k <= 0:
+            raise IndexError("empty weight_ups (reference: IndexError in rule, main.py:25)")
+        aggregate_rule(S, Rule(k, [], c=1), theta, m, v, step, sizes, optim=optim)
+        return
     csz = (ctypes.c_long * len(sizes))(*[int(n) for n in sizes])
     check(lib().flsim_aggregate_adam_sum(
         ptr(S), int(k), ptr(theta), ptr(m), ptr(v), sum(int(n) for n in sizes), csz, len(sizes),
@@ -544,9 +626,18 @@ class ProgramStager:
 
 
 def aggregate_rule(S, rule, theta, m, v, step, sizes, lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
-                   S_out=None):
-    """rule() + Adam from S_t in a buffer (flsim_aggregate_adam_rule_push; S_out may be None)."""
+                   S_out=None, optim=None):
+    """rule() + Adam from S_t in a buffer (flsim_aggregate_adam_rule_push; S_out may be None).
+    optim (an Optim or a dict of its fields): that update rule instead of Adam(lr, betas, eps)
+    (flsim_aggregate_optim_rule_push); m / v may be None where the kind owns no such array (SGD:
+    v; SGD without momentum: m and v) and are left untouched when given."""
     csz = (ctypes.c_long * len(sizes))(*[int(n) for n in sizes])
+    if optim is not None:
+        o = as_optim(optim).c_struct()
+        check(lib().flsim_aggregate_optim_rule_push(
+            ptr(S), ptr(S_out), ctypes.byref(rule.c_rule), ptr(theta), ptr(m), ptr(v),
+            sum(int(n) for n in sizes), csz, len(sizes), int(step), ctypes.byref(o), stream_ptr()))
+        return
     check(lib().flsim_aggregate_adam_rule_push(
         ptr(S), ptr(S_out), ctypes.byref(rule.c_rule), ptr(theta), ptr(m), ptr(v),
         sum(int(n) for n in sizes), csz, len(sizes), int(step), float(lr), float(betas[0]),

@@ -24,7 +24,7 @@ import numpy as np
 import torch
 
 from .data import DevicePool, make_test_pool
-from .engine import PN1_SIZES, ProgramStager, Rule, engine_class, padded, split_views
+from .engine import PN1_SIZES, Optim, ProgramStager, Rule, engine_class, padded, split_views
 from .schedule import Schedule, reference_delays
 
 SEMANTICS = ("reference", "torch1", "independent")
@@ -61,7 +61,8 @@ class FLSimulation:
                  group=None, max_throttle=32, pool=None, betas=(0.9, 0.999), eps=1e-8,
                  engine=None, device_pool=None, test_pool=None, model="PerformantNet1",
                  fused=True, keep_S=False, batch_size=128, distributed=None,
-                 collective="torch"):
+                 collective="torch", optimizer="adam", weight_decay=0.0, momentum=0.0,
+                 dampening=0.0, nesterov=False):
         if semantics not in SEMANTICS:
             raise NotImplementedError(f"semantics {semantics!r} (supported: {SEMANTICS})")
         self.n = int(n_workers)
@@ -72,6 +73,15 @@ class FLSimulation:
         self.delay_arg = delay
         self.throttle = bool(throttle)
         self.lr, self.betas, self.eps = float(lr), tuple(betas), float(eps)
+        # Central(model, optim)'s optimizer (main.py:106 builds Adam(lr)): "adam" (weight_decay:
+        # coupled L2), "adamw" (decoupled) or "sgd" (momentum, dampening, weight_decay, nesterov);
+        # refused here, before any device use, where torch's constructor raises ValueError
+        self.optim = Optim(kind=str(optimizer), lr=self.lr, betas=self.betas, eps=self.eps,
+                           weight_decay=float(weight_decay), momentum=float(momentum),
+                           dampening=float(dampening), nesterov=bool(nesterov)).validate()
+        # plain Adam keeps the flsim_aggregate_adam* / flsim_*_server_step entry points
+        self._optim_arg = None if (self.optim.kind == "adam" and self.optim.weight_decay == 0) \
+            else self.optim
         self.seed = int(seed)
         self.semantics = semantics
         self.dropout = bool(dropout)
@@ -144,8 +154,10 @@ class FLSimulation:
         self.Ppad = padded(P)
         th = default_theta(self.seed, model) if theta0 is None else torch.as_tensor(theta0)
         self.theta = th.to(self.device, torch.float32).contiguous().clone()
-        self.m = torch.zeros_like(self.theta)
-        self.v = torch.zeros_like(self.theta)
+        # optimizer state: Adam family m = exp_avg, v = exp_avg_sq; SGD with momentum m = the
+        # momentum buffer and no v; SGD without momentum neither
+        self.m = torch.zeros_like(self.theta) if self.optim.n_state >= 1 else None
+        self.v = torch.zeros_like(self.theta) if self.optim.n_state >= 2 else None
         self.step = 0
         # [S_t | losses of the computing workers | their per-call BatchNorm statistics (vgg11_bn)]
         # -- one all-reduce per epoch when world > 1 (each rank fills only its workers' rows)
@@ -363,6 +375,8 @@ class FLSimulation:
         self.step += 1
         rule = self._rule(plan, stale)
         hp = dict(lr=self.lr, betas=self.betas, eps=self.eps)
+        if self._optim_arg is not None:
+            hp = dict(optim=self._optim_arg)
         if fused and not self.keep_S:
             eng.server_step(push, rule, self.theta, self.m, self.v, self.step, **hp)
         elif fused:
@@ -458,7 +472,8 @@ class FLSimulation:
             self._all_reduce(self.comm[:self.Ppad + len(fast)])
         self.step += 1
         eng.aggregate_adam_sum(S, len(fast) + len(plan.stale), self.theta, self.m, self.v,
-                               self.step, self.lr, self.betas, self.eps)
+                               self.step, self.lr, self.betas, self.eps,
+                               **({"optim": self._optim_arg} if self._optim_arg else {}))
         self.trace.append(plan)
         if sync_loss:
             lv = losses.detach().cpu().numpy()
@@ -531,15 +546,21 @@ class FLSimulation:
                        "throttle": self.throttle, "seed": self.seed, "semantics": self.semantics,
                        "dropout": self.dropout, "lr": self.lr, "betas": list(self.betas),
                        "eps": self.eps, "max_throttle": self.max_throttle,
-                       "batch_size": self.batch_size},
+                       "batch_size": self.batch_size, **self._optim_config()},
             "epoch": len(self.trace), "step": self.step,
-            "theta": self.theta.detach().cpu(), "m": self.m.detach().cpu(),
-            "v": self.v.detach().cpu(),
+            "theta": self.theta.detach().cpu(),
+            # the state arrays the optimizer owns (SGD: no v; without momentum no m either)
+            **{k: a.detach().cpu() for k, a in (("m", self.m), ("v", self.v)) if a is not None},
             "stale": {int(src): (slot[:self.P].detach().cpu(), int(rc))
                       for src, (slot, rc) in self.stale_store.items()},
             "loss_log": [float(x) for x in self.losses()],
             "buffers": dict(getattr(self.engine, "buffer_state", list)()),
         }
+
+    def _optim_config(self):
+        o = self.optim
+        return {"optimizer": o.kind, "weight_decay": o.weight_decay, "momentum": o.momentum,
+                "dampening": o.dampening, "nesterov": o.nesterov}
 
     def save_checkpoint(self, path):
         torch.save(self.checkpoint(), path)
@@ -556,7 +577,12 @@ class FLSimulation:
         mine = {"n": self.n, "throttle": self.throttle, "seed": self.seed,
                 "semantics": self.semantics, "dropout": self.dropout, "model": self.model,
                 "lr": self.lr, "betas": list(self.betas), "eps": self.eps,
-                "max_throttle": self.max_throttle, "batch_size": self.batch_size}
+                "max_throttle": self.max_throttle, "batch_size": self.batch_size,
+                **self._optim_config()}
+        # a checkpoint from before the optimizer was recorded: Adam without weight decay
+        for k, v in (("optimizer", "adam"), ("weight_decay", 0.0), ("momentum", 0.0),
+                     ("dampening", 0.0), ("nesterov", False)):
+            cfg.setdefault(k, v)
         delays = cfg["delays"].numpy().astype(np.int32)
         if fmt == "flsim-checkpoint-1":
             # format 1 (round 1) had no model / optimizer / throttle-cap keys (they were the
@@ -582,8 +608,10 @@ class FLSimulation:
             self.rs.randint(0, self.n, size=self.n)
         self.step = int(ck["step"])
         self.theta.copy_(ck["theta"].to(self.device))
-        self.m.copy_(ck["m"].to(self.device))
-        self.v.copy_(ck["v"].to(self.device))
+        if self.m is not None:
+            self.m.copy_(ck["m"].to(self.device))
+        if self.v is not None:
+            self.v.copy_(ck["v"].to(self.device))
         self.stale_store = {}
         for src, (vals, rc) in ck["stale"].items():
             slot = self._slot()

@@ -1,7 +1,8 @@
 """Drop-in for the reference's main.py (main.py:37-212) on MI355X.
 
 Same flags and defaults (main.py:38-53): --n_workers --n_epochs --batch_size --learning_rate
---delay --model_file --throttle.  The training loop (main.py:126-188) runs as flsim.sim
+--delay --model_file --throttle.  --optimizer {adam,adamw,sgd} with --momentum --dampening
+--nesterov --weight_decay picks the central optimizer (main.py:106 hard-wires Adam(lr)).  The training loop (main.py:126-188) runs as flsim.sim
 .FLSimulation: host schedule, worker-batched HIP forward/backward, fused rule()+Adam; with
 `torchrun --nproc-per-node N` the computing workers are sharded over N GPUs with one RCCL
 all-reduce per epoch.  'Avg. Loss' per epoch (main.py:185) goes to --log (JSONL; tensorboard is
@@ -35,11 +36,18 @@ def parse(argv=None):
     p.add_argument('--n_workers', type=int, default=5, help='number of FL workers')
     p.add_argument('--n_epochs', type=int, default=1000, help='number of train epochs')
     p.add_argument('--batch_size', type=int, default=128, help='samples per worker-step')
-    p.add_argument('--learning_rate', type=float, default=0.001, help='Adam learning rate')
+    p.add_argument('--learning_rate', type=float, default=0.001, help='learning rate')
     p.add_argument('--delay', type=int, default=100, help='delay in between slow worker')
     p.add_argument('--model_file', type=str, help='path to model to load (pretrained)')
     p.add_argument('--throttle', action='store_true', help='gradient throttling')
     # build flags
+    p.add_argument('--optimizer', default='adam', choices=['adam', 'adamw', 'sgd'],
+                   help="the central optimizer (main.py:106 builds Adam): torch.optim.Adam "
+                        "(--weight_decay: L2), AdamW (decoupled decay) or SGD")
+    p.add_argument('--momentum', type=float, default=0.0, help='SGD momentum')
+    p.add_argument('--dampening', type=float, default=0.0, help='SGD dampening')
+    p.add_argument('--nesterov', action='store_true', help='SGD Nesterov momentum')
+    p.add_argument('--weight_decay', type=float, default=0.0, help='weight decay')
     p.add_argument('--seed', type=int, default=0)
     p.add_argument('--semantics', default='reference', choices=['reference', 'torch1', 'independent'],
                    help='stale entry = S_{t-d} (torch>=2 aliasing), zeros (torch 1.x) or the slow '
@@ -88,7 +96,9 @@ def main(argv=None):
                        lr=args.learning_rate, seed=args.seed, semantics=args.semantics,
                        dropout=not args.no_dropout, chunk_workers=args.chunk, device=dev,
                        theta0=theta0, pool=pool, test_pool=test_pool, model=args.model,
-                       batch_size=args.batch_size)
+                       batch_size=args.batch_size, optimizer=args.optimizer,
+                       weight_decay=args.weight_decay, momentum=args.momentum,
+                       dampening=args.dampening, nesterov=args.nesterov)
     if buffers:
         sim.engine.load_buffers(buffers)
     if args.resume:

@@ -351,6 +351,46 @@ int flsim_vgg11_bn_server_step(void* gradstate, float* S_out, const flsim_rule* 
                                double beta2, double eps, flsim_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Server step with a chosen optimizer: Central(model, optim) (agents.py:4-8) takes any torch
+ * optimizer; these entry points run rule() fused with torch.optim.SGD (momentum, dampening,
+ * weight decay, nesterov), torch.optim.Adam with weight_decay (coupled L2) or torch.optim.AdamW
+ * (decoupled), bit-exact with torch 2.10's CPU single-tensor path (Adam family: except sqrt
+ * rounding, as above).  step = the optimizer's step count after increment; step 1 initialises
+ * SGD's momentum buffer (buf = g).  m holds exp_avg (Adam family) or the momentum buffer (SGD
+ * with momentum != 0), v exp_avg_sq.  Arrays a kind does not own are neither read nor written
+ * and may be NULL: v for SGD, m and v for SGD with momentum == 0.
+ * The hyper-parameters are checked before any pointer: an unknown kind, a negative lr,
+ * weight_decay or momentum, and nesterov with momentum <= 0 or dampening != 0 (where torch
+ * raises ValueError) return status 1.  The flsim_aggregate_adam* / flsim_*_server_step entry
+ * points above are these with kind = FLSIM_OPT_ADAM and weight_decay = 0.
+ * ------------------------------------------------------------------------------------------- */
+#define FLSIM_OPT_ADAM 0
+#define FLSIM_OPT_ADAMW 1
+#define FLSIM_OPT_SGD 2
+typedef struct flsim_optim {
+    int32_t kind;     /* FLSIM_OPT_* */
+    int32_t nesterov; /* SGD only */
+    double lr;
+    double beta1, beta2, eps; /* Adam family */
+    double weight_decay;
+    double momentum, dampening; /* SGD only */
+} flsim_optim;
+
+int flsim_aggregate_optim_rule_push(const float* S, float* S_out, const flsim_rule* rule, float* p,
+                                    float* m, float* v, long P, const long* tensor_sizes,
+                                    int n_tensors, long step, const flsim_optim* optim,
+                                    flsim_stream_t stream);
+int flsim_pn1_server_step_optim(void* gradstate, float* S_out, const flsim_rule* rule, float* p,
+                                float* m, float* v, long step, const flsim_optim* optim,
+                                flsim_stream_t stream);
+int flsim_vgg11_server_step_optim(void* gradstate, float* S_out, const flsim_rule* rule, float* p,
+                                  float* m, float* v, long step, const flsim_optim* optim,
+                                  flsim_stream_t stream);
+int flsim_vgg11_bn_server_step_optim(void* gradstate, float* S_out, const flsim_rule* rule,
+                                     float* p, float* m, float* v, long step,
+                                     const flsim_optim* optim, flsim_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Measurement (no reference counterpart): HIP events around every worker-batched GEMM launch on
  * its stream, for bench.py's live roofline figure.  read() fills flsim_probe_kernel_count()
  * entries per kernel id (launches, total ms, total algorithmic FLOPs) and resets the record.

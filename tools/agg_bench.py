@@ -4,6 +4,13 @@ from S_t in a buffer [+ the FIFO slot write]) at PerformantNet1's P, for the str
 thread).  Bytes are SURVEY 8(d)'s: 4P (1 + distinct stale + 3 + 3) [+ 4P for the slot write].
 
   python tools/agg_bench.py [--iters 50]
+  python tools/agg_bench.py --optimizers adam,sgdm,sgd [--iters 200] [--reps 3]
+
+--optimizers times the streaming step per update rule instead (flsim_aggregate_optim_rule_push:
+adam; adam_wd / adamw = Adam with weight decay; sgdm = SGD momentum 0.9; sgd = plain SGD) with
+k = 512 without a stale array and k = 513 with one, the rules alternating within each of --reps
+rounds.  Bytes: 4P (1 + distinct stale + 2 n_state + 2), n_state = 2 (p, m, v), 1 (p and the
+momentum buffer) or 0 (p only); frac = bytes / time over the 8 TB/s HBM peak.
 
 FLSIM_AGG_G acts only in a lab build of the library (make LAB=1, csrc/common.h): point FLSIM_LIB at
 one to compare the variants; the product build runs its default stream.
@@ -20,10 +27,55 @@ import torch  # noqa: E402
 from flsim.engine import PN1_SIZES, Rule, aggregate_rule  # noqa: E402
 
 
+OPTIMS = {      # name -> (the optim= argument, state arrays the kind owns)
+    "adam": (None, 2),
+    "adam_wd": (dict(kind="adam", weight_decay=5e-4), 2),
+    "adamw": (dict(kind="adamw", weight_decay=1e-2), 2),
+    "sgdm": (dict(kind="sgd", lr=0.01, momentum=0.9), 1),
+    "sgd": (dict(kind="sgd", lr=0.01), 0),
+}
+
+
+def bench_optimizers(names, iters, reps):
+    dev = "cuda:0"
+    P = sum(PN1_SIZES)
+    S = torch.randn(P + 64, device=dev) * 1e-2
+    st = torch.randn(P + 64, device=dev) * 1e-2
+    for rep in range(reps):
+        for c, ns in [(512, 0), (512, 1)]:
+            rule = Rule(c + ns, [st] * ns, c=c)
+            for name in names:
+                optim, nstate = OPTIMS[name]
+                p = torch.randn(P + 64, device=dev)
+                m = torch.zeros(P + 64, device=dev) if nstate >= 1 else None
+                v = torch.zeros(P + 64, device=dev) if nstate >= 2 else None
+                for _ in range(5):
+                    aggregate_rule(S, rule, p, m, v, 2, PN1_SIZES, optim=optim)
+                e0 = torch.cuda.Event(enable_timing=True)
+                e1 = torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(iters):
+                    aggregate_rule(S, rule, p, m, v, 2, PN1_SIZES, optim=optim)
+                e1.record()
+                torch.cuda.synchronize()
+                us = e0.elapsed_time(e1) / iters * 1e3
+                byts = 4 * P * (1 + ns + 2 * nstate + 2)
+                print(json.dumps(dict(optimizer=name, rep=rep, k=c + ns, stale=ns,
+                                      us=round(us, 2), bytes=byts,
+                                      GBps=round(byts / us / 1e3, 1),
+                                      frac=round(byts / us / 1e3 / 8000, 4))), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--optimizers", type=str, default=None,
+                    help="comma list of " + ",".join(OPTIMS) + ": time these update rules")
+    ap.add_argument("--reps", type=int, default=3)
     args = ap.parse_args()
+    if args.optimizers:
+        bench_optimizers(args.optimizers.split(","), args.iters, args.reps)
+        return
     dev = "cuda:0"
     P = sum(PN1_SIZES)
     S = torch.randn(P + 64, device=dev) * 1e-2
