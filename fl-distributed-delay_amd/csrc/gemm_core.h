@@ -132,6 +132,23 @@ struct HasPre : std::false_type {};
 template <class E>
 struct HasPre<E, std::void_t<decltype(E::PRE)>> : std::bool_constant<E::PRE> {};
 
+// A loaders with WANTS_N0 = true take the tile's column origin too, setup(m0, tid, n0): the dense
+// weight gradient's dZ loader shifts its rows by the filter tap of the block's n-tile (loaders.h
+// TapRowsKM)
+template <class L, class = void>
+struct WantsN0 : std::false_type {};
+template <class L>
+struct WantsN0<L, std::void_t<decltype(L::WANTS_N0)>> : std::bool_constant<L::WANTS_N0> {};
+
+// ASUM epilogues with BIAS_RING = true (the dense weight gradient, loaders.h TapRowsKM): the column
+// sums come from the LAST n-tile's blocks (the tap without a shift, whose A tiles are dZ's
+// top-left IH x IW window as it stands), which then add the rest of the map, the ring the window
+// leaves out, through the A loader's bias_ring(ks0, ks1, m0, tid, lds)
+template <class E, class = void>
+struct HasBiasRing : std::false_type {};
+template <class E>
+struct HasBiasRing<E, std::void_t<decltype(E::BIAS_RING)>> : std::bool_constant<E::BIAS_RING> {};
+
 // Blocks of one or two waves keep a single LDS buffer: their barriers span at most two waves, so
 // the store -> barrier -> read order costs little, and half the LDS lifts the LDS-bound ones
 // (PerformantNet1's conv2 / conv3 weight gradients, 48 x 48 of 1 wave, 96 x 48 of 2) from 3 to 5 and
@@ -190,7 +207,10 @@ gemm_kernel(AL al, BL bl, EPI epi, int ksteps_total, int ksteps_per_split, int t
     int ks1 = ks0 + ksteps_per_split;
     if (ks1 > ksteps_total) ks1 = ksteps_total;
 
-    al.setup(m0, tid);
+    // the n-tile whose blocks column-sum their A tiles (EPI::ASUM)
+    const int asum_tn = HasBiasRing<EPI>::value ? gy - 1 : 0;
+    if constexpr (WantsN0<AL>::value) al.setup(m0, tid, n0);
+    else al.setup(m0, tid);
     bl.setup(n0, tid);
 
     f32x4 acc[FM][FN];
@@ -200,6 +220,11 @@ gemm_kernel(AL al, BL bl, EPI epi, int ksteps_total, int ksteps_per_split, int t
         for (int j = 0; j < FN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     float asum = 0.f;
+    if constexpr (HasBiasRing<EPI>::value) {
+        // ahead of the pipeline, while few registers are live and the LDS is still free
+        static_assert(AL::RING_FLOATS <= LDS_FL, "the ring's partial sums fit the pipeline's LDS");
+        if (tn == asum_tn) asum = al.bias_ring(ks0, ks1, m0, tid, lds);   // block-uniform
+    }
     f32x4 ra[AL::UNITS];
     f32x4 rb[BL::UNITS];
     constexpr int BUF = A_FL + B_FL;
@@ -252,9 +277,9 @@ gemm_kernel(AL al, BL bl, EPI epi, int ksteps_total, int ksteps_per_split, int t
         const float* B = A + A_FL;
         if constexpr (EPI::ASUM) {
             // bias gradient fused into the weight gradient: column sums of the KM dZ tile
-            // (rows = reduction index), accumulated by the n-tile-0 blocks in K order
+            // (rows = reduction index), accumulated by the blocks of n-tile asum_tn in K order
             static_assert(!AL::KC, "ASUM needs a k-major A tile");
-            if (tn == 0 && tid < BM) {
+            if (tn == asum_tn && tid < BM) {
 #pragma unroll
                 for (int k = 0; k < GK; ++k) asum += A[k * KMTile<BM>::STRIDE + tid];
             }
@@ -275,7 +300,7 @@ gemm_kernel(AL al, BL bl, EPI epi, int ksteps_total, int ksteps_per_split, int t
     }
 
     if constexpr (EPI::ASUM) {
-        if (tn == 0 && tid < BM) epi.asum(m0 + tid, tz, asum);
+        if (tn == asum_tn && tid < BM) epi.asum(m0 + tid, tz, asum);
     }
     if constexpr (STAGED) {
         static_assert(BN == EPI::NCOL || (IsPartial<EPI>::value && EPI::NCOL % BN == 0),

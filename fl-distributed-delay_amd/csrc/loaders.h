@@ -515,6 +515,206 @@ struct Im2colKM {
 };
 
 // ---------------------------------------------------------------------------------------------
+// The dense weight gradient of a 3x3 / stride-1 / padding-2 convolution: the reduction runs over
+// the INPUT pixels q = (img, ih, iw),
+//     dW[co][kh][kw][ci] = sum_q dZ[img][ih + 2 - kh][iw + 2 - kw][co] * X[img][ih][iw][ci],
+// S IH IW addends per output instead of the S OH OW (OH = IH + 2) of RowsKM x Im2colKM, whose
+// other addends are products with the padding's zeros.  With padding 2 the shifted dZ pixel is
+// always inside the OH x OW map.  The n-tile is exactly one tap (BN == CI), so the tap is
+// block-uniform: TapRowsKM (A, dZ) carries its shift, PixRowsKM (B, the layer input) is a plain
+// stream of pixel rows.
+// ---------------------------------------------------------------------------------------------
+// q -> (image, pixel within the image) of the thread's row of k-step ks: the block-uniform base
+// once (scalar), the thread's row by one carry
+template <int PIXELS>
+__device__ __forceinline__ void km_pixel(int ks, int krow, unsigned& img, unsigned& rem) {
+    static_assert(PIXELS >= GK, "one image carry at most per k-step");
+    img = (unsigned)(ks * GK) / (unsigned)PIXELS;
+    rem = (unsigned)(ks * GK) - img * PIXELS + krow;
+    if (rem >= (unsigned)PIXELS) { rem -= PIXELS; ++img; }
+}
+
+// A operand: dZ [img][DH][DH][ld] (pixel-major), tile columns = channels [c0, c0 + ROWS), reduction
+// rows = input pixels shifted by the tap of the block's n-tile (setup's n0 / CI).
+// DH = IH + 2: the full output map.  DH = IH + 1: dZ stored compact without its last row and
+// column (conv6: the floor-mode pool never reads them, they are zero), which the shift reaches
+// only for kh == 0, ih == IH - 1 and kw == 0, iw == IW - 1: those units read as zero.
+template <int IH, int IW, int CI, int DH, int TR, int NT, class SRC = BufSrc>
+struct TapRowsKM {
+    using Unit = typename SRC::Unit;
+    static_assert(!SRC::SM && !SRC::SPLIT, "pixel-major fp32 dZ");
+    static_assert(FLSIM_BUFLOAD, "buffer loads only");
+    static_assert(DH == IH + 2 || DH == IH + 1, "padding 2: full map, or compact by one row/column");
+    static constexpr int ROWS = TR;
+    static constexpr bool KC = false;
+    static constexpr bool WANTS_N0 = true;
+    static constexpr bool EDGE = DH < IH + 2;
+    static constexpr int C4 = ROWS / 4;
+    static constexpr int TPR = NT / GK;
+    static_assert(NT % GK == 0, "");
+    static constexpr int UNITS = (C4 + TPR - 1) / TPR;
+    // bias_ring: NT / C4 pixel groups of C4 threads, one float4 of columns each
+    static constexpr int GROUPS = NT / C4;
+    static constexpr int RING_FLOATS = GROUPS * ROWS;
+    static constexpr int RING_AHEAD = 4;     // pixels a thread has in flight
+    static_assert(GROUPS >= 1, "");
+    const float* P;
+    long ld;
+    int M;    // input pixels (S IH IW)
+    int NC;
+    int krow;
+    int dh, dw;   // 2 - kh, 2 - kw of the block's tap
+    int c_off[UNITS];
+    short c4[UNITS];
+    SRC buf;
+    __device__ unsigned long bytes() const {
+        return (unsigned long)(M / (IH * IW)) * (DH * DH) * ld * 4;
+    }
+    __device__ void setup(int c0, int tid, int n0) {
+        krow = km_row<TPR>(tid);
+        buf.init(P, bytes());
+        const int tap = n0 / CI;      // block-uniform
+        dh = 2 - tap / 3;
+        dw = 2 - tap % 3;
+#pragma unroll
+        for (int j = 0; j < UNITS; ++j) {
+            const int c = tid % TPR + TPR * j;
+            c4[j] = (short)c;
+            const int col = c0 + 4 * c;
+            c_off[j] = (c < C4 && col < NC) ? col : -1;
+        }
+    }
+    __device__ void load(int ks, Unit (&r)[UNITS]) const {
+        unsigned img, rem;
+        km_pixel<IH * IW>(ks, krow, img, rem);
+        const unsigned ih = SmallDiv<IW, IH * IW + GK>::div(rem);
+        const unsigned oh = ih + dh, ow = rem - ih * IW + dw;
+        bool rok = ks * GK + krow < M;
+        if constexpr (EDGE) rok = rok && oh < (unsigned)DH && ow < (unsigned)DH;
+        const unsigned rb = (img * (unsigned)(DH * DH) + oh * DH + ow) * ((unsigned)ld * 4u);
+#pragma unroll
+        for (int j = 0; j < UNITS; ++j)
+            r[j] = buf.ld_or0(rb + (unsigned)c_off[j] * 4u, rok && c_off[j] >= 0);
+    }
+    __device__ void store(float* lds, const f32x4 (&r)[UNITS]) const {
+#pragma unroll
+        for (int j = 0; j < UNITS; ++j)
+            store_km_or_spare<ROWS>(lds, C4 % TPR == 0 || c4[j] < C4, krow, c4[j], r[j]);
+    }
+    // The bias gradient is the sum over ALL stored dZ pixels, and no tap's rows are all of them.
+    // The blocks of the tap without a shift (kh = kw = 2, the last n-tile) column-sum their A
+    // tiles in the main loop (gemm_core.h ASUM): dZ's window oh < IH, ow < IW for the split's
+    // input pixels.  bias_ring adds the rest of the map, rows oh >= IH and columns ow >= IW
+    // (DH^2 - IH IW pixels per image), for the images whose first pixel lies in the split's
+    // k-steps [ks0, ks1): every output pixel is counted by exactly one split.  No B operand and
+    // no MFMA: thread (g, c) adds ring pixels g, g + GROUPS, ... of its float4 of columns in
+    // index order, then the first ROWS threads add the GROUPS partial sums in group order -- a
+    // fixed order, no atomics.  Called by every thread of the block ahead of the main loop (the
+    // LDS is free again when it returns); returns column c0 + tid's sum to the first ROWS threads.
+    __device__ float bias_ring(int ks0, int ks1, int c0, int tid, float* lds) const {
+        constexpr int P = IH * IW, RN = DH * DH - P;
+        constexpr int BOTTOM = (DH - IH) * DH;    // rows oh >= IH: contiguous pixels
+        constexpr int RW = DH - IW;               // columns ow >= IW of the rows above them
+        const int q0 = ks0 * GK;
+        int q1 = ks1 * GK < M ? ks1 * GK : M;
+        if (q1 < q0) q1 = q0;
+        const int i0 = (q0 + P - 1) / P, i1 = (q1 + P - 1) / P;     // block-uniform
+        const int total = (i1 - i0) * RN;
+        const int g = tid / C4, c = tid - g * C4;
+        const int col = c0 + 4 * c;
+        const unsigned rstride = (unsigned)ld * 4u;
+        auto off = [&](int idx) -> unsigned {
+            const unsigned img = (unsigned)idx / (unsigned)RN;
+            const unsigned r = (unsigned)idx - img * RN;
+            unsigned pix = IH * DH + r;
+            if (r >= (unsigned)BOTTOM) {
+                const unsigned r2 = r - BOTTOM, oh = r2 / RW;
+                pix = oh * DH + IW + (r2 - oh * RW);
+            }
+            return ((i0 + img) * (unsigned)(DH * DH) + pix) * rstride + (unsigned)col * 4u;
+        };
+        f32x4 s = zero4();
+        if (g < GROUPS && col < NC) {
+            int i = g;
+            for (; i + (RING_AHEAD - 1) * GROUPS < total; i += RING_AHEAD * GROUPS) {
+                f32x4 v[RING_AHEAD];
+#pragma unroll
+                for (int j = 0; j < RING_AHEAD; ++j) v[j] = buf.ld(off(i + j * GROUPS));
+#pragma unroll
+                for (int j = 0; j < RING_AHEAD; ++j) s += v[j];
+            }
+            for (; i < total; i += GROUPS) s += buf.ld(off(i));
+        }
+        if (g < GROUPS) *reinterpret_cast<f32x4*>(lds + g * ROWS + 4 * c) = s;
+        __syncthreads();
+        float t = 0.f;
+        if (tid < ROWS) {
+            t = lds[tid];
+#pragma unroll
+            for (int i = 1; i < GROUPS; ++i) t += lds[i * ROWS + tid];
+        }
+        __syncthreads();
+        return t;
+    }
+};
+
+// B operand: the layer input X, pixel-major [q][CI] or channel-slice-major [img][CI/16][IH][IW][16]
+// (SRC::SM); tile columns = channels n0 % CI + [0, ROWS), reduction rows = input pixels q as they
+// stand: no tap arithmetic, no mask beyond q < M.
+template <int IH, int IW, int CI, int TR, int NT, class SRC = BufSrc>
+struct PixRowsKM {
+    using Unit = typename SRC::Unit;
+    static_assert(!SRC::SPLIT, "fp32 layer input");
+    static_assert(FLSIM_BUFLOAD, "buffer loads only");
+    static_assert(!SRC::SM || CI % GK == 0, "slice-major maps have whole 16-channel slices");
+    static constexpr int ROWS = TR;
+    static constexpr bool KC = false;
+    static constexpr int C4 = ROWS / 4;
+    static constexpr int TPR = NT / GK;
+    static_assert(NT % GK == 0, "");
+    static constexpr int UNITS = (C4 + TPR - 1) / TPR;
+    static constexpr int PIX = SRC::SM ? GK : CI;
+    static constexpr int SLICE = SRC::SM ? IH * IW * GK : GK;
+    const float* X;
+    int M;    // input pixels (S IH IW)
+    int krow;
+    int coff[UNITS];   // channel offset from the pixel's first float, -1: no such column
+    short c4[UNITS];
+    SRC buf;
+    __device__ void setup(int n0, int tid) {
+        krow = km_row<TPR>(tid);
+        buf.init(X, (unsigned long)M * CI * 4);
+        const int ci0 = n0 % CI;      // block-uniform (0 when the tile is a whole tap)
+#pragma unroll
+        for (int j = 0; j < UNITS; ++j) {
+            const int c = tid % TPR + TPR * j;
+            c4[j] = (short)c;
+            const int ci = ci0 + 4 * c;
+            coff[j] = (c < C4 && ci < CI) ? (ci / GK) * SLICE + ci % GK : -1;
+        }
+    }
+    __device__ void load(int ks, Unit (&r)[UNITS]) const {
+        const int q = ks * GK + krow;
+        unsigned xb;
+        if constexpr (SRC::SM) {
+            unsigned img, rem;
+            km_pixel<IH * IW>(ks, krow, img, rem);
+            xb = img * (unsigned)(IH * IW * CI * 4) + rem * (PIX * 4u);
+        } else {
+            xb = (unsigned)q * (CI * 4u);
+        }
+#pragma unroll
+        for (int j = 0; j < UNITS; ++j)
+            r[j] = buf.ld_or0(xb + (unsigned)coff[j] * 4u, q < M && coff[j] >= 0);
+    }
+    __device__ void store(float* lds, const f32x4 (&r)[UNITS]) const {
+#pragma unroll
+        for (int j = 0; j < UNITS; ++j)
+            store_km_or_spare<ROWS>(lds, C4 % TPR == 0 || c4[j] < C4, krow, c4[j], r[j]);
+    }
+};
+
+// ---------------------------------------------------------------------------------------------
 // Epilogues
 // ---------------------------------------------------------------------------------------------
 // conv forward without activation: Y[m][n] = acc + bias[n]  (vgg11_bn: the BatchNorm input)
@@ -836,6 +1036,12 @@ struct EpiSlabAcc {
                 if (m + r < M) base[(long)(m + r) * N + n] = v[r];
         }
     }
+};
+
+// EpiSlabAcc of the dense weight gradient: the column sums of the last n-tile's dZ tiles plus the
+// ring of the map they leave out (gemm_core.h BIAS_RING, TapRowsKM::bias_ring), to the same Bsl rows
+struct EpiSlabAccRing : EpiSlabAcc {
+    static constexpr bool BIAS_RING = true;
 };
 
 // split-K partial, overwritten: S[z][m][n] = acc

@@ -933,6 +933,47 @@ static int conv_wgrad(const float* dz, const float* X, int S, int CO, int KP, fl
                                            2.0 * M * CO * kreal);
 }
 
+// conv_wgrad for padding 2 reduced over the S IH IW input pixels instead of the S OH OW output
+// pixels (loaders.h TapRowsKM / PixRowsKM): the same sums without the addends that multiply the
+// padding's zeros, IH^2 / OH^2 of the k-steps.  One n-tile per filter tap (BN == CI); the last
+// tap's blocks also sum dZ's columns for the bias gradient (TapRowsKM::bias_ring).
+// DH: side of the stored dZ map, IH + 2, or IH + 1 when it is compact (conv6)
+// fp32 operands on the fp32 MFMA; SRCB = BufSrcSM: X channel-slice-major
+template <int IH, int IW, int CI, int FM, int FN, int WM, int WN, int DH, class SRCB = BufSrc>
+static int conv_wgrad_dense(const float* dz, const float* X, int S, int CO, int KP, float* slab,
+                            float* bslab, int Z, hipStream_t st, int kid, int kreal,
+                            int zinit = 0x7fffffff, int* zused = nullptr) {
+    constexpr int NT = 64 * WM * WN;
+    constexpr int BM = 16 * FM * WM, BN = 16 * FN * WN;
+    static_assert(IH == IW, "square maps only");
+    static_assert(BN == CI, "an n-tile is exactly one filter tap");
+    using AL = TapRowsKM<IH, IW, CI, DH, BM, NT>;
+    using BL = PixRowsKM<IH, IW, CI, BN, NT, SRCB>;
+    FLSIM_REQUIRE(KP == 9 * CI, "dense weight gradient: %d columns, not 9 taps of %d", KP, CI);
+    const int M = S * IH * IW;
+    AL al;
+    al.P = dz;
+    al.ld = CO;
+    al.M = M;
+    al.NC = CO;
+    BL bl;
+    bl.X = X;
+    bl.M = M;
+    EpiSlabAccRing epi{{slab, CO, KP, (long)CO * KP, bslab, zinit}};
+    const int tm = ceil_div(CO, BM), tn = KP / BN;
+    static const int cap =
+        resident_blocks((const void*)gemm_kernel<FM, FN, WM, WN, AL, BL, EpiSlabAccRing>, NT);
+    const int ksteps = ceil_div(M, GK);
+    const int zu = wsplit(ksteps, Z, tm * tn, cap);
+    if (zused) *zused = zu;
+    const int per = (ksteps + zu - 1) / zu;
+    const ProbeSlot ps = probe_begin();
+    hipExtLaunchKernelGGL((gemm_kernel<FM, FN, WM, WN, AL, BL, EpiSlabAccRing>), dim3(tm * tn * zu),
+                          dim3(NT), 0, st, ps.start, ps.stop, 0, al, bl, epi, ksteps, per, tm, tn);
+    FLSIM_LAUNCH_CHECK();
+    return probe_end(ps, kid, 2.0 * M * CO * kreal);      // the FLOPs executed
+}
+
 // conv_wgrad with a second tile for chunks of at most small_chunk_samples() samples
 // (profiles/r03f/lab_s640_wgrad.txt: at 640 samples 96x96 4-wave tiles beat the 128-worker
 // chunk's larger ones on conv3/5/6 by 3-10 %, 48x144 beats 48x48 on conv2 by 4 %)

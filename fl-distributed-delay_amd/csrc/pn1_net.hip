@@ -568,6 +568,26 @@ constexpr int DG_FMS = FLSIM_DG_FMS;
 #define FLSIM_WGRAD_X6 0
 #endif
 
+// conv2-6 fp32 weight gradients reduced over the input pixels (1: net_kernels.h conv_wgrad_dense)
+// or over the padded output map (0: conv_wgrad), per layer; DESIGN 8b has both forms' times.
+// conv2 stays on the padded form: dense it ran 6.71 against 6.75 ms, but conv2's data gradient
+// behind it 6.60 against 6.43 ms (profiles/wgrad_dense)
+#ifndef FLSIM_WGD2
+#define FLSIM_WGD2 0
+#endif
+#ifndef FLSIM_WGD3
+#define FLSIM_WGD3 1
+#endif
+#ifndef FLSIM_WGD4
+#define FLSIM_WGD4 1
+#endif
+#ifndef FLSIM_WGD5
+#define FLSIM_WGD5 1
+#endif
+#ifndef FLSIM_WGD6
+#define FLSIM_WGD6 1
+#endif
+
 // debug / measurement: FLSIM_DEBUG_BWD_STOP=6 / 5 / 4 / 3 ends the backward pass after conv6's /
 // conv5's / conv4's / conv3's data gradient (dz5 in gx; dz4 in a4, dz5 in gx; dz3 in gx, dz4 in
 // a4; dz2 in a2, dz3 in gx; all fp32), so each GEMM can be checked on its own inputs
@@ -647,6 +667,9 @@ static int backward(const GradState& g, const WS& w, const float* theta, int S, 
     RC((conv_wgrad_sz<13, 13, 192, 2, 6, 3, 2, 2, 3, 3, 2, 2, 14, true, true, BufSrc, XsSrc>(
         dz6, w.a5, S, 192, 1728, g.sw[5], g.sb[5], GEO[5].ZW, sw, K_WG6, 1728, zi(5), &zu[5],
         nullptr, w.a5l)));
+#elif FLSIM_WGD6
+    RC((conv_wgrad_dense<13, 13, 192, 6, 3, 2, 4, 14>(
+        dz6, w.a5f, S, 192, 1728, g.sw[5], g.sb[5], GEO[5].ZW, sw, K_WG6, 1728, zi(5), &zu[5])));
 #else
     RC((conv_wgrad<13, 13, 192, 2, 6, 3, 2, 4, 14, true, false, BufSrc, BufSrc>(
         dz6, w.a5f, S, 192, 1728, g.sw[5], g.sb[5], GEO[5].ZW, sw, K_WG6, 1728, zi(5), &zu[5])));
@@ -664,6 +687,9 @@ static int backward(const GradState& g, const WS& w, const float* theta, int S, 
     RC((conv_wgrad_sz<11, 11, 96, 2, 6, 3, 2, 2, 3, 3, 2, 2, 0, false, true, BufSrc, XsSrc>(
         dz5, w.d2, S, 192, 864, g.sw[4], g.sb[4], GEO[4].ZW, sw, K_WG5, 864, zi(4), &zu[4],
         nullptr, w.d2l)));
+#elif FLSIM_WGD5
+    RC((conv_wgrad_dense<11, 11, 96, 6, 3, 2, 2, 13>(
+        dz5, w.d2f, S, 192, 864, g.sw[4], g.sb[4], GEO[4].ZW, sw, K_WG5, 864, zi(4), &zu[4])));
 #else
     RC((conv_wgrad<11, 11, 96, 2, 6, 3, 2, 2, 0, false, false, BufSrc, BufSrc>(
         dz5, w.d2f, S, 192, 864, g.sw[4], g.sb[4], GEO[4].ZW, sw, K_WG5, 864, zi(4), &zu[4])));
@@ -684,6 +710,9 @@ static int backward(const GradState& g, const WS& w, const float* theta, int S, 
     RC((conv_wgrad<20, 20, 96, 2, 3, 3, 2, 2, 0, false, true, BufSrc, XsSrcSM>(
         dz4, w.a3, S, 96, 864, g.sw[3], g.sb[3], GEO[3].ZW, sw, K_WG4, 864, zi(3), &zu[3],
         nullptr, w.a3l)));
+#elif FLSIM_WGD4
+    RC((conv_wgrad_dense<20, 20, 96, 3, 3, 2, 2, 22, BufSrcSM>(
+        dz4, w.a3f, S, 96, 864, g.sw[3], g.sb[3], GEO[3].ZW, sw, K_WG4, 864, zi(3), &zu[3])));
 #else
     RC((conv_wgrad<20, 20, 96, 2, 3, 3, 2, 2, 0, false, false, BufSrc, BufSrcSM>(
         dz4, w.a3f, S, 96, 864, g.sw[3], g.sb[3], GEO[3].ZW, sw, K_WG4, 864, zi(3), &zu[3])));
@@ -700,6 +729,9 @@ static int backward(const GradState& g, const WS& w, const float* theta, int S, 
     RC((conv_wgrad_sz<18, 18, 48, 2, 3, 3, 2, 2, 3, 3, 2, 2, 0, false, true, BufSrc, XsSrcSM>(
         dz3, w.d1, S, 96, 432, g.sw[2], g.sb[2], GEO[2].ZW, sw, K_WG3, 432, zi(2), &zu[2],
         nullptr, w.d1l)));
+#elif FLSIM_WGD3
+    RC((conv_wgrad_dense<18, 18, 48, 3, 3, 2, 1, 20, BufSrcSM>(
+        dz3, w.d1f, S, 96, 432, g.sw[2], g.sb[2], GEO[2].ZW, sw, K_WG3, 432, zi(2), &zu[2])));
 #else
     RC((conv_wgrad<18, 18, 48, 2, 3, 3, 2, 1, 0, false, false, BufSrc, BufSrcSM>(
         dz3, w.d1f, S, 96, 432, g.sw[2], g.sb[2], GEO[2].ZW, sw, K_WG3, 432, zi(2), &zu[2])));
@@ -722,6 +754,9 @@ static int backward(const GradState& g, const WS& w, const float* theta, int S, 
     RC((conv_wgrad_sz<34, 34, 48, 2, 3, 3, 1, 3, 3, 3, 1, 3, 0, false, true, BufSrc, XsSrcSM>(
         dz2, w.a1, S, 48, 432, g.sw[1], g.sb[1], GEO[1].ZW, sw, K_WG2, 432, zi(1), &zu[1],
         nullptr, w.a1l)));
+#elif FLSIM_WGD2
+    RC((conv_wgrad_dense<34, 34, 48, 3, 3, 1, 1, 36, BufSrcSM>(
+        dz2, w.a1f, S, 48, 432, g.sw[1], g.sb[1], GEO[1].ZW, sw, K_WG2, 432, zi(1), &zu[1])));
 #else
     // (one 48 x 48 wave per block; its tap tiles fetch dZ and the layer input once each, 53 GB
     // per launch, profiles/traffic.json.  Blocks spanning 3 or 9 taps, 48 x 144 of 3 waves /

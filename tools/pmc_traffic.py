@@ -47,8 +47,8 @@ def probe_name(kname):
             return "linear1_wgrad" if big else "linear2_wgrad"
         if "EpiDropMask" in kname and "Im2col" not in kname:
             return "linear1_dgrad" if big else "linear2_dgrad"
-    m = re.search(r"Im2colKM<(\d+), (\d+), (\d+),", kname)
-    if m:
+    m = re.search(r"(?:Im2colKM|PixRowsKM)<(\d+), (\d+), (\d+),", kname)
+    if m:     # (PixRowsKM: the dense weight gradient's layer-input loader)
         return f"conv{FWD[tuple(map(int, m.groups()))]}_wgrad"
     m = re.search(r"Im2col(?:KC|Direct)<(\d+), (\d+), (\d+), (\d+),", kname)
     if m:
