@@ -85,6 +85,11 @@ void flsim_sched_state(const flsim_sched* s, int64_t* out3);
  * Gradients of all chunks of an epoch accumulate (agents.py:35 in-place .grad accumulation)
  * into split-K slabs inside `gradstate`; flsim_pn1_end_epoch sums them into S_t (torch
  * named_parameters layout, P = flsim_pn1_param_count() floats).
+ * `gradstate` (flsim_pn1_gradstate_bytes()) and `workspace` (flsim_pn1_workspace_bytes()) need no
+ * initialisation by the caller: results do not depend on what the buffers held before
+ * flsim_pn1_begin_epoch (any bytes, NaN patterns included), nor on earlier epochs and chunks run
+ * on them.  The caller only keeps them alive and calls flsim_pn1_begin_epoch before the first
+ * backward pass on a gradstate.  The same holds for the flsim_vgg11_* and flsim_vgg11_bn_* families.
  * ------------------------------------------------------------------------------------------- */
 long flsim_pn1_param_count(void);
 long flsim_pn1_gradstate_bytes(void);
