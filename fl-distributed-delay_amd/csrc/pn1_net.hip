@@ -12,7 +12,7 @@
 // dz1 and the linear layers stay fp32.
 // Conv weights are re-packed once per epoch (net_kernels.h, shared with the VGG-11 engine
 // vgg_net.hip together with the batch assembly, pool scatter, head, slab reduction and GEMM
-// launchers).
+// launchers).  The entry points the two engines have in common are net_abi.h's templates.
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
@@ -20,8 +20,7 @@
 #include <mutex>
 #include <unordered_map>
 
-#include "net_kernels.h"
-#include "slabstep.h"
+#include "net_abi.h"
 
 namespace flsim {
 
@@ -428,21 +427,12 @@ static int forward(const GradState& g, const WS& w, const float* theta, int S,
 // begin_epoch does not clear the 1.9 GB of slabs: the weight-gradient GEMMs store into rows not
 // yet written this epoch and accumulate into the others (EpiSlabAcc::zinit), and the epoch's
 // slab sum reads only the written rows (SlabSeg::zlim).  Small chunks use fewer rows (wsplit), so
-// an n = 10 epoch no longer pays a 0.3 ms clear and a full 1.9 GB read.  Keyed by the gradstate
-// address; the entry is created by begin_epoch and erased by flsim_pn1_release (engine teardown),
-// and a backward pass on a gradstate without one is refused: the slab rows would otherwise be
-// read or accumulated without ever having been written.
+// an n = 10 epoch no longer pays a 0.3 ms clear and a full 1.9 GB read.  A backward pass on a
+// gradstate without a record (HostState below) is refused: the slab rows would otherwise be read
+// or accumulated without ever having been written.
 struct EpochRows {
     int z[8];
 };
-static std::mutex g_rows_mu;
-static std::unordered_map<const void*, EpochRows> g_rows;
-
-static EpochRows* epoch_rows(const void* gradstate) {
-    std::lock_guard<std::mutex> lk(g_rows_mu);
-    auto it = g_rows.find(gradstate);
-    return it == g_rows.end() ? nullptr : &it->second;
-}
 
 // Chunk pipelining (flsim_pn1_fwd_bwd_chunk_async): chunk i's forward runs on the caller's stream
 // while chunk i-1's backward runs on the gradstate's own backward stream, so the HBM-bound kernels
@@ -453,36 +443,57 @@ static EpochRows* epoch_rows(const void* gradstate) {
 // caller's stream to the outstanding backward work (pipe_join), so the packing of the next
 // epoch's weights, the slab reduction and the evaluations see a finished epoch.
 struct Pipe {
-    hipStream_t bs = nullptr;
+    hipStream_t bs = nullptr;      // created on first use (queue_backward)
     hipEvent_t fwd_done = nullptr, bwd_tail = nullptr;
     std::unordered_map<const void*, hipEvent_t> ws_free;   // workspace -> its last backward
     bool pending = false;
 };
-static std::mutex g_pipe_mu;
-static std::unordered_map<const void*, Pipe> g_pipes;
+
+// The host side of a gradstate, keyed by its address: created by begin_epoch, erased by
+// flsim_pn1_release (engine teardown, any thread).  A record is found and used under g_state_mu
+// only: whatever reads or writes it holds the mutex from the lookup to its last use, a whole
+// backward enqueue included (lock order: g_state_mu, then the side stream's mutex in backward()).
+struct HostState {
+    EpochRows rows{};
+    Pipe pipe;
+};
+static std::mutex g_state_mu;
+static std::unordered_map<const void*, HostState> g_state;
+
+// (g_state_mu held)
+static HostState* find_state(const void* gradstate) {
+    auto it = g_state.find(gradstate);
+    return it == g_state.end() ? nullptr : &it->second;
+}
+
 
 static int pipe_join(const void* gradstate, hipStream_t st) {
-    std::lock_guard<std::mutex> lk(g_pipe_mu);
-    auto it = g_pipes.find(gradstate);
-    if (it == g_pipes.end() || !it->second.pending) return 0;
-    Pipe& p = it->second;
+    std::lock_guard<std::mutex> lk(g_state_mu);
+    HostState* hs = find_state(gradstate);
+    if (!hs || !hs->pipe.pending) return 0;
+    Pipe& p = hs->pipe;
     FLSIM_CHECK_HIP(hipEventRecord(p.bwd_tail, p.bs));
     FLSIM_CHECK_HIP(hipStreamWaitEvent(st, p.bwd_tail, 0));
     p.pending = false;
     return 0;
 }
 
-static void pipe_release(const void* gradstate) {
-    std::lock_guard<std::mutex> lk(g_pipe_mu);
-    auto it = g_pipes.find(gradstate);
-    if (it == g_pipes.end()) return;
-    Pipe& p = it->second;
-    (void)hipStreamSynchronize(p.bs);
-    for (auto& kv : p.ws_free) (void)hipEventDestroy(kv.second);
-    (void)hipEventDestroy(p.fwd_done);
-    (void)hipEventDestroy(p.bwd_tail);
-    (void)hipStreamDestroy(p.bs);
-    g_pipes.erase(it);
+// (g_state_mu held) rows a queued backward still reads are not overwritten: `stream` waits for
+// the last backward that read this workspace
+static int wait_workspace(const Pipe& p, const void* workspace, hipStream_t stream) {
+    auto e = p.ws_free.find(workspace);
+    if (e != p.ws_free.end() && e->second)
+        FLSIM_CHECK_HIP(hipStreamWaitEvent(stream, e->second, 0));
+    return 0;
+}
+
+// before a row entry point writes workspace rows; need_epoch: refused without begin_epoch
+static int begin_rows(const void* gradstate, const void* workspace, bool need_epoch,
+                      hipStream_t stream) {
+    std::lock_guard<std::mutex> lk(g_state_mu);
+    const HostState* hs = find_state(gradstate);
+    FLSIM_REQUIRE(hs || !need_epoch, "forward rows without flsim_pn1_begin_epoch");
+    return hs ? wait_workspace(hs->pipe, workspace, stream) : 0;
 }
 
 // the plan replanned over each tracked segment's rows written this epoch: a small chunk
@@ -490,15 +501,20 @@ static void pipe_release(const void* gradstate) {
 // full-Z plan empty, each still taking part in its tile's partial hand-off.  The replanned units
 // and tiles never exceed the full plan's, so the counters and partials laid out for it suffice.
 static StepPlan plan_in_use(const GradState& g, const void* gradstate) {
-    const EpochRows* er = epoch_rows(gradstate);
-    if (!er) return g.plan;
+    EpochRows er;
+    {
+        std::lock_guard<std::mutex> lk(g_state_mu);
+        const HostState* hs = find_state(gradstate);
+        if (!hs) return g.plan;
+        er = hs->rows;
+    }
     SegSpec specs[STEP_MAX_SEG];
     const int n = pn1_segments(g, reinterpret_cast<const float*>(gradstate), specs);
     int zin[STEP_MAX_SEG];
     for (int i = 0; i < n; ++i) {
         zin[i] = specs[i].Z;
         if (specs[i].group >= 0) {
-            const int z = er->z[specs[i].group];
+            const int z = er.z[specs[i].group];
             zin[i] = z < specs[i].Z ? z : specs[i].Z;
             specs[i].Z = zin[i] > 0 ? zin[i] : 1;
         }
@@ -777,6 +793,79 @@ static int backward(const GradState& g, const WS& w, const float* theta, int S, 
     return finish();                              // (the next chunk's forward rewrites a1, a2)
 }
 
+// ---- the network description of net_abi.h ---------------------------------------------------
+struct PN1 {
+    using Grad = GradState;
+    using Ws = WS;
+    static constexpr int HEAD = 256;
+    static constexpr bool BATCH_NORM = false;
+    static GradState grad(void* gradstate) { return gs_layout((float*)gradstate); }
+    static WS ws(void* workspace, int samples) { return ws_layout((char*)workspace, samples); }
+    static long params() { return P_TOTAL; }
+    static long head_w() { return P_OFF[16]; }
+    static long head_b() { return P_OFF[17]; }
+    // linear3 + CrossEntropyLoss (models.py:46, main.py:107); dropout2 precedes linear3
+    static float head_scale(int dropout) { return dropout ? SCALE_P50 : 1.f; }
+    static int pack(const GradState& g, const float* theta, hipStream_t st) {
+        return pack_weights(g, theta, st);
+    }
+    static int forward(const GradState& g, const WS& w, const float* theta, int S,
+                       const WorkerRec* workers, uint64_t seed, int dropout, int, float*,
+                       hipStream_t st) {
+        return flsim::forward(g, w, theta, S, workers, seed, dropout, st);
+    }
+    static int backward(void* gradstate, const GradState& g, const WS& w, const float* theta,
+                        int S, int dropout, hipStream_t st) {
+        std::lock_guard<std::mutex> lk(g_state_mu);
+        HostState* hs = find_state(gradstate);
+        FLSIM_REQUIRE(hs, "backward pass without flsim_pn1_begin_epoch on this gradstate");
+        return flsim::backward(g, w, theta, S, dropout, st, &hs->rows);
+    }
+    static int join(void* gradstate, hipStream_t st) { return pipe_join(gradstate, st); }
+    static StepPlan plan(const GradState& g, const void* gradstate) {
+        return plan_in_use(g, gradstate);
+    }
+};
+
+// (g_state_mu held) the backward of workspace rows [0, S) on the gradstate's backward stream,
+// after everything queued on `stream` so far; the workspace's event marks its end
+static int queue_backward(HostState& hs, const GradState& g, const WS& w, const void* workspace,
+                          const float* theta, int S, int dropout, hipStream_t stream) {
+    Pipe& p = hs.pipe;
+    if (!p.bs) {
+        // the lowest priority: the caller's forwards (the facade's per-call forward, whose loss
+        // the caller waits for) get the CUs first as the backward's blocks retire
+        int least = 0, greatest = 0;
+        FLSIM_CHECK_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
+        FLSIM_CHECK_HIP(hipStreamCreateWithPriority(&p.bs, hipStreamNonBlocking, least));
+        FLSIM_CHECK_HIP(hipEventCreateWithFlags(&p.fwd_done, hipEventDisableTiming));
+        FLSIM_CHECK_HIP(hipEventCreateWithFlags(&p.bwd_tail, hipEventDisableTiming));
+    }
+    hipEvent_t& ws_ev = p.ws_free[workspace];
+    if (!ws_ev) FLSIM_CHECK_HIP(hipEventCreateWithFlags(&ws_ev, hipEventDisableTiming));
+    FLSIM_CHECK_HIP(hipEventRecord(p.fwd_done, stream));
+    FLSIM_CHECK_HIP(hipStreamWaitEvent(p.bs, p.fwd_done, 0));
+    RC(backward(g, w, theta, S, dropout, p.bs, &hs.rows));
+    FLSIM_CHECK_HIP(hipEventRecord(ws_ev, p.bs));
+    p.pending = true;
+    return 0;
+}
+
+// one pipelined pass: `front` (batch fill, forward, loss) on `stream`, then the backward on the
+// gradstate's backward stream; a forward waits for the backward that last read its workspace
+template <class Front>
+static int run_pipelined(void* gradstate, void* workspace, int max_samples, const float* theta,
+                         int S, int dropout, hipStream_t stream, Front&& front) {
+    std::lock_guard<std::mutex> lk(g_state_mu);
+    HostState* hs = find_state(gradstate);
+    FLSIM_REQUIRE(hs, "backward pass without flsim_pn1_begin_epoch on this gradstate");
+    RC(wait_workspace(hs->pipe, workspace, stream));
+    const WS w = PN1::ws(workspace, max_samples);
+    const GradState g = PN1::grad(gradstate);
+    RC(front(g, w));
+    return queue_backward(*hs, g, w, workspace, theta, S, dropout, stream);
+}
+
 }  // namespace flsim
 
 using namespace flsim;
@@ -802,9 +891,7 @@ int flsim_pn1_workspace_offset(int which, int samples, long* offset_bytes) {
                        w.i1, w.i2, w.i3,
                        w.a1l, w.d1l, w.a3l, w.d2l, w.a5l, w.a6l, w.a4l, w.a2l, w.gxl,
                        w.a1f, w.d1f, w.a3f, w.d2f, w.a5f};
-    FLSIM_REQUIRE(which >= 0 && which < (int)(sizeof(p) / sizeof(p[0])), "bad workspace id %d", which);
-    *offset_bytes = (long)((const char*)p[which] - fake);
-    return 0;
+    return tensor_offset(p, (int)(sizeof(p) / sizeof(p[0])), fake, which, offset_bytes);
 }
 
 // a workspace tensor held in the split-bf16 form (split.h): the id of its L part (its HM part is
@@ -835,36 +922,26 @@ int flsim_pn1_begin_epoch(void* gradstate, const float* theta, hipStream_t strea
     FLSIM_CHECK_HIP(hipMemsetAsync(g.l3w, 0, (g.l3b + ZH * 10 - g.l3w) * 4, stream));
     FLSIM_CHECK_HIP(hipMemsetAsync((float*)gradstate + g.cnt_off, 0,
                                    step_counter_floats(g.plan) * 4, stream));
-    std::lock_guard<std::mutex> lk(g_rows_mu);
-    g_rows[gradstate] = EpochRows{{0, 0, 0, 0, 0, 0, 0, 0}};
+    std::lock_guard<std::mutex> lk(g_state_mu);
+    g_state[gradstate].rows = EpochRows{};
     return 0;
 }
 
-// forget the gradstate's slab-row table (the engine that owns the buffer is going away; the
-// caching allocator may hand the same address to a new engine)
+// forget the gradstate's host state (the engine that owns the buffer is going away; the caching
+// allocator may hand the same address to a new engine)
 void flsim_pn1_release(void* gradstate) {
-    pipe_release(gradstate);
-    std::lock_guard<std::mutex> lk(g_rows_mu);
-    g_rows.erase(gradstate);
-}
-
-static int run_chunk(void* gradstate, const WS& w, const float* theta, const WorkerRec* workers,
-                     int n_chunk_workers, uint64_t seed, int dropout, int backward_pass,
-                     float* worker_loss, hipStream_t stream,
-                     float gscale = 1.f / SAMPLES_PER_WORKER) {
-    const int S = n_chunk_workers * SAMPLES_PER_WORKER;
-    GradState g = gs_layout((float*)gradstate);
-    RC(forward(g, w, theta, S, workers, seed, dropout, stream));
-    // linear3 + CrossEntropyLoss (models.py:46, main.py:107); dropout2 precedes linear3
-    RC(head_and_loss<256>(w.e2, theta + P_OFF[16], theta + P_OFF[17], w.y, w.loss_s, w.dlog, w.dh2,
-                          S, backward_pass, dropout ? SCALE_P50 : 1.f, gscale, worker_loss,
-                          stream, workers));
-    if (backward_pass) {
-        EpochRows* er = epoch_rows(gradstate);
-        FLSIM_REQUIRE(er, "backward pass without flsim_pn1_begin_epoch on this gradstate");
-        RC(backward(g, w, theta, S, dropout, stream, er));
+    std::lock_guard<std::mutex> lk(g_state_mu);
+    HostState* hs = find_state(gradstate);
+    if (!hs) return;
+    Pipe& p = hs->pipe;
+    if (p.bs) {
+        (void)hipStreamSynchronize(p.bs);
+        for (auto& kv : p.ws_free) (void)hipEventDestroy(kv.second);
+        (void)hipEventDestroy(p.fwd_done);
+        (void)hipEventDestroy(p.bwd_tail);
+        (void)hipStreamDestroy(p.bs);
     }
-    return 0;
+    g_state.erase(gradstate);
 }
 
 int flsim_pn1_fwd_bwd_chunk(void* gradstate, void* workspace, int max_samples, const float* theta,
@@ -873,116 +950,32 @@ int flsim_pn1_fwd_bwd_chunk(void* gradstate, void* workspace, int max_samples, c
                             const WorkerRec* workers, int n_chunk_workers, int n_workers_total,
                             uint64_t seed, int dropout, int backward_pass, float* worker_loss,
                             hipStream_t stream) {
-    FLSIM_REQUIRE(gradstate && workspace && theta && pool && labels && list_a && list_b && lut &&
-                  workers && worker_loss, "null pointer");
-    FLSIM_REQUIRE(n_chunk_workers > 0, "empty chunk");
-    const int S = n_chunk_workers * SAMPLES_PER_WORKER;
-    FLSIM_REQUIRE(S <= max_samples, "chunk of %d samples exceeds workspace (%d)", S, max_samples);
-    FLSIM_REQUIRE(S <= 16384, "chunk of %d samples exceeds the 32-bit index budget", S);
-    FLSIM_REQUIRE(len_a > 0 && len_b > 0, "empty class list");
-    RC(pipe_join(gradstate, stream));
-    WS w = ws_layout((char*)workspace, max_samples);
-    hipLaunchKernelGGL(k_fill_batch, dim3(S), dim3(256), 0, stream, pool, labels, list_a, len_a,
-                       list_b, len_b, workers, n_workers_total, seed, lut, w.x0, w.y);
-    FLSIM_LAUNCH_CHECK();
-    return run_chunk(gradstate, w, theta, workers, n_chunk_workers, seed, dropout, backward_pass,
-                     worker_loss, stream);
+    const ChunkSrc src{pool, labels, list_a, len_a, list_b, len_b, lut, n_workers_total};
+    return net_fwd_bwd_chunk<PN1>(gradstate, workspace, max_samples, theta, src, workers,
+                                  n_chunk_workers, seed, dropout, backward_pass, worker_loss,
+                                  nullptr, stream);
 }
 
 // the same chunk, pipelined: fill + forward + head on `stream`, the backward on the gradstate's
 // backward stream after this forward and after the previous chunk's backward; `workspace` must
 // not be the one the previous call used (alternate two).  Losses are ordered on `stream`; the
 // gradients are complete for any later entry point on the gradstate (pipe_join).
-}  // extern "C"
-
-// one pipelined pass: `front` (batch fill, forward, loss) on `stream`, then the backward on the
-// gradstate's backward stream; a forward waits for the backward that last read its workspace
-// (g_pipe_mu held) the gradstate's pipe, its stream and events created on first use
-static int pipe_of(void* gradstate, Pipe** out) {
-    Pipe& p = g_pipes[gradstate];
-    if (!p.bs) {
-        // the lowest priority: the caller's forwards (the facade's per-call forward, whose loss
-        // the caller waits for) get the CUs first as the backward's blocks retire
-        int least = 0, greatest = 0;
-        FLSIM_CHECK_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
-        FLSIM_CHECK_HIP(hipStreamCreateWithPriority(&p.bs, hipStreamNonBlocking, least));
-        FLSIM_CHECK_HIP(hipEventCreateWithFlags(&p.fwd_done, hipEventDisableTiming));
-        FLSIM_CHECK_HIP(hipEventCreateWithFlags(&p.bwd_tail, hipEventDisableTiming));
-    }
-    *out = &p;
-    return 0;
-}
-
-// (g_pipe_mu held) the backward of workspace rows [0, S) on the gradstate's backward stream,
-// after everything queued on `stream` so far; the workspace's event marks its end
-static int queue_backward(void* gradstate, Pipe& p, hipEvent_t& ws_ev, void* workspace,
-                          int max_samples, const float* theta, int S, int dropout,
-                          hipStream_t stream, EpochRows* er) {
-    WS w = ws_layout((char*)workspace, max_samples);
-    GradState g = gs_layout((float*)gradstate);
-    FLSIM_CHECK_HIP(hipEventRecord(p.fwd_done, stream));
-    FLSIM_CHECK_HIP(hipStreamWaitEvent(p.bs, p.fwd_done, 0));
-    RC(backward(g, w, theta, S, dropout, p.bs, er));
-    FLSIM_CHECK_HIP(hipEventRecord(ws_ev, p.bs));
-    p.pending = true;
-    return 0;
-}
-
-template <class Front>
-static int run_pipelined(void* gradstate, void* workspace, int max_samples, const float* theta,
-                         int S, int dropout, hipStream_t stream, Front&& front) {
-    EpochRows* er = epoch_rows(gradstate);
-    FLSIM_REQUIRE(er, "backward pass without flsim_pn1_begin_epoch on this gradstate");
-    std::lock_guard<std::mutex> lk(g_pipe_mu);
-    Pipe* p = nullptr;
-    RC(pipe_of(gradstate, &p));
-    hipEvent_t& ws_ev = p->ws_free[workspace];
-    if (!ws_ev) FLSIM_CHECK_HIP(hipEventCreateWithFlags(&ws_ev, hipEventDisableTiming));
-    else FLSIM_CHECK_HIP(hipStreamWaitEvent(stream, ws_ev, 0));   // its last backward is done
-    WS w = ws_layout((char*)workspace, max_samples);
-    GradState g = gs_layout((float*)gradstate);
-    RC(front(g, w));
-    return queue_backward(gradstate, *p, ws_ev, workspace, max_samples, theta, S, dropout, stream,
-                          er);
-}
-
-// rows a queued backward still reads are not overwritten: `stream` waits for the last backward
-// that read this workspace
-static int wait_workspace(void* gradstate, void* workspace, hipStream_t stream) {
-    std::lock_guard<std::mutex> lk(g_pipe_mu);
-    auto it = g_pipes.find(gradstate);
-    if (it != g_pipes.end()) {
-        auto e = it->second.ws_free.find(workspace);
-        if (e != it->second.ws_free.end() && e->second)
-            FLSIM_CHECK_HIP(hipStreamWaitEvent(stream, e->second, 0));
-    }
-    return 0;
-}
-
-extern "C" {
-
 int flsim_pn1_fwd_bwd_chunk_async(void* gradstate, void* workspace, int max_samples,
                                   const float* theta, const uint8_t* pool, const int32_t* labels,
                                   const int32_t* list_a, int len_a, const int32_t* list_b,
                                   int len_b, const float* lut, const WorkerRec* workers,
                                   int n_chunk_workers, int n_workers_total, uint64_t seed,
                                   int dropout, float* worker_loss, hipStream_t stream) {
-    FLSIM_REQUIRE(gradstate && workspace && theta && pool && labels && list_a && list_b && lut &&
-                  workers && worker_loss, "null pointer");
-    FLSIM_REQUIRE(n_chunk_workers > 0, "empty chunk");
-    const int S = n_chunk_workers * SAMPLES_PER_WORKER;
-    FLSIM_REQUIRE(S <= max_samples, "chunk of %d samples exceeds workspace (%d)", S, max_samples);
-    FLSIM_REQUIRE(S <= 16384, "chunk of %d samples exceeds the 32-bit index budget", S);
-    FLSIM_REQUIRE(len_a > 0 && len_b > 0, "empty class list");
+    const ChunkSrc src{pool, labels, list_a, len_a, list_b, len_b, lut, n_workers_total};
+    FLSIM_REQUIRE(gradstate && workspace && theta && src.complete() && workers && worker_loss,
+                  "null pointer");
+    int S;
+    RC(check_chunk(n_chunk_workers, max_samples, len_a, len_b, &S));
     return run_pipelined(gradstate, workspace, max_samples, theta, S, dropout, stream,
                          [&](const GradState& g, const WS& w) -> int {
-        hipLaunchKernelGGL(k_fill_batch, dim3(S), dim3(256), 0, stream, pool, labels, list_a,
-                           len_a, list_b, len_b, workers, n_workers_total, seed, lut, w.x0, w.y);
-        FLSIM_LAUNCH_CHECK();
-        RC(forward(g, w, theta, S, workers, seed, dropout, stream));
-        return head_and_loss<256>(w.e2, theta + P_OFF[16], theta + P_OFF[17], w.y, w.loss_s,
-                                  w.dlog, w.dh2, S, 1, dropout ? SCALE_P50 : 1.f,
-                                  1.f / SAMPLES_PER_WORKER, worker_loss, stream, workers);
+        RC(fill_batch(src, workers, seed, w.x0, w.y, S, stream));
+        return forward_loss<PN1>(g, w, theta, S, workers, seed, dropout, 1,
+                                 1.f / SAMPLES_PER_WORKER, worker_loss, nullptr, stream);
     });
 }
 
@@ -994,20 +987,13 @@ int flsim_pn1_fwd_bwd_input_async(void* gradstate, void* workspace, int max_samp
                                   int dropout, float* worker_loss, hipStream_t stream) {
     FLSIM_REQUIRE(gradstate && workspace && theta && x && y && workers && worker_loss,
                   "null pointer");
-    FLSIM_REQUIRE(n_samples > 0, "empty batch");
-    const int S = ceil_div(n_samples, SAMPLES_PER_WORKER) * SAMPLES_PER_WORKER;
-    FLSIM_REQUIRE(S <= max_samples, "batch of %d samples exceeds workspace (%d)", n_samples,
-                  max_samples);
-    FLSIM_REQUIRE(S <= 16384, "batch of %d samples exceeds the 32-bit index budget", n_samples);
+    int S;
+    RC(check_batch(n_samples, max_samples, false, &S));
     return run_pipelined(gradstate, workspace, max_samples, theta, S, dropout, stream,
                          [&](const GradState& g, const WS& w) -> int {
-        hipLaunchKernelGGL(k_load_input, dim3(S), dim3(256), 0, stream, x, y, n_samples, w.x0,
-                           w.y);
-        FLSIM_LAUNCH_CHECK();
-        RC(forward(g, w, theta, S, workers, seed, dropout, stream));
-        return head_and_loss<256>(w.e2, theta + P_OFF[16], theta + P_OFF[17], w.y, w.loss_s,
-                                  w.dlog, w.dh2, S, 1, dropout ? SCALE_P50 : 1.f,
-                                  1.f / (float)n_samples, worker_loss, stream, workers);
+        RC(load_input(x, y, n_samples, w.x0, w.y, S, stream));
+        return forward_loss<PN1>(g, w, theta, S, workers, seed, dropout, 1,
+                                 1.f / (float)n_samples, worker_loss, nullptr, stream);
     });
 }
 
@@ -1024,24 +1010,13 @@ int flsim_pn1_fwd_rows(void* gradstate, void* workspace, int max_samples, int ro
                        hipStream_t stream) {
     FLSIM_REQUIRE(gradstate && workspace && theta && x && y && workers && worker_loss,
                   "null pointer");
-    FLSIM_REQUIRE(n_samples > 0, "empty batch");
-    FLSIM_REQUIRE(row0 >= 0 && row0 % SAMPLES_PER_WORKER == 0,
-                  "row0 %d is not a multiple of %d", row0, SAMPLES_PER_WORKER);
-    const int S = ceil_div(n_samples, SAMPLES_PER_WORKER) * SAMPLES_PER_WORKER;
-    FLSIM_REQUIRE((long)row0 + S <= max_samples, "rows [%d, %d) exceed workspace (%d)", row0,
-                  row0 + S, max_samples);
-    FLSIM_REQUIRE(max_samples <= 16384, "workspace of %d samples exceeds the 32-bit index budget",
-                  max_samples);
-    FLSIM_REQUIRE(epoch_rows(gradstate), "forward rows without flsim_pn1_begin_epoch");
-    RC(wait_workspace(gradstate, workspace, stream));
+    int S;
+    RC(check_batch_rows(n_samples, row0, max_samples, &S));
+    RC(begin_rows(gradstate, workspace, true, stream));
     WS w = ws_layout((char*)workspace, max_samples, row0);
-    GradState g = gs_layout((float*)gradstate);
-    hipLaunchKernelGGL(k_load_input, dim3(S), dim3(256), 0, stream, x, y, n_samples, w.x0, w.y);
-    FLSIM_LAUNCH_CHECK();
-    RC(forward(g, w, theta, S, workers, seed, dropout, stream));
-    return head_and_loss<256>(w.e2, theta + P_OFF[16], theta + P_OFF[17], w.y, w.loss_s, w.dlog,
-                              w.dh2, S, 1, dropout ? SCALE_P50 : 1.f, 1.f / (float)n_samples,
-                              worker_loss, stream, workers);
+    RC(load_input(x, y, n_samples, w.x0, w.y, S, stream));
+    return forward_loss<PN1>(PN1::grad(gradstate), w, theta, S, workers, seed, dropout, 1,
+                             1.f / (float)n_samples, worker_loss, nullptr, stream);
 }
 
 // The facade's deferred forward (Worker.fwd_bkwd of 128-sample batches): a call only stages its
@@ -1053,19 +1028,11 @@ int flsim_pn1_fwd_rows(void* gradstate, void* workspace, int max_samples, int ro
 int flsim_pn1_load_rows(void* gradstate, void* workspace, int max_samples, int row0,
                         const float* x, const int64_t* y, int n_samples, hipStream_t stream) {
     FLSIM_REQUIRE(gradstate && workspace && x && y, "null pointer");
-    FLSIM_REQUIRE(n_samples > 0, "empty batch");
-    FLSIM_REQUIRE(row0 >= 0 && row0 % SAMPLES_PER_WORKER == 0,
-                  "row0 %d is not a multiple of %d", row0, SAMPLES_PER_WORKER);
-    const int S = ceil_div(n_samples, SAMPLES_PER_WORKER) * SAMPLES_PER_WORKER;
-    FLSIM_REQUIRE((long)row0 + S <= max_samples, "rows [%d, %d) exceed workspace (%d)", row0,
-                  row0 + S, max_samples);
-    FLSIM_REQUIRE(max_samples <= 16384, "workspace of %d samples exceeds the 32-bit index budget",
-                  max_samples);
-    RC(wait_workspace(gradstate, workspace, stream));
+    int S;
+    RC(check_batch_rows(n_samples, row0, max_samples, &S));
+    RC(begin_rows(gradstate, workspace, false, stream));
     WS w = ws_layout((char*)workspace, max_samples, row0);
-    hipLaunchKernelGGL(k_load_input, dim3(S), dim3(256), 0, stream, x, y, n_samples, w.x0, w.y);
-    FLSIM_LAUNCH_CHECK();
-    return 0;
+    return load_input(x, y, n_samples, w.x0, w.y, S, stream);
 }
 
 // forward + CrossEntropyLoss of rows [row0, row0 + n_rows) staged by flsim_pn1_load_rows, every
@@ -1077,18 +1044,11 @@ int flsim_pn1_fwd_loaded_rows(void* gradstate, void* workspace, int max_samples,
     FLSIM_REQUIRE(gradstate && workspace && theta && workers && worker_loss, "null pointer");
     FLSIM_REQUIRE(row0 >= 0 && row0 % SAMPLES_PER_WORKER == 0 && n_rows > 0 &&
                   n_rows % SAMPLES_PER_WORKER == 0, "bad rows [%d, +%d)", row0, n_rows);
-    FLSIM_REQUIRE((long)row0 + n_rows <= max_samples, "rows [%d, %d) exceed workspace (%d)", row0,
-                  row0 + n_rows, max_samples);
-    FLSIM_REQUIRE(max_samples <= 16384, "workspace of %d samples exceeds the 32-bit index budget",
-                  max_samples);
-    FLSIM_REQUIRE(epoch_rows(gradstate), "forward rows without flsim_pn1_begin_epoch");
-    RC(wait_workspace(gradstate, workspace, stream));
-    WS w = ws_layout((char*)workspace, max_samples, row0);
-    GradState g = gs_layout((float*)gradstate);
-    RC(forward(g, w, theta, n_rows, workers, seed, dropout, stream));
-    return head_and_loss<256>(w.e2, theta + P_OFF[16], theta + P_OFF[17], w.y, w.loss_s, w.dlog,
-                              w.dh2, n_rows, 1, dropout ? SCALE_P50 : 1.f,
-                              1.f / SAMPLES_PER_WORKER, worker_loss, stream, workers);
+    RC(check_row_range(row0, n_rows, max_samples));
+    RC(begin_rows(gradstate, workspace, true, stream));
+    return forward_loss<PN1>(PN1::grad(gradstate), ws_layout((char*)workspace, max_samples, row0),
+                             theta, n_rows, workers, seed, dropout, 1, 1.f / SAMPLES_PER_WORKER,
+                             worker_loss, nullptr, stream);
 }
 
 // the backward of rows [0, n_rows) written by flsim_pn1_fwd_rows with this theta and dropout
@@ -1098,129 +1058,53 @@ int flsim_pn1_fwd_loaded_rows(void* gradstate, void* workspace, int max_samples,
 int flsim_pn1_bwd_rows(void* gradstate, void* workspace, int max_samples, int n_rows,
                        const float* theta, int dropout, hipStream_t stream) {
     FLSIM_REQUIRE(gradstate && workspace && theta, "null pointer");
-    FLSIM_REQUIRE(n_rows > 0 && n_rows % SAMPLES_PER_WORKER == 0 && n_rows <= max_samples &&
-                  n_rows <= 16384, "bad row count %d (workspace %d)", n_rows, max_samples);
-    EpochRows* er = epoch_rows(gradstate);
-    FLSIM_REQUIRE(er, "backward pass without flsim_pn1_begin_epoch on this gradstate");
-    std::lock_guard<std::mutex> lk(g_pipe_mu);
-    Pipe* p = nullptr;
-    RC(pipe_of(gradstate, &p));
-    hipEvent_t& ws_ev = p->ws_free[workspace];
-    if (!ws_ev) FLSIM_CHECK_HIP(hipEventCreateWithFlags(&ws_ev, hipEventDisableTiming));
-    return queue_backward(gradstate, *p, ws_ev, workspace, max_samples, theta, n_rows, dropout,
-                          stream, er);
+    RC(check_row_count(n_rows, max_samples));
+    std::lock_guard<std::mutex> lk(g_state_mu);
+    HostState* hs = find_state(gradstate);
+    FLSIM_REQUIRE(hs, "backward pass without flsim_pn1_begin_epoch on this gradstate");
+    return queue_backward(*hs, PN1::grad(gradstate), PN1::ws(workspace, max_samples), workspace,
+                          theta, n_rows, dropout, stream);
 }
 
-// explicit batch (the Worker.fwd_bkwd(inp, outp) facade, agents.py:32-35): x NCHW fp32, y int64,
-// any n_samples (main.py:43-44 --batch_size); the batch is padded to whole 128-sample groups
-// (padding has zero loss and gradient) and the CE gradient is the mean over the n samples.
-// workers[ceil(n/128)] give each group's dropout key; worker_loss[g] = group g's loss sum / 128.
 int flsim_pn1_fwd_bwd_input(void* gradstate, void* workspace, int max_samples, const float* theta,
                             const float* x, const int64_t* y, int n_samples,
                             const WorkerRec* workers, uint64_t seed, int dropout,
                             int backward_pass, float* worker_loss, hipStream_t stream) {
-    FLSIM_REQUIRE(gradstate && workspace && theta && x && y && workers && worker_loss,
-                  "null pointer");
-    FLSIM_REQUIRE(n_samples > 0, "empty batch");
-    const int S = ceil_div(n_samples, SAMPLES_PER_WORKER) * SAMPLES_PER_WORKER;
-    FLSIM_REQUIRE(S <= max_samples, "batch of %d samples exceeds workspace (%d)", n_samples,
-                  max_samples);
-    FLSIM_REQUIRE(S <= 16384, "batch of %d samples exceeds the 32-bit index budget", n_samples);
-    RC(pipe_join(gradstate, stream));
-    WS w = ws_layout((char*)workspace, max_samples);
-    hipLaunchKernelGGL(k_load_input, dim3(S), dim3(256), 0, stream, x, y, n_samples, w.x0, w.y);
-    FLSIM_LAUNCH_CHECK();
-    return run_chunk(gradstate, w, theta, workers, S / SAMPLES_PER_WORKER, seed, dropout,
-                     backward_pass, worker_loss, stream, 1.f / (float)n_samples);
+    return net_fwd_bwd_input<PN1>(gradstate, workspace, max_samples, theta, x, y, n_samples,
+                                  workers, seed, dropout, backward_pass, worker_loss, nullptr,
+                                  stream);
 }
 
-// Evaluation of an explicit batch (util.py:31-45: model(images) after central.model.eval(),
-// main.py:190): x NCHW fp32 [n][3][32][32] -> argmax predictions pred[n].  Re-packs theta.
 int flsim_pn1_eval_input(void* gradstate, void* workspace, int max_samples, const float* theta,
                          const float* x, int n_images, int32_t* pred, hipStream_t stream) {
     FLSIM_REQUIRE(gradstate && workspace && theta && x && pred, "null pointer");
     FLSIM_REQUIRE(n_images > 0, "empty batch");
-    FLSIM_REQUIRE(max_samples >= SAMPLES_PER_WORKER && max_samples % SAMPLES_PER_WORKER == 0,
-                  "max_samples must be a positive multiple of %d", SAMPLES_PER_WORKER);
-    GradState g = gs_layout((float*)gradstate);
-    RC(pipe_join(gradstate, stream));
-    WS w = ws_layout((char*)workspace, max_samples);
-    RC(pack_weights(g, theta, stream));
-    const int cap = max_samples < 16384 ? max_samples : 16384;
-    for (int c0 = 0; c0 < n_images; c0 += cap) {
-        const int n = n_images - c0 < cap ? n_images - c0 : cap;
-        const int S = ceil_div(n, SAMPLES_PER_WORKER) * SAMPLES_PER_WORKER;
-        hipLaunchKernelGGL(k_load_input, dim3(S), dim3(256), 0, stream, x + (long)c0 * 3072,
-                           (const int64_t*)nullptr, n, w.x0, w.y);
-        FLSIM_LAUNCH_CHECK();
-        RC(forward(g, w, theta, S, nullptr, 0, 0, stream));
-        RC(head_predict<256>(w.e2, theta + P_OFF[16], theta + P_OFF[17], w.y, w.loss_s, S,
-                             pred + c0, n, stream));
-    }
-    return 0;
+    return net_eval<PN1>(gradstate, workspace, max_samples, theta, nullptr, 0, n_images, nullptr,
+                         x, nullptr, pred, stream);
 }
 
-// Evaluation (util.py:31-45 print_test_accuracy; main.py:190 central.model.eval(), so dropout is
-// off): forward of pool images [first, first + n_images) in chunks of max_samples, argmax of the
-// logits into pred[n_images].  Re-packs theta (the next begin_epoch packs again).
 int flsim_pn1_eval_pool(void* gradstate, void* workspace, int max_samples, const float* theta,
                         const uint8_t* pool, int first, int n_images, const float* lut,
                         int32_t* pred, hipStream_t stream) {
-    FLSIM_REQUIRE(gradstate && workspace && theta && pool && lut && pred, "null pointer");
-    FLSIM_REQUIRE(n_images > 0 && first >= 0, "bad image range");
-    FLSIM_REQUIRE(max_samples >= SAMPLES_PER_WORKER && max_samples % SAMPLES_PER_WORKER == 0,
-                  "max_samples must be a positive multiple of %d", SAMPLES_PER_WORKER);
-    GradState g = gs_layout((float*)gradstate);
-    RC(pipe_join(gradstate, stream));
-    WS w = ws_layout((char*)workspace, max_samples);
-    RC(pack_weights(g, theta, stream));
-    const int cap = max_samples < 16384 ? max_samples : 16384;   // 32-bit index budget
-    for (int c0 = 0; c0 < n_images; c0 += cap) {
-        const int n = n_images - c0 < cap ? n_images - c0 : cap;
-        const int S = ceil_div(n, SAMPLES_PER_WORKER) * SAMPLES_PER_WORKER;
-        hipLaunchKernelGGL(k_fill_seq, dim3(S), dim3(256), 0, stream, pool, first + c0, n, lut,
-                           w.x0, w.y);
-        FLSIM_LAUNCH_CHECK();
-        RC(forward(g, w, theta, S, nullptr, 0, 0, stream));
-        RC(head_predict<256>(w.e2, theta + P_OFF[16], theta + P_OFF[17], w.y, w.loss_s, S,
-                             pred + c0, n, stream));
-    }
-    return 0;
+    return net_eval<PN1>(gradstate, workspace, max_samples, theta, pool, first, n_images, lut,
+                         nullptr, nullptr, pred, stream);
 }
 
-// S_t (torch named_parameters layout, P floats) = sum of the epoch's slabs (fixed order)
 int flsim_pn1_end_epoch(void* gradstate, float* grad_out, hipStream_t stream) {
-    FLSIM_REQUIRE(gradstate && grad_out, "null pointer");
-    RC(pipe_join(gradstate, stream));
-    GradState g = gs_layout((float*)gradstate);
-    return slab_step_launch((float*)gradstate, plan_in_use(g, gradstate), g.cnt_off, g.part_off,
-                            grad_out, nullptr, nullptr, nullptr, nullptr, nullptr, P_TOTAL, stream);
+    return net_end_epoch<PN1>(gradstate, grad_out, stream);
 }
 
-// the same reduction fused with rule() + Adam (world = 1)
 int flsim_pn1_server_step(void* gradstate, float* S_out, const flsim_rule* rule, float* p,
                           float* m, float* v, long step, double lr, double beta1, double beta2,
                           double eps, hipStream_t stream) {
-    const flsim_optim o = adam_optim(lr, beta1, beta2, eps);
-    return flsim_pn1_server_step_optim(gradstate, S_out, rule, p, m, v, step, &o, stream);
+    return net_server_step<PN1>(gradstate, S_out, rule, p, m, v, step, lr, beta1, beta2, eps,
+                                stream);
 }
 
-// ... with the update rule of `optim` (include/flsim.h: SGD, Adam with weight decay, AdamW)
 int flsim_pn1_server_step_optim(void* gradstate, float* S_out, const flsim_rule* rule, float* p,
                                 float* m, float* v, long step, const flsim_optim* optim,
                                 hipStream_t stream) {
-    RC(check_optim(optim));
-    const int nstate = optim->kind == FLSIM_OPT_SGD ? (optim->momentum != 0.0 ? 1 : 0) : 2;
-    FLSIM_REQUIRE(gradstate && rule && p && (m || nstate < 1) && (v || nstate < 2),
-                  "null pointer");
-    RC(pipe_join(gradstate, stream));
-    GradState g = gs_layout((float*)gradstate);
-    RuleProg R;
-    RC(make_rule(rule, &R));
-    OptLaunch ol;
-    RC(make_opt_launch(optim, rule->k, step, &ol));
-    return slab_step_launch_optim((float*)gradstate, plan_in_use(g, gradstate), g.cnt_off,
-                                  g.part_off, S_out, &R, ol, p, m, v, P_TOTAL, stream);
+    return net_server_step_optim<PN1>(gradstate, S_out, rule, p, m, v, step, optim, stream);
 }
 
 }  // extern "C"

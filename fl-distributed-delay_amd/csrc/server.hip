@@ -1112,7 +1112,7 @@ int flsim_aggregate_optim_rule_push(const float* S, float* S_out, const flsim_ru
                                     int n_tensors, long step, const flsim_optim* optim,
                                     hipStream_t stream) {
     RC(check_optim(optim));
-    const int nstate = optim->kind == FLSIM_OPT_SGD ? (optim->momentum != 0.0 ? 1 : 0) : 2;
+    const int nstate = optim_n_state(optim);
     FLSIM_REQUIRE(S && p && (m || nstate < 1) && (v || nstate < 2) && tensor_sizes && rule,
                   "null pointer");
     if (nstate < 2) v = nullptr;

@@ -140,6 +140,10 @@ struct AdamConst {
 //   OK_SGD    torch.optim.SGD with momentum == 0: p only; m and v untouched
 enum OptKind { OK_ADAM = 0, OK_ADAMD = 1, OK_SGDM = 2, OK_SGD = 3 };
 constexpr int opt_n_state(int ok) { return ok <= OK_ADAMD ? 2 : (ok == OK_SGDM ? 1 : 0); }
+// the same count from a checked flsim_optim (check_optim), before its OptLaunch is made
+inline int optim_n_state(const flsim_optim* o) {
+    return o->kind == FLSIM_OPT_SGD ? (o->momentum != 0.0 ? 1 : 0) : 2;
+}
 
 // what the kinds other than OK_ADAM need besides AdamConst (whose fk, rk every kind uses)
 enum { OF_DECOUPLED = 1, OF_WD = 2, OF_NESTEROV = 4, OF_FIRST = 8 };

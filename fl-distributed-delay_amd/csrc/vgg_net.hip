@@ -20,7 +20,7 @@
 // normalisation + ReLU (+ pool / dropout).  The backward turns the masked gradient of each
 // BatchNorm output into dz in place before the conv's weight / data gradients.
 #include "bn_kernels.h"
-#include "slabstep.h"
+#include "net_abi.h"
 
 namespace flsim {
 
@@ -418,24 +418,42 @@ static int vbackward(const VGrad& g, const VWS& w, const float* th, const VOff& 
     return 0;
 }
 
+// ---- the network descriptions of net_abi.h: vgg11 (BN = false) and vgg11_bn -------------------
 template <bool BN>
-static int vrun_chunk(void* gradstate, const VWS& w, const float* theta, const WorkerRec* workers,
-                      int n_chunk_workers, uint64_t seed, int dropout, int backward_pass,
-                      float* worker_loss, float* bn_stats, hipStream_t stream,
-                      float gscale = 1.f / SAMPLES_PER_WORKER) {
-    const int S = n_chunk_workers * SAMPLES_PER_WORKER;
-    const VOff o = voff(BN);
-    VGrad g = vgs_layout((float*)gradstate, BN);
-    const VBN bn{&w, 1, bn_stats};
-    RC(vforward<BN>(g, w, theta, o, S, workers, seed, dropout, &bn, stream));
-    // Linear(512,10) + CrossEntropyLoss (models.py:64, main.py:107); no dropout after the ReLU
-    RC(head_and_loss<VFEAT>(w.e2, theta + o.l3w, theta + o.l3b, w.y, w.loss_s, w.dlog, w.dh2, S,
-                            backward_pass, 1.f, gscale, worker_loss, stream, workers));
-    if (backward_pass) RC(vbackward<BN>(g, w, theta, o, S, dropout, stream));
-    return 0;
-}
+struct VggNet {
+    using Grad = VGrad;
+    using Ws = VWS;
+    static constexpr int HEAD = VFEAT;
+    static constexpr bool BATCH_NORM = BN;
+    static VGrad grad(void* gradstate) { return vgs_layout((float*)gradstate, BN); }
+    static VWS ws(void* workspace, int samples) { return vws_layout((char*)workspace, samples, BN); }
+    static long params() { return voff(BN).total; }
+    static long head_w() { return voff(BN).l3w; }
+    static long head_b() { return voff(BN).l3b; }
+    static float head_scale(int) { return 1.f; }      // no dropout after the last ReLU
+    static int pack(const VGrad& g, const float* th, hipStream_t st) {
+        return vpack(g, th, voff(BN), st);
+    }
+    static int forward(const VGrad& g, const VWS& w, const float* th, int S,
+                       const WorkerRec* workers, uint64_t seed, int dropout, int train,
+                       float* bn_stats, hipStream_t st) {
+        const VBN bn{&w, train, bn_stats};
+        return vforward<BN>(g, w, th, voff(BN), S, workers, seed, dropout, &bn, st);
+    }
+    static int eval_coef(const VWS& w, const float* running, hipStream_t st) {
+        return vbn_eval_coef(w, running, st);
+    }
+    static int backward(void*, const VGrad& g, const VWS& w, const float* th, int S, int dropout,
+                        hipStream_t st) {
+        return vbackward<BN>(g, w, th, voff(BN), S, dropout, st);
+    }
+    static int join(void*, hipStream_t) { return 0; }      // every pass runs on the caller's stream
+    static StepPlan plan(const VGrad& g, const void*) { return g.plan; }
+};
+using V11 = VggNet<false>;
+using V11BN = VggNet<true>;
 
-// ---- the C-ABI bodies, shared by vgg11 (BN = false) and vgg11_bn ----------------------------
+// ---- the C-ABI bodies that differ from PerformantNet1's ---------------------------------------
 template <bool BN>
 static int vgg_workspace_offset(int which, int samples, long* offset_bytes) {
     char* const fake = reinterpret_cast<char*>(4096);   // layout only; never dereferenced
@@ -448,11 +466,7 @@ static int vgg_workspace_offset(int which, int samples, long* offset_bytes) {
                        w.bmean[6], w.bmean[7],
                        w.binv[0], w.binv[1], w.binv[2], w.binv[3], w.binv[4], w.binv[5],
                        w.binv[6], w.binv[7]};
-    const int n = BN ? (int)(sizeof(p) / sizeof(p[0])) : 24;
-    FLSIM_REQUIRE(offset_bytes, "null pointer");
-    FLSIM_REQUIRE(which >= 0 && which < n, "bad workspace id %d", which);
-    *offset_bytes = (long)((const char*)p[which] - fake);
-    return 0;
+    return tensor_offset(p, BN ? (int)(sizeof(p) / sizeof(p[0])) : 24, fake, which, offset_bytes);
 }
 
 template <bool BN>
@@ -464,53 +478,6 @@ static int vgg_begin_epoch(void* gradstate, const float* theta, hipStream_t stre
     return 0;
 }
 
-template <bool BN>
-static int vgg_fwd_bwd_chunk(void* gradstate, void* workspace, int max_samples,
-                             const float* theta, const uint8_t* pool, const int32_t* labels,
-                             const int32_t* list_a, int len_a, const int32_t* list_b, int len_b,
-                             const float* lut, const WorkerRec* workers, int n_chunk_workers,
-                             int n_workers_total, uint64_t seed, int dropout, int backward_pass,
-                             float* worker_loss, float* bn_stats, hipStream_t stream) {
-    FLSIM_REQUIRE(gradstate && workspace && theta && pool && labels && list_a && list_b && lut &&
-                  workers && worker_loss, "null pointer");
-    FLSIM_REQUIRE(n_chunk_workers > 0, "empty chunk");
-    const int S = n_chunk_workers * SAMPLES_PER_WORKER;
-    FLSIM_REQUIRE(S <= max_samples, "chunk of %d samples exceeds workspace (%d)", S, max_samples);
-    FLSIM_REQUIRE(S <= 16384, "chunk of %d samples exceeds the 32-bit index budget", S);
-    FLSIM_REQUIRE(len_a > 0 && len_b > 0, "empty class list");
-    VWS w = vws_layout((char*)workspace, max_samples, BN);
-    hipLaunchKernelGGL(k_fill_batch, dim3(S), dim3(256), 0, stream, pool, labels, list_a, len_a,
-                       list_b, len_b, workers, n_workers_total, seed, lut, w.x0, w.y);
-    FLSIM_LAUNCH_CHECK();
-    return vrun_chunk<BN>(gradstate, w, theta, workers, n_chunk_workers, seed, dropout,
-                          backward_pass, worker_loss, bn_stats, stream);
-}
-
-template <bool BN>
-static int vgg_fwd_bwd_input(void* gradstate, void* workspace, int max_samples,
-                             const float* theta, const float* x, const int64_t* y, int n_samples,
-                             const WorkerRec* workers, uint64_t seed, int dropout,
-                             int backward_pass, float* worker_loss, float* bn_stats,
-                             hipStream_t stream) {
-    FLSIM_REQUIRE(gradstate && workspace && theta && x && y && workers && worker_loss,
-                  "null pointer");
-    FLSIM_REQUIRE(n_samples > 0, "empty batch");
-    // vgg11_bn: one BatchNorm batch per 128-sample group, so only whole groups
-    FLSIM_REQUIRE(!BN || n_samples % SAMPLES_PER_WORKER == 0,
-                  "vgg11_bn batch of %d samples: must be a multiple of %d", n_samples,
-                  SAMPLES_PER_WORKER);
-    const int S = ceil_div(n_samples, SAMPLES_PER_WORKER) * SAMPLES_PER_WORKER;
-    FLSIM_REQUIRE(S <= max_samples, "batch of %d samples exceeds workspace (%d)", n_samples,
-                  max_samples);
-    FLSIM_REQUIRE(S <= 16384, "batch of %d samples exceeds the 32-bit index budget", n_samples);
-    VWS w = vws_layout((char*)workspace, max_samples, BN);
-    hipLaunchKernelGGL(k_load_input, dim3(S), dim3(256), 0, stream, x, y, n_samples, w.x0, w.y);
-    FLSIM_LAUNCH_CHECK();
-    return vrun_chunk<BN>(gradstate, w, theta, workers, S / SAMPLES_PER_WORKER, seed, dropout,
-                          backward_pass, worker_loss, bn_stats, stream,
-                          BN ? 1.f / SAMPLES_PER_WORKER : 1.f / (float)n_samples);
-}
-
 // The facade's deferred fwd_bkwd for vgg11 (Worker.fwd_bkwd of 128-sample batches, agents.py:32-40):
 // a call stages its batch into workspace rows [row0, row0 + 128) (vgg_load_rows); the forward,
 // loss and backward of the staged rows [0, n_rows) then run as ONE worker-batched pass
@@ -519,17 +486,10 @@ template <bool BN>
 static int vgg_load_rows(void* gradstate, void* workspace, int max_samples, int row0,
                          const float* x, const int64_t* y, int n_samples, hipStream_t stream) {
     FLSIM_REQUIRE(gradstate && workspace && x && y, "null pointer");
-    FLSIM_REQUIRE(n_samples > 0, "empty batch");
-    FLSIM_REQUIRE(row0 >= 0 && row0 % SAMPLES_PER_WORKER == 0,
-                  "row0 %d is not a multiple of %d", row0, SAMPLES_PER_WORKER);
-    const int S = ceil_div(n_samples, SAMPLES_PER_WORKER) * SAMPLES_PER_WORKER;
-    FLSIM_REQUIRE((long)row0 + S <= max_samples && max_samples <= 16384,
-                  "rows [%d, %d) exceed workspace (%d)", row0, row0 + S, max_samples);
+    int S;
+    RC(check_batch_rows(n_samples, row0, max_samples, &S));
     VWS w = vws_layout((char*)workspace, max_samples, BN);
-    hipLaunchKernelGGL(k_load_input, dim3(S), dim3(256), 0, stream, x, y, n_samples,
-                       w.x0 + (long)row0 * 4096, w.y + row0);
-    FLSIM_LAUNCH_CHECK();
-    return 0;
+    return load_input(x, y, n_samples, w.x0 + (long)row0 * 4096, w.y + row0, S, stream);
 }
 
 template <bool BN>
@@ -539,85 +499,10 @@ static int vgg_fwd_bwd_loaded_rows(void* gradstate, void* workspace, int max_sam
                                    hipStream_t stream) {
     FLSIM_REQUIRE(gradstate && workspace && theta && workers && worker_loss, "null pointer");
     FLSIM_REQUIRE(!BN || bn_stats, "null bn_stats");
-    FLSIM_REQUIRE(n_rows > 0 && n_rows % SAMPLES_PER_WORKER == 0 && n_rows <= max_samples &&
-                  n_rows <= 16384, "bad row count %d (workspace %d)", n_rows, max_samples);
-    VWS w = vws_layout((char*)workspace, max_samples, BN);
-    return vrun_chunk<BN>(gradstate, w, theta, workers, n_rows / SAMPLES_PER_WORKER, seed, dropout,
-                          1, worker_loss, bn_stats, stream);
-}
-
-// Evaluation (util.py:31-45 after central.model.eval(), main.py:190: dropout off; vgg11_bn:
-// BatchNorm with the running buffers)
-template <bool BN>
-static int vgg_eval_pool(void* gradstate, void* workspace, int max_samples, const float* theta,
-                         const uint8_t* pool, int first, int n_images, const float* lut,
-                         const float* running, int32_t* pred, hipStream_t stream,
-                         const float* xin = nullptr) {
-    // xin != nullptr: an explicit NCHW fp32 batch (util.py:31-45 over a test loader) instead of
-    // pool images
-    FLSIM_REQUIRE(gradstate && workspace && theta && (xin || (pool && lut)) && pred,
-                  "null pointer");
-    FLSIM_REQUIRE(!BN || running, "null running buffers");
-    FLSIM_REQUIRE(n_images > 0 && first >= 0, "bad image range");
-    FLSIM_REQUIRE(max_samples >= SAMPLES_PER_WORKER && max_samples % SAMPLES_PER_WORKER == 0,
-                  "max_samples must be a positive multiple of %d", SAMPLES_PER_WORKER);
-    const VOff o = voff(BN);
-    VGrad g = vgs_layout((float*)gradstate, BN);
-    VWS w = vws_layout((char*)workspace, max_samples, BN);
-    RC(vpack(g, theta, o, stream));
-    const VBN bn{&w, 0, nullptr};
-    if (BN) RC(vbn_eval_coef(w, running, stream));
-    const int cap = max_samples < 16384 ? max_samples : 16384;   // 32-bit index budget
-    for (int c0 = 0; c0 < n_images; c0 += cap) {
-        const int n = n_images - c0 < cap ? n_images - c0 : cap;
-        const int S = ceil_div(n, SAMPLES_PER_WORKER) * SAMPLES_PER_WORKER;
-        if (xin)
-            hipLaunchKernelGGL(k_load_input, dim3(S), dim3(256), 0, stream, xin + (long)c0 * 3072,
-                               (const int64_t*)nullptr, n, w.x0, w.y);
-        else
-            hipLaunchKernelGGL(k_fill_seq, dim3(S), dim3(256), 0, stream, pool, first + c0, n, lut,
-                               w.x0, w.y);
-        FLSIM_LAUNCH_CHECK();
-        RC(vforward<BN>(g, w, theta, o, S, nullptr, 0, 0, &bn, stream));
-        RC(head_predict<VFEAT>(w.e2, theta + o.l3w, theta + o.l3b, w.y, w.loss_s, S, pred + c0, n,
-                               stream));
-    }
-    return 0;
-}
-
-// S_t (torch named_parameters layout) = sum of the epoch's slabs (fixed order)
-template <bool BN>
-static int vgg_end_epoch(void* gradstate, float* grad_out, hipStream_t stream) {
-    FLSIM_REQUIRE(gradstate && grad_out, "null pointer");
-    VGrad g = vgs_layout((float*)gradstate, BN);
-    return slab_step_launch((float*)gradstate, g.plan, g.cnt_off, g.part_off, grad_out, nullptr,
-                            nullptr, nullptr, nullptr, nullptr, voff(BN).total, stream);
-}
-
-// the same reduction fused with rule() + Adam (world = 1)
-template <bool BN>
-static int vgg_server_step_optim(void* gradstate, float* S_out, const flsim_rule* rule, float* p,
-                                 float* m, float* v, long step, const flsim_optim* optim,
-                                 hipStream_t stream) {
-    RC(check_optim(optim));
-    const int nstate = optim->kind == FLSIM_OPT_SGD ? (optim->momentum != 0.0 ? 1 : 0) : 2;
-    FLSIM_REQUIRE(gradstate && rule && p && (m || nstate < 1) && (v || nstate < 2),
-                  "null pointer");
-    VGrad g = vgs_layout((float*)gradstate, BN);
-    RuleProg R;
-    RC(make_rule(rule, &R));
-    OptLaunch ol;
-    RC(make_opt_launch(optim, rule->k, step, &ol));
-    return slab_step_launch_optim((float*)gradstate, g.plan, g.cnt_off, g.part_off, S_out, &R, ol,
-                                  p, m, v, voff(BN).total, stream);
-}
-
-template <bool BN>
-static int vgg_server_step(void* gradstate, float* S_out, const flsim_rule* rule, float* p,
-                           float* m, float* v, long step, double lr, double beta1, double beta2,
-                           double eps, hipStream_t stream) {
-    const flsim_optim o = adam_optim(lr, beta1, beta2, eps);
-    return vgg_server_step_optim<BN>(gradstate, S_out, rule, p, m, v, step, &o, stream);
+    RC(check_row_count(n_rows, max_samples));
+    return run_chunk<VggNet<BN>>(gradstate, vws_layout((char*)workspace, max_samples, BN), theta,
+                                 workers, n_rows, seed, dropout, 1, 1.f / SAMPLES_PER_WORKER,
+                                 worker_loss, bn_stats, stream);
 }
 
 }  // namespace flsim
@@ -651,19 +536,19 @@ int flsim_vgg11_fwd_bwd_chunk(void* gradstate, void* workspace, int max_samples,
                               const float* lut, const WorkerRec* workers, int n_chunk_workers,
                               int n_workers_total, uint64_t seed, int dropout, int backward_pass,
                               float* worker_loss, hipStream_t stream) {
-    return vgg_fwd_bwd_chunk<false>(gradstate, workspace, max_samples, theta, pool, labels, list_a,
-                                    len_a, list_b, len_b, lut, workers, n_chunk_workers,
-                                    n_workers_total, seed, dropout, backward_pass, worker_loss,
-                                    nullptr, stream);
+    const ChunkSrc src{pool, labels, list_a, len_a, list_b, len_b, lut, n_workers_total};
+    return net_fwd_bwd_chunk<V11>(gradstate, workspace, max_samples, theta, src, workers,
+                                  n_chunk_workers, seed, dropout, backward_pass, worker_loss,
+                                  nullptr, stream);
 }
 
 int flsim_vgg11_fwd_bwd_input(void* gradstate, void* workspace, int max_samples,
                               const float* theta, const float* x, const int64_t* y, int n_samples,
                               const WorkerRec* workers, uint64_t seed, int dropout,
                               int backward_pass, float* worker_loss, hipStream_t stream) {
-    return vgg_fwd_bwd_input<false>(gradstate, workspace, max_samples, theta, x, y, n_samples,
-                                    workers, seed, dropout, backward_pass, worker_loss, nullptr,
-                                    stream);
+    return net_fwd_bwd_input<V11>(gradstate, workspace, max_samples, theta, x, y, n_samples,
+                                  workers, seed, dropout, backward_pass, worker_loss, nullptr,
+                                  stream);
 }
 
 int flsim_vgg11_load_rows(void* gradstate, void* workspace, int max_samples, int row0,
@@ -680,6 +565,7 @@ int flsim_vgg11_fwd_bwd_loaded_rows(void* gradstate, void* workspace, int max_sa
 
 int flsim_vgg11_bn_load_rows(void* gradstate, void* workspace, int max_samples, int row0,
                              const float* x, const int64_t* y, int n_samples, hipStream_t stream) {
+    // one BatchNorm batch per 128-sample group, so only whole groups
     FLSIM_REQUIRE(n_samples % SAMPLES_PER_WORKER == 0,
                   "vgg11_bn batch of %d samples: must be a multiple of %d", n_samples,
                   SAMPLES_PER_WORKER);
@@ -697,31 +583,31 @@ int flsim_vgg11_bn_fwd_bwd_loaded_rows(void* gradstate, void* workspace, int max
 int flsim_vgg11_eval_pool(void* gradstate, void* workspace, int max_samples, const float* theta,
                           const uint8_t* pool, int first, int n_images, const float* lut,
                           int32_t* pred, hipStream_t stream) {
-    return vgg_eval_pool<false>(gradstate, workspace, max_samples, theta, pool, first, n_images,
-                                lut, nullptr, pred, stream);
+    return net_eval<V11>(gradstate, workspace, max_samples, theta, pool, first, n_images, lut,
+                         nullptr, nullptr, pred, stream);
 }
 
 int flsim_vgg11_eval_input(void* gradstate, void* workspace, int max_samples, const float* theta,
                            const float* x, int n_images, int32_t* pred, hipStream_t stream) {
-    return vgg_eval_pool<false>(gradstate, workspace, max_samples, theta, nullptr, 0, n_images,
-                                nullptr, nullptr, pred, stream, x);
+    return net_eval<V11>(gradstate, workspace, max_samples, theta, nullptr, 0, n_images, nullptr,
+                         x, nullptr, pred, stream);
 }
 
 int flsim_vgg11_end_epoch(void* gradstate, float* grad_out, hipStream_t stream) {
-    return vgg_end_epoch<false>(gradstate, grad_out, stream);
+    return net_end_epoch<V11>(gradstate, grad_out, stream);
 }
 
 int flsim_vgg11_server_step(void* gradstate, float* S_out, const flsim_rule* rule, float* p,
                             float* m, float* v, long step, double lr, double beta1, double beta2,
                             double eps, hipStream_t stream) {
-    return vgg_server_step<false>(gradstate, S_out, rule, p, m, v, step, lr, beta1, beta2, eps,
-                                  stream);
+    return net_server_step<V11>(gradstate, S_out, rule, p, m, v, step, lr, beta1, beta2, eps,
+                                stream);
 }
 
 int flsim_vgg11_server_step_optim(void* gradstate, float* S_out, const flsim_rule* rule, float* p,
                                   float* m, float* v, long step, const flsim_optim* optim,
                                   hipStream_t stream) {
-    return vgg_server_step_optim<false>(gradstate, S_out, rule, p, m, v, step, optim, stream);
+    return net_server_step_optim<V11>(gradstate, S_out, rule, p, m, v, step, optim, stream);
 }
 
 // ---- vgg11_bn -------------------------------------------------------------------------------
@@ -750,10 +636,10 @@ int flsim_vgg11_bn_fwd_bwd_chunk(void* gradstate, void* workspace, int max_sampl
                                  int n_chunk_workers, int n_workers_total, uint64_t seed,
                                  int dropout, int backward_pass, float* worker_loss,
                                  float* bn_stats, hipStream_t stream) {
-    return vgg_fwd_bwd_chunk<true>(gradstate, workspace, max_samples, theta, pool, labels, list_a,
-                                   len_a, list_b, len_b, lut, workers, n_chunk_workers,
-                                   n_workers_total, seed, dropout, backward_pass, worker_loss,
-                                   bn_stats, stream);
+    const ChunkSrc src{pool, labels, list_a, len_a, list_b, len_b, lut, n_workers_total};
+    return net_fwd_bwd_chunk<V11BN>(gradstate, workspace, max_samples, theta, src, workers,
+                                    n_chunk_workers, seed, dropout, backward_pass, worker_loss,
+                                    bn_stats, stream);
 }
 
 int flsim_vgg11_bn_fwd_bwd_input(void* gradstate, void* workspace, int max_samples,
@@ -761,41 +647,41 @@ int flsim_vgg11_bn_fwd_bwd_input(void* gradstate, void* workspace, int max_sampl
                                  int n_samples, const WorkerRec* workers, uint64_t seed,
                                  int dropout, int backward_pass, float* worker_loss,
                                  float* bn_stats, hipStream_t stream) {
-    return vgg_fwd_bwd_input<true>(gradstate, workspace, max_samples, theta, x, y, n_samples,
-                                   workers, seed, dropout, backward_pass, worker_loss, bn_stats,
-                                   stream);
+    return net_fwd_bwd_input<V11BN>(gradstate, workspace, max_samples, theta, x, y, n_samples,
+                                    workers, seed, dropout, backward_pass, worker_loss, bn_stats,
+                                    stream);
 }
 
 int flsim_vgg11_bn_eval_pool(void* gradstate, void* workspace, int max_samples,
                              const float* theta, const uint8_t* pool, int first, int n_images,
                              const float* lut, const float* running, int32_t* pred,
                              hipStream_t stream) {
-    return vgg_eval_pool<true>(gradstate, workspace, max_samples, theta, pool, first, n_images,
-                               lut, running, pred, stream);
+    return net_eval<V11BN>(gradstate, workspace, max_samples, theta, pool, first, n_images, lut,
+                           nullptr, running, pred, stream);
 }
 
 int flsim_vgg11_bn_eval_input(void* gradstate, void* workspace, int max_samples,
                               const float* theta, const float* x, int n_images,
                               const float* running, int32_t* pred, hipStream_t stream) {
-    return vgg_eval_pool<true>(gradstate, workspace, max_samples, theta, nullptr, 0, n_images,
-                               nullptr, running, pred, stream, x);
+    return net_eval<V11BN>(gradstate, workspace, max_samples, theta, nullptr, 0, n_images,
+                           nullptr, x, running, pred, stream);
 }
 
 int flsim_vgg11_bn_end_epoch(void* gradstate, float* grad_out, hipStream_t stream) {
-    return vgg_end_epoch<true>(gradstate, grad_out, stream);
+    return net_end_epoch<V11BN>(gradstate, grad_out, stream);
 }
 
 int flsim_vgg11_bn_server_step(void* gradstate, float* S_out, const flsim_rule* rule, float* p,
                                float* m, float* v, long step, double lr, double beta1,
                                double beta2, double eps, hipStream_t stream) {
-    return vgg_server_step<true>(gradstate, S_out, rule, p, m, v, step, lr, beta1, beta2, eps,
-                                 stream);
+    return net_server_step<V11BN>(gradstate, S_out, rule, p, m, v, step, lr, beta1, beta2, eps,
+                                  stream);
 }
 
 int flsim_vgg11_bn_server_step_optim(void* gradstate, float* S_out, const flsim_rule* rule,
                                      float* p, float* m, float* v, long step,
                                      const flsim_optim* optim, hipStream_t stream) {
-    return vgg_server_step_optim<true>(gradstate, S_out, rule, p, m, v, step, optim, stream);
+    return net_server_step_optim<V11BN>(gradstate, S_out, rule, p, m, v, step, optim, stream);
 }
 
 int flsim_vgg11_bn_update_running(float* running, const float* bn_stats, int n_workers,
@@ -810,3 +696,4 @@ int flsim_vgg11_bn_update_running(float* running, const float* bn_stats, int n_w
 }
 
 }  // extern "C"
+

@@ -120,6 +120,11 @@ def as_optim(optim):
     return optim if isinstance(optim, Optim) else Optim(**dict(optim))
 
 
+def _batch(x, y):
+    """An explicit batch as the entry points read it: x contiguous, y contiguous int64."""
+    return x.contiguous(), y.to(torch.int64).contiguous()
+
+
 def padded(n, q=64):
     return (n + q - 1) // q * q
 
@@ -196,9 +201,7 @@ class NetEngine:
 
     def run_chunk_async(self, theta, pool, workers_dev, n_chunk, n_workers_total, seed, dropout,
                         loss_out, slot):
-        if getattr(self, "workspace2", None) is None:
-            self.workspace2 = torch.empty_like(self.workspace)
-        ws = self.workspace if slot % 2 == 0 else self.workspace2
+        ws = self._slot_workspace(slot)
         self.last_workspace = ws
         check(lib().flsim_pn1_fwd_bwd_chunk_async(
             ptr(self.gradstate), ptr(ws), self.max_samples, ptr(theta),
@@ -210,12 +213,9 @@ class NetEngine:
     def run_input_async(self, theta, x, y, workers_dev, seed, dropout, loss_out, slot):
         """run_input with the backward pipelined (PN1Engine): the loss is ready on the current
         stream after the forward; the gradient is complete for every later entry point."""
-        if getattr(self, "workspace2", None) is None:
-            self.workspace2 = torch.empty_like(self.workspace)
-        ws = self.workspace if slot % 2 == 0 else self.workspace2
+        ws = self._slot_workspace(slot)
         self.last_workspace = ws
-        x = x.contiguous()
-        y = y.to(torch.int64).contiguous()
+        x, y = _batch(x, y)
         check(lib().flsim_pn1_fwd_bwd_input_async(
             ptr(self.gradstate), ptr(ws), self.max_samples, ptr(theta), ptr(x), ptr(y),
             int(x.shape[0]), ptr(workers_dev), ctypes.c_uint64(seed), int(bool(dropout)),
@@ -232,8 +232,7 @@ class NetEngine:
         the current stream.  backward_rows() later runs the backward of all rows at once."""
         ws = self._slot_workspace(slot)
         self.last_workspace = ws
-        x = x.contiguous()
-        y = y.to(torch.int64).contiguous()
+        x, y = _batch(x, y)
         check(lib().flsim_pn1_fwd_rows(
             ptr(self.gradstate), ptr(ws), self.max_samples, int(row0), ptr(theta), ptr(x), ptr(y),
             int(x.shape[0]), ptr(workers_dev), ctypes.c_uint64(seed), int(bool(dropout)),
@@ -244,8 +243,7 @@ class NetEngine:
         [row0, row0 + ceil(n/128)*128) of workspace `slot`; nothing is computed yet."""
         ws = self._slot_workspace(slot)
         self.last_workspace = ws
-        x = x.contiguous()
-        y = y.to(torch.int64).contiguous()
+        x, y = _batch(x, y)
         check(self._fn("load_rows")(ptr(self.gradstate), ptr(ws), self.max_samples, int(row0),
                                     ptr(x), ptr(y), int(x.shape[0]), stream_ptr()))
 
@@ -280,8 +278,7 @@ class NetEngine:
 
     def run_input(self, theta, x, y, workers_dev, seed, dropout, loss_out, backward=True,
                   stats_out=None):
-        x = x.contiguous()
-        y = y.to(torch.int64).contiguous()
+        x, y = _batch(x, y)
         self.last_workspace = self.workspace
         check(self._fn("fwd_bwd_input")(
             ptr(self.gradstate), ptr(self.workspace), self.max_samples, ptr(theta), ptr(x), ptr(y),
