@@ -8,7 +8,8 @@ Same classes, signatures and aliasing semantics; the arithmetic runs in libflsim
                                views of ONE flat buffer (every worker of the epoch gets the same
                                tensors, as in the reference)
   Agg(rule)                    agents.py:43-45; use FL.agents.rule (== main.py:23-25's mean) to
-                               get the fused path: it returns a lazy mean that Central consumes
+                               get the fused path: it returns a lazy mean that Central consumes;
+                               FL.agents.weighted_rule is the staleness-weighted alternative
   Central.update_model(ups)    agents.py:9-21 -> flsim_aggregate_optim_rule_push (cascade mean over
                                the entries in any order + the optimizer's step: torch.optim.Adam,
                                AdamW or SGD with the hyper-parameters of its param_groups[0]);
@@ -416,9 +417,11 @@ def _context(model):
 class _LazyMean(list):
     """What FL.agents.rule returns: the weight_ups list, reduced inside Central.update_model."""
 
-    def __init__(self, ups_list):
+    def __init__(self, ups_list, weights=None, normalize="weights"):
         super().__init__()
         self.ups_list = ups_list
+        self.weights = weights          # one Python float per entry, or None: the plain mean
+        self.normalize = normalize
 
 
 def rule(ups_list):
@@ -427,6 +430,25 @@ def rule(ups_list):
     if len(ups_list) == 0:
         raise IndexError("list index out of range")        # main.py:25 ups_list[0]
     return _LazyMean(ups_list)
+
+
+def weighted_rule(ups_list, weights, normalize="weights"):
+    """The staleness-weighted alternative to rule(), for Agg(rule) with the extra arguments bound:
+
+        W = float(sum(weights)) if normalize == "weights" else float(len(ups_list))
+        [torch.stack([x[i] * w for x, w in zip(ups_list, weights)]).sum(0) / W for i in ...]
+
+    evaluated lazily and fused with the optimizer step in Central.update_model, bit-exact with
+    that text on torch CPU.  weights: one Python float per entry, finite and >= 0; an entry that is
+    this epoch's gradient (a fast worker's aliased .grad) must weigh 1.0."""
+    if len(ups_list) == 0:
+        raise IndexError("list index out of range")
+    weights = [float(w) for w in weights]
+    if len(weights) != len(ups_list):
+        raise ValueError(f"{len(weights)} weights for {len(ups_list)} entries")
+    if normalize not in ("weights", "count"):
+        raise ValueError(f"normalize {normalize!r} (supported: 'weights', 'count')")
+    return _LazyMean(ups_list, weights, normalize)
 
 
 class Central:
@@ -482,20 +504,37 @@ class Central:
         entries = [u[0] for u in ups.ups_list]
         S = ctx.G if ctx.G is not None else torch.zeros(padded(ctx.P), device=ctx.device)
         sbase = S.untyped_storage().data_ptr()
-        arrays, bases, events = [], [], []
+        wts = ups.weights
+        arrays, bases, events, aw = [], [], [], []
         for pos, e in enumerate(entries):
             b = e.untyped_storage().data_ptr()
             if b == sbase:
+                if wts is not None and wts[pos] != 1.0:
+                    raise NotImplementedError(f"entry {pos} is this epoch's gradient: its weight "
+                                              f"must be 1.0 (is {wts[pos]})")
                 continue
             if b not in bases:
                 bases.append(b)
                 arrays.append(_flat_of(e, ctx))
-            events.append((pos, bases.index(b)))
+                aw.append(None if wts is None else wts[pos])
+            j = bases.index(b)
+            if wts is not None and wts[pos] != aw[j]:
+                raise NotImplementedError(f"entries of one gradient buffer with different weights "
+                                          f"({aw[j]} and {wts[pos]})")
+            events.append((pos, j))
         k = len(entries)
         c = k - len(events)
+        kw = {}
+        if wts is not None and not all(w == 1.0 for w in wts):   # else: the plain mean
+            W = float(sum(wts)) if ups.normalize == "weights" else float(k)
+            kw = dict(divisor=W)
         if len(events) <= 8 and all(p >= c for p, _ in events):    # reference order
-            return S, Rule(k, [arrays[j] for _, j in events], c=c)
-        return S, Rule(k, arrays, events=events, stager=ctx.stager)
+            if kw:
+                kw["weights"] = [aw[j] for _, j in events]
+            return S, Rule(k, [arrays[j] for _, j in events], c=c, **kw)
+        if kw:
+            kw["weights"] = aw
+        return S, Rule(k, arrays, events=events, stager=ctx.stager, **kw)
 
     def update_model(self, ups):
         """agents.py:9-21: install the aggregated gradient, Adam step, clear .grad."""
@@ -517,7 +556,8 @@ class Central:
         else:
             hp = dict(optim=o)
         if isinstance(ups, _LazyMean) and ctx.G is not None and ctx.carry is None and \
-                not ctx.touched and hasattr(eng, "server_step"):
+                not ctx.touched and hasattr(eng, "server_step") and \
+                not (r.c_weights is not None and len(r.arrays) > 16):
             # fused: this epoch's slabs -> S_t (also written into G, which the FIFO entries of
             # main.py:156,161 alias) -> rule() + Adam, one pass
             ctx.flush_backward()

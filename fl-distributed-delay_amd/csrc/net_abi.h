@@ -238,11 +238,13 @@ static int net_end_epoch(void* gradstate, float* grad_out, hipStream_t stream) {
 
 // the same reduction fused with rule() + the update rule of `optim` (include/flsim.h: SGD, Adam
 // with weight decay, AdamW), world = 1
+// wts (nullable): the staleness-weighted rule (include/flsim.h)
 template <class N>
-static int net_server_step_optim(void* gradstate, float* S_out, const flsim_rule* rule, float* p,
-                                 float* m, float* v, long step, const flsim_optim* optim,
-                                 hipStream_t stream) {
+static int net_server_step_wrule(void* gradstate, float* S_out, const flsim_rule* rule,
+                                 const flsim_rule_weights* wts, float* p, float* m, float* v,
+                                 long step, const flsim_optim* optim, hipStream_t stream) {
     RC(check_optim(optim));
+    RC(check_weights(wts));
     const int nstate = optim_n_state(optim);
     FLSIM_REQUIRE(gradstate && rule && p && (m || nstate < 1) && (v || nstate < 2),
                   "null pointer");
@@ -251,9 +253,18 @@ static int net_server_step_optim(void* gradstate, float* S_out, const flsim_rule
     RuleProg R;
     RC(make_rule(rule, &R));
     OptLaunch ol;
-    RC(make_opt_launch(optim, rule->k, step, &ol));
+    RC(make_opt_launch(optim, wts ? wts->divisor : (double)rule->k, step, &ol));
+    float w[STEP_MAX_WARR];
+    if (wts) RC(make_weights(rule, wts, S_out, nullptr, w, STEP_MAX_WARR));
     return slab_step_launch_optim((float*)gradstate, N::plan(g, gradstate), g.cnt_off, g.part_off,
-                                  S_out, &R, ol, p, m, v, N::params(), stream);
+                                  S_out, &R, ol, p, m, v, N::params(), stream, wts ? w : nullptr);
+}
+
+template <class N>
+static int net_server_step_optim(void* gradstate, float* S_out, const flsim_rule* rule, float* p,
+                                 float* m, float* v, long step, const flsim_optim* optim,
+                                 hipStream_t stream) {
+    return net_server_step_wrule<N>(gradstate, S_out, rule, nullptr, p, m, v, step, optim, stream);
 }
 
 // ... with Adam(lr, betas, eps)

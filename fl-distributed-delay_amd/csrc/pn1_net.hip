@@ -1107,4 +1107,10 @@ int flsim_pn1_server_step_optim(void* gradstate, float* S_out, const flsim_rule*
     return net_server_step_optim<PN1>(gradstate, S_out, rule, p, m, v, step, optim, stream);
 }
 
+int flsim_pn1_server_step_wrule(void* gradstate, float* S_out, const flsim_rule* rule,
+                                const flsim_rule_weights* wts, float* p, float* m, float* v,
+                                long step, const flsim_optim* optim, hipStream_t stream) {
+    return net_server_step_wrule<PN1>(gradstate, S_out, rule, wts, p, m, v, step, optim, stream);
+}
+
 }  // extern "C"

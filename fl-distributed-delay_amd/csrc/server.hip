@@ -13,6 +13,10 @@
 // Central(model, optim) takes other optimizers too: the kernels are instantiated per update rule
 // (OptKind, slabstep.h: Adam, Adam with weight decay / AdamW, SGD with and without momentum; see
 // opt_elem), each streaming only the state arrays its rule owns.
+// Agg(rule) takes other rules too: every rule-carrying kernel also has a weighted form (W), the
+// staleness-weighted rule sum_j w_j * entry_j / W with w = 1 for the S_t entries (a stale value is
+// multiplied by its array's fp32 weight where it is loaded, the same cascade sums the products,
+// one IEEE division follows); bit-exact with torch.stack([x * w ...]).sum(0) / W.
 //
 // Two kernels:
 //   k_agg_stream  S_t already in a buffer (after the all-reduce at world > 1, or the facade):
@@ -83,9 +87,19 @@ __device__ __forceinline__ void adam_update(const AdamConst& A, float g, float& 
     v = vi;
 }
 
+// rule()'s division.  Unweighted: the divisor is the entry count k, an integer, where div_const is
+// correctly rounded.  Weighted (W): the divisor is any positive fp32 (a sum of discounts), where
+// a * RN(1/b) can be 2 ulp off and one correction is then not enough: the IEEE division.
+template <bool W>
+__device__ __forceinline__ float rule_div(const AdamConst& A, float s) {
+    if constexpr (W) return __fdiv_rn(s, A.fk);
+    else return div_const(s, A.fk, A.rk);
+}
+
+template <bool W = false>
 __device__ __forceinline__ void adam_elem(const AdamConst& A, float s, float& p, float& m,
                                           float& v) {
-    const float g = div_const(s, A.fk, A.rk);               // rule(): mean = sum / k
+    const float g = rule_div<W>(A, s);                      // rule(): mean = sum / k
     adam_update(A, g, p, m, v);
 }
 
@@ -98,13 +112,13 @@ __device__ __forceinline__ void adam_elem(const AdamConst& A, float s, float& p,
 //                         p = fma(g, -lr, p)
 // The flags are launch-uniform (scalar branches).  m is SGD's momentum buffer; a kind never
 // touches an argument it does not own (the callers pass dummies).
-template <int OK>
+template <int OK, bool W = false>
 __device__ __forceinline__ void opt_elem(const AdamConst& A, const OptConst& X, float s, float& p,
                                          float& m, float& v) {
     if constexpr (OK == OK_ADAM) {
-        adam_elem(A, s, p, m, v);
+        adam_elem<W>(A, s, p, m, v);
     } else {
-        float g = div_const(s, A.fk, A.rk);                 // rule(): mean = sum / k
+        float g = rule_div<W>(A, s);                        // rule(): mean = sum / k
         if constexpr (OK == OK_ADAMD) {
             if (X.flags & OF_DECOUPLED) p = p * X.wd;
             else g = __fmaf_rn(p, X.wd, g);
@@ -119,6 +133,17 @@ __device__ __forceinline__ void opt_elem(const AdamConst& A, const OptConst& X, 
             p = __fmaf_rn(g, X.neg_lr, p);
         }
     }
+}
+
+// The leading elements of a tensor of `numel` elements that rule()'s sum takes as multi_row_sum
+// columns (the main program); the rest are row_sum columns (the tail program).  ATen sums 32
+// columns at a time with multi_row_sum and what is left with row_sum.  A tensor of fewer than 8
+// elements takes ATen's scalar path instead, which still sums 4 columns at a time with
+// multi_row_sum: the weighted kernels follow it (they are pinned to torch itself); the
+// unweighted ones keep the 32-column rule for every tensor, as the oracle states it (no
+// supported model has a tensor of 4 .. 7 elements, where the two differ).
+__host__ __device__ inline long rule_body(int numel, bool weighted) {
+    return (weighted && numel < 8) ? (long)(numel / 4 * 4) : (long)(numel / 32) * 32;
 }
 
 // Program access.  The interpreter reads one macro word (two dwords) per step at a uniform address,
@@ -173,7 +198,8 @@ struct AggArgs {
     long edge_lo[MAX_EDGE];
     AdamConst ac;
     RuleProg R;
-    OptConst oc;                    // last: the OK_ADAM kernels' argument offsets stay as they were
+    OptConst oc;                    // after R: the OK_ADAM kernels' argument offsets stay as they were
+    float w[RULE_MAX_ARR];          // weighted rule (W kernels only): the weight of R.arr[q]
 };
 static_assert(sizeof(AggArgs) <= 4096, "kernel argument block");
 
@@ -199,7 +225,12 @@ __device__ __forceinline__ bool block_touch(const AggArgs& A, long blo, long spa
 // per thread; a streaming block that is also an edge block returns at once.  Every load of a
 // thread (S_t, the staged entry arrays, p, m, v) is issued before the arithmetic; loads and
 // stores are non-temporal (each byte is touched once).
-template <bool INL, int OK = OK_ADAM>
+//
+// W: the staleness-weighted rule, sum_j w_j * entry_j / divisor.  A stale value is multiplied by
+// its array's weight once, where it is loaded (before the staging, and in the on-demand path); the
+// program then runs on the products as it runs on the values.  The multiply is a plain fp32
+// multiply (no contraction), a null array stays 0.
+template <bool INL, int OK = OK_ADAM, bool W = false>
 __global__ void __launch_bounds__(256) k_agg_stream(AggArgs A) {
     constexpr bool HAS_M = opt_n_state(OK) >= 1, HAS_V = opt_n_state(OK) == 2;
     __shared__ f32x4 ys_lds[NYR * 256];
@@ -212,13 +243,17 @@ __global__ void __launch_bounds__(256) k_agg_stream(AggArgs A) {
         float p = A.p[e], m = 0.f, v = 0.f;
         if constexpr (HAS_M) m = A.m[e];
         if constexpr (HAS_V) v = A.v[e];
-        auto yf = [&](int q) -> float { return A.R.arr[q] ? A.R.arr[q][e] : 0.f; };
+        auto yf = [&](int q) -> float {
+            if (!A.R.arr[q]) return 0.f;
+            if constexpr (W) return A.R.arr[q][e] * A.w[q];
+            else return A.R.arr[q][e];
+        };
         const CascVals<float> cv = casc_values(x, A.R.info.need, A.R.info.lp);
         const bool tail = in_tail(A, e);
         float s = 0.f;
         if (!tail) s = casc_run_macro(prog, 0, cv, yf);
         if (tail) s = casc_run_macro(prog, A.R.info.tail_off, cv, yf);
-        opt_elem<OK>(A.ac, A.oc, s, p, m, v);
+        opt_elem<OK, W>(A.ac, A.oc, s, p, m, v);
         A.p[e] = p;
         if constexpr (HAS_M) A.m[e] = m;
         if constexpr (HAS_V) A.v[e] = v;
@@ -238,6 +273,11 @@ __global__ void __launch_bounds__(256) k_agg_stream(AggArgs A) {
 #pragma unroll
     for (int q = 0; q < NYR; ++q)
         ys[q] = (q < nst && A.R.arr[q]) ? ld(A.R.arr[q] + e0) : f32x4{0.f, 0.f, 0.f, 0.f};
+    if constexpr (W) {
+#pragma unroll
+        for (int q = 0; q < NYR; ++q)
+            if (q < nst) ys[q] = ys[q] * A.w[q];
+    }
     const f32x4 x = ld(A.S + e0);
     f32x4 p = ld(A.p + e0), m = {0.f, 0.f, 0.f, 0.f}, v = m;
     if constexpr (HAS_M) m = ld(A.m + e0);
@@ -247,14 +287,16 @@ __global__ void __launch_bounds__(256) k_agg_stream(AggArgs A) {
         if (q < nst) ys_lds[q * 256 + tid] = ys[q];
     auto yf = [&](int q) -> f32x4 {
         if (q < NYR) return ys_lds[q * 256 + tid];
-        return A.R.arr[q] ? ld(A.R.arr[q] + e0) : f32x4{0.f, 0.f, 0.f, 0.f};
+        if (!A.R.arr[q]) return f32x4{0.f, 0.f, 0.f, 0.f};
+        if constexpr (W) return ld(A.R.arr[q] + e0) * A.w[q];
+        else return ld(A.R.arr[q] + e0);
     };
     const f32x4 sum = casc_run_macro<true>(
         prog, 0, casc_values(x, A.R.info.need, A.R.info.lp), yf);
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
         float pp = p[u], mm = m[u], vv = v[u];
-        opt_elem<OK>(A.ac, A.oc, sum[u], pp, mm, vv);
+        opt_elem<OK, W>(A.ac, A.oc, sum[u], pp, mm, vv);
         p[u] = pp;
         m[u] = mm;
         v[u] = vv;
@@ -279,7 +321,7 @@ struct AggVec<1> { typedef float T __attribute__((ext_vector_type(4))); };
 template <>
 struct AggVec<2> { typedef float T __attribute__((ext_vector_type(8))); };
 
-template <int G, int NY, int OK = OK_ADAM>
+template <int G, int NY, int OK = OK_ADAM, bool W = false>
 __global__ void __launch_bounds__(256) k_agg_stream_reg(AggArgs A) {
     constexpr bool HAS_M = opt_n_state(OK) >= 1, HAS_V = opt_n_state(OK) == 2;
     typedef typename AggVec<G>::T T;
@@ -292,13 +334,17 @@ __global__ void __launch_bounds__(256) k_agg_stream_reg(AggArgs A) {
         float p = A.p[e], m = 0.f, v = 0.f;
         if constexpr (HAS_M) m = A.m[e];
         if constexpr (HAS_V) v = A.v[e];
-        auto yf = [&](int q) -> float { return A.R.arr[q] ? A.R.arr[q][e] : 0.f; };
+        auto yf = [&](int q) -> float {
+            if (!A.R.arr[q]) return 0.f;
+            if constexpr (W) return A.R.arr[q][e] * A.w[q];
+            else return A.R.arr[q][e];
+        };
         const CascVals<float> cv = casc_values(x, A.R.info.need, A.R.info.lp);
         const bool tail = in_tail(A, e);
         float s = 0.f;
         if (!tail) s = casc_run_macro(prog, 0, cv, yf);
         if (tail) s = casc_run_macro(prog, A.R.info.tail_off, cv, yf);
-        opt_elem<OK>(A.ac, A.oc, s, p, m, v);
+        opt_elem<OK, W>(A.ac, A.oc, s, p, m, v);
         A.p[e] = p;
         if constexpr (HAS_M) A.m[e] = m;
         if constexpr (HAS_V) A.v[e] = v;
@@ -322,6 +368,12 @@ __global__ void __launch_bounds__(256) k_agg_stream_reg(AggArgs A) {
 #pragma unroll
         for (int j = 0; j < G; ++j)
             ys[q][j] = A.R.arr[q] ? ld(A.R.arr[q] + e[j]) : f32x4{0.f, 0.f, 0.f, 0.f};
+    if constexpr (W) {
+#pragma unroll
+        for (int q = 0; q < NY; ++q)
+#pragma unroll
+            for (int j = 0; j < G; ++j) ys[q][j] = ys[q][j] * A.w[q];
+    }
 #pragma unroll
     for (int j = 0; j < G; ++j) {
         xs[j] = ld(A.S + e[j]);
@@ -354,7 +406,7 @@ __global__ void __launch_bounds__(256) k_agg_stream_reg(AggArgs A) {
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             float pp = ps[j][u], mm = ms[j][u], vv = vs[j][u];
-            opt_elem<OK>(A.ac, A.oc, sum[4 * j + u], pp, mm, vv);
+            opt_elem<OK, W>(A.ac, A.oc, sum[4 * j + u], pp, mm, vv);
             ps[j][u] = pp;
             ms[j][u] = mm;
             vs[j][u] = vv;
@@ -382,7 +434,8 @@ struct StepArgs {
     AdamConst ac;
     RuleProg R;
     SlabSeg seg[STEP_MAX_SEG];
-    OptConst oc;                    // last: the OK_ADAM kernels' argument offsets stay as they were
+    OptConst oc;                    // after seg: the OK_ADAM kernels' argument offsets stay as they were
+    float w[STEP_MAX_WARR];         // weighted rule (W kernels only): the weight of R.arr[q]
 };
 static_assert(sizeof(StepArgs) <= 4096, "kernel argument block");
 
@@ -485,7 +538,7 @@ __device__ __forceinline__ bool col_to_param(const SlabSeg& g, long col, long& t
 // Identity-layout segments (the linear layers): tiles of 1024 elements, thread t owns the float4
 // column 4t; it sums its Z slab rows itself (small Z, four accumulators) and finishes with 16-B
 // parameter-side loads and stores; the parameter loads are issued before the slab reads.
-template <bool ADAM, bool INL, int OK>
+template <bool ADAM, bool INL, int OK, bool W>
 __device__ __forceinline__ void slab_step_wide(const StepArgs& A, const SlabSeg& g, int u, int ul,
                                                float* lds) {
     constexpr bool HAS_M = opt_n_state(OK) >= 1, HAS_V = opt_n_state(OK) == 2;
@@ -520,6 +573,11 @@ __device__ __forceinline__ void slab_step_wide(const StepArgs& A, const SlabSeg&
 #pragma unroll
             for (int q = 0; q < NYW; ++q)
                 ys[q] = (q < A.R.narr && A.R.arr[q]) ? ld(A.R.arr[q] + e) : f32x4{0.f, 0.f, 0.f, 0.f};
+            if constexpr (W) {
+#pragma unroll
+                for (int q = 0; q < NYW; ++q)
+                    if (q < A.R.narr) ys[q] = ys[q] * A.w[q];
+            }
             p = ld(A.p + e);
             if constexpr (HAS_M) m = ld(A.m + e);
             else m = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -610,7 +668,9 @@ __device__ __forceinline__ void slab_step_wide(const StepArgs& A, const SlabSeg&
                     case 6: return ys[6];
                     case 7: return ys[7];
                     default:
-                        return A.R.arr[q] ? ld(A.R.arr[q] + e) : f32x4{0.f, 0.f, 0.f, 0.f};
+                        if (!A.R.arr[q]) return f32x4{0.f, 0.f, 0.f, 0.f};
+                        if constexpr (W) return ld(A.R.arr[q] + e) * A.w[q];
+                        else return ld(A.R.arr[q] + e);
                 }
             };
             const f32x4 sum = casc_run_macro<true>(
@@ -618,7 +678,7 @@ __device__ __forceinline__ void slab_step_wide(const StepArgs& A, const SlabSeg&
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 float pp = p[k], mm = m[k], vv = v[k];
-                opt_elem<OK>(A.ac, A.oc, sum[k], pp, mm, vv);
+                opt_elem<OK, W>(A.ac, A.oc, sum[k], pp, mm, vv);
                 p[k] = pp;
                 m[k] = mm;
                 v[k] = vv;
@@ -635,7 +695,7 @@ __device__ __forceinline__ void slab_step_wide(const StepArgs& A, const SlabSeg&
 // loads, whose cost does not depend on which XCD the last arriver sits on.  Each thread's
 // parameter-side loads (p, m, v, staged entry arrays) are issued before the slab reduction (whole
 // tiles) or together with the partial loads (split tiles), so the two memory round trips overlap.
-template <bool ADAM, bool INL, int OK>
+template <bool ADAM, bool INL, int OK, bool W>
 __device__ __forceinline__ void slab_step_body(const StepArgs& A, float* lds) {
     constexpr bool HAS_M = opt_n_state(OK) >= 1, HAS_V = opt_n_state(OK) == 2;
     const int tid = threadIdx.x;
@@ -661,7 +721,7 @@ __device__ __forceinline__ void slab_step_body(const StepArgs& A, float* lds) {
     const SlabSeg& g = A.seg[si];
     const int ul = u - g.unit0;
     if (g.wide) {
-        slab_step_wide<ADAM, INL, OK>(A, g, u, ul, lds);
+        slab_step_wide<ADAM, INL, OK, W>(A, g, u, ul, lds);
         return;
     }
     int tile, t_end, j;
@@ -689,6 +749,11 @@ __device__ __forceinline__ void slab_step_body(const StepArgs& A, float* lds) {
 #pragma unroll
             for (int q = 0; q < NYR; ++q)
                 ys[q] = (q < nst && A.R.arr[q]) ? A.R.arr[q][e] : 0.f;
+            if constexpr (W) {
+#pragma unroll
+                for (int q = 0; q < NYR; ++q)
+                    if (q < nst) ys[q] = ys[q] * A.w[q];
+            }
             p = A.p[e];
             if constexpr (HAS_M) m = A.m[e];
             if constexpr (HAS_V) v = A.v[e];
@@ -742,7 +807,7 @@ __device__ __forceinline__ void slab_step_body(const StepArgs& A, float* lds) {
             // Tiles holding row_sum tail elements, or more arrays than NYR, take the per-element
             // path below.
             if (valid && A.S_out) A.S_out[e] = s;
-            const bool tail = valid && tl >= (long)(g.numel / 32) * 32;
+            const bool tail = valid && tl >= rule_body(g.numel, W);
             lds[L_S + tid] = valid ? s : 0.f;
             lds[L_P + tid] = p;
             if constexpr (HAS_M) lds[L_M + tid] = m;
@@ -769,7 +834,7 @@ __device__ __forceinline__ void slab_step_body(const StepArgs& A, float* lds) {
                         long tk;
                         if (!col_to_param(g, (long)tile * 256 + 4 * tid + k, tk)) continue;
                         float p1 = pp[k], m1 = mm[k], v1 = vv[k];
-                        opt_elem<OK>(A.ac, A.oc, sum[k], p1, m1, v1);
+                        opt_elem<OK, W>(A.ac, A.oc, sum[k], p1, m1, v1);
                         const long ek = g.toff + tk;
                         A.p[ek] = p1;
                         if constexpr (HAS_M) A.m[ek] = m1;
@@ -789,7 +854,7 @@ __device__ __forceinline__ void slab_step_body(const StepArgs& A, float* lds) {
 #pragma unroll
                     for (int k = 0; k < 4; ++k) {
                         float p1 = pp[k], m1 = mm[k], v1 = vv[k];
-                        opt_elem<OK>(A.ac, A.oc, sum[k], p1, m1, v1);
+                        opt_elem<OK, W>(A.ac, A.oc, sum[k], p1, m1, v1);
                         pp[k] = p1;
                         mm[k] = m1;
                         vv[k] = v1;
@@ -816,14 +881,16 @@ __device__ __forceinline__ void slab_step_body(const StepArgs& A, float* lds) {
                 if (q < nst) lds[L_Y + q * 256 + tid] = ys[q];
             auto yf = [&](int q) -> float {
                 if (q < NYR) return lds[L_Y + q * 256 + tid];
-                return A.R.arr[q] ? A.R.arr[q][e] : 0.f;
+                if (!A.R.arr[q]) return 0.f;
+                if constexpr (W) return A.R.arr[q][e] * A.w[q];
+                else return A.R.arr[q][e];
             };
             const CascVals<float> cv = casc_values(s, A.R.info.need, A.R.info.lp);
-            const bool tail = tl >= (long)(g.numel / 32) * 32;
+            const bool tail = tl >= rule_body(g.numel, W);
             float sum = 0.f;
             if (!tail) sum = casc_run_macro(prog, 0, cv, yf);
             if (tail) sum = casc_run_macro(prog, A.R.info.tail_off, cv, yf);
-            opt_elem<OK>(A.ac, A.oc, sum, p, m, v);
+            opt_elem<OK, W>(A.ac, A.oc, sum, p, m, v);
             A.p[e] = p;
             if constexpr (HAS_M) A.m[e] = m;
             if constexpr (HAS_V) A.v[e] = v;
@@ -831,10 +898,10 @@ __device__ __forceinline__ void slab_step_body(const StepArgs& A, float* lds) {
     }
 }
 
-template <bool ADAM, bool INL, int OK = OK_ADAM>
+template <bool ADAM, bool INL, int OK = OK_ADAM, bool W = false>
 __global__ void __launch_bounds__(256) k_slab_step(StepArgs A) {
     __shared__ float lds[L_Y + NYR * 256];
-    slab_step_body<ADAM, INL, OK>(A, lds);
+    slab_step_body<ADAM, INL, OK, W>(A, lds);
 }
 
 // General-order programs: the interpreter's chains of dependent adds want many resident waves to
@@ -842,25 +909,33 @@ __global__ void __launch_bounds__(256) k_slab_step(StepArgs A) {
 #ifndef SEQ_WAVES
 #define SEQ_WAVES 4
 #endif
-template <int OK = OK_ADAM>
+template <int OK = OK_ADAM, bool W = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SEQ_WAVES, 8)))
 k_slab_step_seq(StepArgs A) {
     __shared__ float lds[L_END];
-    slab_step_body<true, false, OK>(A, lds);
+    slab_step_body<true, false, OK, W>(A, lds);
 }
 
 // ================================================================================================
 // host
 // ================================================================================================
-int make_adam_const(int divisor, long step, double lr, double beta1, double beta2, double eps,
-                    AdamConst* ac) {
-    FLSIM_REQUIRE(divisor > 0 && divisor < (1 << 24), "divisor %d out of range", divisor);
-    FLSIM_REQUIRE(step >= 1, "step must be >= 1");
+// rule()'s divisor in launch form: the entry count k (an integer below 2^24, exact in fp32) or a
+// weighted rule's divisor, rounded to fp32 once
+static int make_divisor(double divisor, AdamConst* ac) {
+    FLSIM_REQUIRE(divisor > 0 && divisor < (double)(1 << 24), "divisor %g out of range", divisor);
     ac->fk = (float)divisor;                         // rule(): mean = sum / k
+    FLSIM_REQUIRE(ac->fk > 0.f, "ZeroDivisionError: divisor %g rounds to 0 in fp32", divisor);
     {
-        volatile float one = 1.f, fk = (float)divisor;   // RN(1/k) in fp32, not via double
+        volatile float one = 1.f, fk = ac->fk;       // RN(1/k) in fp32, not via double
         ac->rk = one / fk;
     }
+    return 0;
+}
+
+int make_adam_const(double divisor, long step, double lr, double beta1, double beta2, double eps,
+                    AdamConst* ac) {
+    RC(make_divisor(divisor, ac));
+    FLSIM_REQUIRE(step >= 1, "step must be >= 1");
     const double bc1 = 1.0 - pow(beta1, (double)step);
     const double bc2 = 1.0 - pow(beta2, (double)step);
     ac->w1 = (float)(1.0 - beta1);
@@ -890,18 +965,47 @@ int check_optim(const flsim_optim* o) {
     return 0;
 }
 
-int make_opt_launch(const flsim_optim* o, int divisor, long step, OptLaunch* ol) {
+// A weighted rule's weights and divisor (the cases where the rule text would divide by zero or
+// average with a negative or non-finite weight); before any pointer check, like check_optim.
+// Negated comparisons: a NaN is refused too.
+int check_weights(const flsim_rule_weights* w) {
+    if (!w) return 0;
+    FLSIM_REQUIRE(w->n >= 0 && w->n <= RULE_MAX_ARR, "weights for %d arrays (max %d)", w->n,
+                  RULE_MAX_ARR);
+    for (int q = 0; q < w->n; ++q)
+        FLSIM_REQUIRE(w->w[q] >= 0.0 && w->w[q] <= 3.0e38, "Invalid weight %g of array %d",
+                      w->w[q], q);
+    FLSIM_REQUIRE(w->divisor == w->divisor && w->divisor <= 3.0e38, "Invalid divisor %g",
+                  w->divisor);
+    FLSIM_REQUIRE(w->divisor > 0.0, "ZeroDivisionError: weighted rule divisor %g", w->divisor);
+    return 0;
+}
+
+// the weights in launch form (fp32, rounded once) for a rule whose arrays they belong to; an
+// array that is S_t itself (`alias`: the buffer S_t is read from or written to) must weigh 1.0:
+// the cascade program's blocks of pure S_t entries stand for x added as it is
+int make_weights(const flsim_rule* r, const flsim_rule_weights* w, const float* alias0,
+                 const float* alias1, float* out, int cap) {
+    FLSIM_REQUIRE(w->n == r->n_arrays, "weights for %d arrays, the rule has %d", w->n,
+                  r->n_arrays);
+    FLSIM_REQUIRE(w->n <= cap, "NotImplementedError: weighted rule with %d arrays in this step "
+                  "(max %d)", w->n, cap);
+    for (int q = 0; q < w->n; ++q) {
+        const bool alias = r->arrays[q] && (r->arrays[q] == alias0 || r->arrays[q] == alias1);
+        FLSIM_REQUIRE(!alias || w->w[q] == 1.0, "NotImplementedError: array %d is S_t itself, its "
+                      "weight must be 1.0 (is %g)", q, w->w[q]);
+        out[q] = (float)w->w[q];
+    }
+    return 0;
+}
+
+int make_opt_launch(const flsim_optim* o, double divisor, long step, OptLaunch* ol) {
     RC(check_optim(o));
     memset(ol, 0, sizeof(*ol));
     if (o->kind == FLSIM_OPT_SGD) {
-        FLSIM_REQUIRE(divisor > 0 && divisor < (1 << 24), "divisor %d out of range", divisor);
+        RC(make_divisor(divisor, &ol->ac));
         FLSIM_REQUIRE(step >= 1, "step must be >= 1");
         ol->ok = o->momentum != 0.0 ? OK_SGDM : OK_SGD;
-        ol->ac.fk = (float)divisor;                      // rule(): mean = sum / k
-        {
-            volatile float one = 1.f, fk = (float)divisor;   // RN(1/k) in fp32, not via double
-            ol->ac.rk = one / fk;
-        }
         ol->oc.wd = (float)o->weight_decay;
         ol->oc.mu = (float)o->momentum;
         ol->oc.omd = (float)(1.0 - o->dampening);
@@ -978,20 +1082,31 @@ int slab_step_launch(float* gradstate, const StepPlan& plan, long cnt_off, long 
 }
 
 // the fused step's two rule() + update launches of one kind
-template <int OK>
+template <int OK, bool W>
 static void launch_slab_rule(bool seq, unsigned nblk, hipStream_t stream, const ProbeSlot& ps,
                              const StepArgs& A) {
     if (!seq)
-        hipExtLaunchKernelGGL((k_slab_step<true, true, OK>), dim3(nblk), dim3(256), 0, stream,
+        hipExtLaunchKernelGGL((k_slab_step<true, true, OK, W>), dim3(nblk), dim3(256), 0, stream,
                               ps.start, ps.stop, 0, A);
     else
-        hipExtLaunchKernelGGL((k_slab_step_seq<OK>), dim3(nblk), dim3(256), 0, stream, ps.start,
+        hipExtLaunchKernelGGL((k_slab_step_seq<OK, W>), dim3(nblk), dim3(256), 0, stream, ps.start,
                               ps.stop, 0, A);
+}
+
+template <bool W>
+static void launch_slab_kind(int ok, bool seq, unsigned nblk, hipStream_t stream,
+                             const ProbeSlot& ps, const StepArgs& A) {
+    switch (ok) {
+        case OK_ADAM: launch_slab_rule<OK_ADAM, W>(seq, nblk, stream, ps, A); break;
+        case OK_ADAMD: launch_slab_rule<OK_ADAMD, W>(seq, nblk, stream, ps, A); break;
+        case OK_SGDM: launch_slab_rule<OK_SGDM, W>(seq, nblk, stream, ps, A); break;
+        default: launch_slab_rule<OK_SGD, W>(seq, nblk, stream, ps, A); break;
+    }
 }
 
 int slab_step_launch_optim(float* gradstate, const StepPlan& plan, long cnt_off, long part_off,
                            float* S_out, const RuleProg* rule, const OptLaunch& ol, float* p,
-                           float* m, float* v, long P, hipStream_t stream) {
+                           float* m, float* v, long P, hipStream_t stream, const float* weights) {
     const int nstate = opt_n_state(ol.ok);
     StepArgs A{};
     A.base = gradstate;
@@ -1009,6 +1124,10 @@ int slab_step_launch_optim(float* gradstate, const StepPlan& plan, long cnt_off,
         A.R = *rule;
         A.ac = ol.ac;
         A.oc = ol.oc;
+        if (weights) {
+            FLSIM_REQUIRE(rule->narr <= STEP_MAX_WARR, "weighted rule with %d arrays", rule->narr);
+            for (int q = 0; q < rule->narr; ++q) A.w[q] = weights[q];
+        }
     }
     // FLSIM_STEP_UNITS="lo,hi" (measurement only): run units [lo, hi) of the plan -- whole
     // segments, so every split tile completes and resets its counter
@@ -1045,12 +1164,8 @@ int slab_step_launch_optim(float* gradstate, const StepPlan& plan, long cnt_off,
     } else {
         const bool seq = rule->prog != nullptr;
         if (seq) RC(stage_program(*rule, stream));
-        switch (ol.ok) {
-            case OK_ADAM: launch_slab_rule<OK_ADAM>(seq, nblk, stream, ps, A); break;
-            case OK_ADAMD: launch_slab_rule<OK_ADAMD>(seq, nblk, stream, ps, A); break;
-            case OK_SGDM: launch_slab_rule<OK_SGDM>(seq, nblk, stream, ps, A); break;
-            default: launch_slab_rule<OK_SGD>(seq, nblk, stream, ps, A); break;
-        }
+        if (weights) launch_slab_kind<true>(ol.ok, seq, nblk, stream, ps, A);
+        else launch_slab_kind<false>(ol.ok, seq, nblk, stream, ps, A);
     }
     FLSIM_LAUNCH_CHECK();
     const int kid = !rule ? K_SLABSUM : (rule->prog == nullptr ? K_STEP : K_STEP_SEQ);
@@ -1059,23 +1174,34 @@ int slab_step_launch_optim(float* gradstate, const StepPlan& plan, long cnt_off,
 
 // the streaming launch of one kind: the register-array form (reference order, <= 2 entry arrays,
 // G groups per thread) or the LDS-staged one (inline or staged program)
-template <int OK>
+template <int OK, bool W>
 static void launch_agg(bool reg, int G, dim3 grid, hipStream_t stream, const ProbeSlot& ps,
                        const AggArgs& A) {
     if (reg) {
-        auto k = G == 2 ? (A.R.narr == 0 ? k_agg_stream_reg<2, 0, OK>
-                           : A.R.narr == 1 ? k_agg_stream_reg<2, 1, OK>
-                                           : k_agg_stream_reg<2, 2, OK>)
-                        : (A.R.narr == 0 ? k_agg_stream_reg<1, 0, OK>
-                           : A.R.narr == 1 ? k_agg_stream_reg<1, 1, OK>
-                                           : k_agg_stream_reg<1, 2, OK>);
+        auto k = G == 2 ? (A.R.narr == 0 ? k_agg_stream_reg<2, 0, OK, W>
+                           : A.R.narr == 1 ? k_agg_stream_reg<2, 1, OK, W>
+                                           : k_agg_stream_reg<2, 2, OK, W>)
+                        : (A.R.narr == 0 ? k_agg_stream_reg<1, 0, OK, W>
+                           : A.R.narr == 1 ? k_agg_stream_reg<1, 1, OK, W>
+                                           : k_agg_stream_reg<1, 2, OK, W>);
         hipExtLaunchKernelGGL(k, grid, dim3(256), 0, stream, ps.start, ps.stop, 0, A);
     } else if (A.R.prog == nullptr)
-        hipExtLaunchKernelGGL((k_agg_stream<true, OK>), grid, dim3(256), 0, stream, ps.start,
+        hipExtLaunchKernelGGL((k_agg_stream<true, OK, W>), grid, dim3(256), 0, stream, ps.start,
                               ps.stop, 0, A);
     else
-        hipExtLaunchKernelGGL((k_agg_stream<false, OK>), grid, dim3(256), 0, stream, ps.start,
+        hipExtLaunchKernelGGL((k_agg_stream<false, OK, W>), grid, dim3(256), 0, stream, ps.start,
                               ps.stop, 0, A);
+}
+
+template <bool W>
+static void launch_agg_kind(int ok, bool reg, int G, dim3 grid, hipStream_t stream,
+                            const ProbeSlot& ps, const AggArgs& A) {
+    switch (ok) {
+        case OK_ADAM: launch_agg<OK_ADAM, W>(reg, G, grid, stream, ps, A); break;
+        case OK_ADAMD: launch_agg<OK_ADAMD, W>(reg, G, grid, stream, ps, A); break;
+        case OK_SGDM: launch_agg<OK_SGDM, W>(reg, G, grid, stream, ps, A); break;
+        default: launch_agg<OK_SGD, W>(reg, G, grid, stream, ps, A); break;
+    }
 }
 
 }  // namespace flsim
@@ -1111,7 +1237,18 @@ int flsim_aggregate_optim_rule_push(const float* S, float* S_out, const flsim_ru
                                     float* m, float* v, long P, const long* tensor_sizes,
                                     int n_tensors, long step, const flsim_optim* optim,
                                     hipStream_t stream) {
+    return flsim_aggregate_optim_wrule_push(S, S_out, rule, nullptr, p, m, v, P, tensor_sizes,
+                                            n_tensors, step, optim, stream);
+}
+
+// the same with a staleness-weighted rule: sum_j w_j * entry_j / divisor, w = 1 for the S_t
+// entries and wts->w[q] for arrays[q]; wts == NULL: the plain mean above
+int flsim_aggregate_optim_wrule_push(const float* S, float* S_out, const flsim_rule* rule,
+                                     const flsim_rule_weights* wts, float* p, float* m, float* v,
+                                     long P, const long* tensor_sizes, int n_tensors, long step,
+                                     const flsim_optim* optim, hipStream_t stream) {
     RC(check_optim(optim));
+    RC(check_weights(wts));
     const int nstate = optim_n_state(optim);
     FLSIM_REQUIRE(S && p && (m || nstate < 1) && (v || nstate < 2) && tensor_sizes && rule,
                   "null pointer");
@@ -1126,9 +1263,10 @@ int flsim_aggregate_optim_rule_push(const float* S, float* S_out, const flsim_ru
     for (int q = 0; q < A.R.narr; ++q)
         FLSIM_REQUIRE(((uintptr_t)A.R.arr[q] & 15) == 0, "entry arrays must be 16-byte aligned");
     OptLaunch ol;
-    RC(make_opt_launch(optim, rule->k, step, &ol));
+    RC(make_opt_launch(optim, wts ? wts->divisor : (double)rule->k, step, &ol));
     A.ac = ol.ac;
     A.oc = ol.oc;
+    if (wts) RC(make_weights(rule, wts, S, S_out, A.w, RULE_MAX_ARR));
     // the register-array stream for the reference order with <= 2 entry arrays: 2 float4 groups
     // per thread without a stale array, 1 with (tools/agg_bench.py, profiles/r03a/agg_bench.txt:
     // 28.2 vs 28.4 us for k = 512; 32.0 vs 33.1 us for k = 513 with the stale S_{t-d});
@@ -1158,10 +1296,11 @@ int flsim_aggregate_optim_rule_push(const float* S, float* S_out, const flsim_ru
         long hi = lo;
         while (t < n_tensors) {
             const long n = tensor_sizes[t];
-            const bool tail = (n % 32) != 0;
+            const long body = rule_body((int)n, wts != nullptr);
+            const bool tail = body != n;
             if (tail && A.ntail == MAX_TAILS) break;
             if (tail) {
-                A.tail_lo[A.ntail] = (int)(off + (n / 32) * 32);
+                A.tail_lo[A.ntail] = (int)(off + body);
                 A.tail_hi[A.ntail] = (int)(off + n);
                 A.ntail++;
             }
@@ -1200,12 +1339,8 @@ int flsim_aggregate_optim_rule_push(const float* S, float* S_out, const flsim_ru
         const ProbeSlot ps = probe_begin();
         const dim3 grid((unsigned)(nblk + A.nedge));
         if (!reg && A.R.prog != nullptr) RC(stage_program(A.R, stream));
-        switch (ol.ok) {
-            case OK_ADAM: launch_agg<OK_ADAM>(reg, G, grid, stream, ps, A); break;
-            case OK_ADAMD: launch_agg<OK_ADAMD>(reg, G, grid, stream, ps, A); break;
-            case OK_SGDM: launch_agg<OK_SGDM>(reg, G, grid, stream, ps, A); break;
-            default: launch_agg<OK_SGD>(reg, G, grid, stream, ps, A); break;
-        }
+        if (wts) launch_agg_kind<true>(ol.ok, reg, G, grid, stream, ps, A);
+        else launch_agg_kind<false>(ol.ok, reg, G, grid, stream, ps, A);
         FLSIM_LAUNCH_CHECK();
         if (probe_end(ps, A.R.prog == nullptr ? K_AGG : K_AGG_SEQ, bytes)) return 2;
         lo = hi;
@@ -1267,11 +1402,11 @@ int flsim_cascade_program(int k, const int32_t* pos, const int32_t* arr, int n_e
 }
 
 // host interpreter of a macro program (testing): out[e] = the cascade sum of element e, x = S[e],
-// entry arrays ys[q][e]; tail[e] != 0 selects the row_sum program
-int flsim_cascade_eval_host(const int32_t* prog, const int32_t* info, const float* S,
-                            const float* const* ys, int n_arrays, const uint8_t* tail, long n,
-                            float* out) {
-    FLSIM_REQUIRE(prog && info && S && out, "null pointer");
+// entry arrays ys[q][e]; tail[e] != 0 selects the row_sum program.  wf (nullable): entry array q
+// enters as ys[q][e] * wf[q]; fdiv != 0: out[e] = sum / fdiv.
+static void eval_host(const int32_t* prog, const int32_t* info, const float* S,
+                      const float* const* ys, const float* wf, int n_arrays, float fdiv,
+                      const uint8_t* tail, long n, float* out) {
     struct HostPairs {
         const int32_t* w;
         uint32_t lo(int i) const { return (uint32_t)w[2 * i]; }
@@ -1280,10 +1415,41 @@ int flsim_cascade_eval_host(const int32_t* prog, const int32_t* info, const floa
     for (long e = 0; e < n; ++e) {
         const CascVals<float> cv = casc_values(S[e], info[2], info[3]);
         auto yf = [&](int q) -> float {
-            return (q < n_arrays && ys[q]) ? ys[q][e] : 0.f;
+            if (!(q < n_arrays && ys[q])) return 0.f;
+            return wf ? ys[q][e] * wf[q] : ys[q][e];
         };
-        out[e] = casc_run_macro(hp, (tail && tail[e]) ? info[1] : 0, cv, yf);
+        const float s = casc_run_macro(hp, (tail && tail[e]) ? info[1] : 0, cv, yf);
+        out[e] = fdiv != 0.f ? s / fdiv : s;
     }
+}
+
+int flsim_cascade_eval_host(const int32_t* prog, const int32_t* info, const float* S,
+                            const float* const* ys, int n_arrays, const uint8_t* tail, long n,
+                            float* out) {
+    FLSIM_REQUIRE(prog && info && S && out, "null pointer");
+    eval_host(prog, info, S, ys, nullptr, n_arrays, 0.f, tail, n, out);
+    return 0;
+}
+
+// the weighted twin of the W kernels (testing): entry array q enters as ys[q][e] * (float)w[q]
+// (one fp32 multiply where the value is loaded) and out[e] = sum / (float)divisor (the IEEE
+// division); weights and divisor are refused as the entry points refuse them
+int flsim_cascade_eval_host_w(const int32_t* prog, const int32_t* info, const float* S,
+                              const float* const* ys, const double* w, int n_arrays,
+                              double divisor, const uint8_t* tail, long n, float* out) {
+    FLSIM_REQUIRE(n_arrays >= 0 && n_arrays <= RULE_MAX_ARR, "n_arrays = %d", n_arrays);
+    FLSIM_REQUIRE(w || n_arrays == 0, "null pointer");
+    flsim_rule_weights rw{};
+    rw.n = n_arrays;
+    for (int q = 0; q < n_arrays; ++q) rw.w[q] = w[q];
+    rw.divisor = divisor;
+    RC(check_weights(&rw));
+    FLSIM_REQUIRE(prog && info && S && out && (ys || n_arrays == 0), "null pointer");
+    AdamConst ac;
+    RC(make_divisor(divisor, &ac));
+    float wf[RULE_MAX_ARR];
+    for (int q = 0; q < n_arrays; ++q) wf[q] = (float)w[q];
+    eval_host(prog, info, S, ys, wf, n_arrays, ac.fk, tail, n, out);
     return 0;
 }
 

@@ -25,6 +25,9 @@ namespace flsim {
 constexpr int STEP_MAX_SEG = 40;      // parameter tensors per network (vgg11_bn: 38)
 constexpr int RULE_MAX_ARR = FLSIM_MAX_ARRAYS;   // weight_ups arrays besides S_t per launch
 constexpr int RULE_INL_PROG = 192;    // program words carried in the kernel arguments
+// arrays of a weighted rule in the fused step: its argument block (the segments take 2.5 KB of the
+// 4 KB) has room for this many weights; the streaming step carries RULE_MAX_ARR
+constexpr int STEP_MAX_WARR = 16;
 constexpr long STEP_UNIT_FLOATS = 65536;
 
 // host description of one parameter tensor's gradient slabs (offsets in floats)
@@ -182,17 +185,25 @@ struct OptLaunch {
     OptConst oc;
 };
 // the same with a chosen update rule; m / v may be null where the kind does not own them
+// weights (nullable): the staleness-weighted rule, weights[q] (fp32) of rule->arr[q], at most
+// STEP_MAX_WARR arrays; ol's divisor is then the weighted rule's
 int slab_step_launch_optim(float* gradstate, const StepPlan& plan, long cnt_off, long part_off,
                            float* S_out, const RuleProg* rule, const OptLaunch& ol, float* p,
-                           float* m, float* v, long P, hipStream_t stream);
+                           float* m, float* v, long P, hipStream_t stream,
+                           const float* weights = nullptr);
 
 // host helpers shared with server.hip's C-ABI
 int make_rule(const flsim_rule* r, RuleProg* out);
-int make_adam_const(int divisor, long step, double lr, double beta1, double beta2, double eps,
+int make_adam_const(double divisor, long step, double lr, double beta1, double beta2, double eps,
                     AdamConst* ac);
 // hyper-parameter checks (the cases where torch raises ValueError); before any pointer check
 int check_optim(const flsim_optim* o);
-int make_opt_launch(const flsim_optim* o, int divisor, long step, OptLaunch* ol);
+int make_opt_launch(const flsim_optim* o, double divisor, long step, OptLaunch* ol);
+// a weighted rule's weights and divisor (include/flsim.h); before any pointer check
+int check_weights(const flsim_rule_weights* w);
+// the weights in launch form (fp32); alias0 / alias1: buffers that are S_t (their weight must be 1)
+int make_weights(const flsim_rule* r, const flsim_rule_weights* w, const float* alias0,
+                 const float* alias1, float* out, int cap);
 inline flsim_optim adam_optim(double lr, double beta1, double beta2, double eps) {
     flsim_optim o{};
     o.kind = FLSIM_OPT_ADAM;

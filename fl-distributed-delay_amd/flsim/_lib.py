@@ -43,6 +43,9 @@ EXPORTS = [
     "flsim_allreduce_sum", "flsim_comm_destroy",
     "flsim_aggregate_optim_rule_push", "flsim_pn1_server_step_optim",
     "flsim_vgg11_server_step_optim", "flsim_vgg11_bn_server_step_optim",
+    "flsim_aggregate_optim_wrule_push", "flsim_pn1_server_step_wrule",
+    "flsim_vgg11_server_step_wrule", "flsim_vgg11_bn_server_step_wrule",
+    "flsim_cascade_eval_host_w",
 ]
 COMM_ID_BYTES = 128      # FLSIM_COMM_ID_BYTES
 
@@ -59,6 +62,12 @@ class FlsimRule(ctypes.Structure):
     _fields_ = [("k", ctypes.c_int32), ("c", ctypes.c_int32), ("prog", ctypes.c_void_p),
                 ("info", ctypes.c_int32 * 4), ("n_arrays", ctypes.c_int32),
                 ("arrays", ctypes.c_void_p * MAX_ARRAYS)]
+
+
+class FlsimRuleWeights(ctypes.Structure):
+    """flsim_rule_weights (include/flsim.h): the weights of a rule's arrays and its divisor."""
+    _fields_ = [("n", ctypes.c_int32), ("w", ctypes.c_double * MAX_ARRAYS),
+                ("divisor", ctypes.c_double)]
 
 
 OPT_KINDS = {"adam": 0, "adamw": 1, "sgd": 2}      # FLSIM_OPT_ADAM / _ADAMW / _SGD
@@ -117,6 +126,7 @@ def lib():
         f("server_step").argtypes = [vp, vp, vp, vp, vp, vp, ctypes.c_long, ctypes.c_double,
                                      ctypes.c_double, ctypes.c_double, ctypes.c_double, vp]
         f("server_step_optim").argtypes = [vp, vp, vp, vp, vp, vp, ctypes.c_long, vp, vp]
+        f("server_step_wrule").argtypes = [vp, vp, vp, vp, vp, vp, vp, ctypes.c_long, vp, vp]
         f("eval_pool").argtypes = [vp, vp, ctypes.c_int, vp, vp, ctypes.c_int, ctypes.c_int,
                                    vp] + bn + [vp, vp]
     L.flsim_pn1_workspace_split_part.argtypes = [ctypes.c_int]
@@ -164,6 +174,10 @@ def lib():
         ctypes.c_long, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, vp]
     L.flsim_aggregate_optim_rule_push.argtypes = [
         vp, vp, vp, vp, vp, vp, ctypes.c_long, vp, ctypes.c_int, ctypes.c_long, vp, vp]
+    L.flsim_aggregate_optim_wrule_push.argtypes = [
+        vp, vp, vp, vp, vp, vp, vp, ctypes.c_long, vp, ctypes.c_int, ctypes.c_long, vp, vp]
+    L.flsim_cascade_eval_host_w.argtypes = [vp, vp, vp, vp, vp, ctypes.c_int, ctypes.c_double, vp,
+                                            ctypes.c_long, vp]
     L.flsim_cascade_program.argtypes = [ctypes.c_int, vp, vp, ctypes.c_int, vp, ctypes.c_int, vp]
     L.flsim_cascade_eval_host.argtypes = [vp, vp, vp, vp, ctypes.c_int, vp, ctypes.c_long, vp]
     L.flsim_probe_enable.argtypes = [ctypes.c_int]
@@ -182,6 +196,8 @@ def check(rc):
                 raise IndexError(msg)
             if "ZeroDivisionError" in msg:
                 raise ZeroDivisionError(msg)
+            if "NotImplementedError" in msg:
+                raise NotImplementedError(msg)
             raise ValueError(msg)
         raise FLSimError(msg)
 

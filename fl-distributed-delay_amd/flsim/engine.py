@@ -18,8 +18,10 @@ import dataclasses
 import numpy as np
 import torch
 
-from ._lib import (MAX_ARRAYS, OPT_KINDS, FlsimOptim, FlsimRule, WorkerRec, check, lib, ptr,
-                   stream_ptr)
+import math
+
+from ._lib import (MAX_ARRAYS, OPT_KINDS, FlsimOptim, FlsimRule, FlsimRuleWeights, WorkerRec, check,
+                   lib, ptr, stream_ptr)
 
 # named_parameters() order of models.py:PerformantNet1 (models.py:13-25)
 PN1_SHAPES = [
@@ -316,7 +318,16 @@ class NetEngine:
         """world = 1: the epoch's slabs -> S_t [-> S_out] -> rule() + Adam in one launch
         (flsim_<net>_server_step).  rule: a Rule.  optim (an Optim or a dict of its fields): that
         update rule instead (flsim_<net>_server_step_optim); m / v may be None where the kind
-        owns no such array."""
+        owns no such array.  A rule with weights runs the staleness-weighted step
+        (flsim_<net>_server_step_wrule)."""
+        if rule.c_weights is not None:
+            o = (as_optim(optim) if optim is not None else
+                 Optim(lr=lr, betas=tuple(betas), eps=eps)).c_struct()
+            check(self._fn("server_step_wrule")(
+                ptr(self.gradstate), ptr(S_out), ctypes.byref(rule.c_rule),
+                ctypes.byref(rule.c_weights), ptr(theta), ptr(m), ptr(v), int(step),
+                ctypes.byref(o), stream_ptr()))
+            return
         if optim is not None:
             o = as_optim(optim).c_struct()
             check(self._fn("server_step_optim")(
@@ -563,10 +574,42 @@ class Rule:
     """weight_ups of one rule() call (flsim_rule): k entries (the mean's divisor); either the
     reference order [S_t] * c + arrays, or a general order given as events [(position, array
     index)] whose program is built on the host and staged to the device (`stager`).  arrays:
-    device tensors or None (a zero entry, torch-1.x)."""
+    device tensors or None (a zero entry, torch-1.x).
 
-    def __init__(self, k, arrays=(), c=None, events=None, stager=None):
+    weights (one Python float per array; None = the plain mean) make it the staleness-weighted
+    rule sum_j w_j * entry_j / divisor with w = 1.0 for every S_t entry: divisor defaults to the
+    sum of all k weights ("weights" normalisation; pass k for "count").  A weight must be finite
+    and >= 0 (ValueError), the divisor > 0 (ZeroDivisionError)."""
+
+    def __init__(self, k, arrays=(), c=None, events=None, stager=None, weights=None,
+                 divisor=None):
         arrays = list(arrays)
+        self.weights, self.divisor, self.c_weights = None, None, None
+        if weights is None and divisor is not None:
+            weights = [1.0] * len(arrays)
+        if weights is not None:
+            weights = [float(w) for w in weights]
+            if len(weights) != len(arrays):
+                raise ValueError(f"{len(weights)} weights for {len(arrays)} arrays")
+            for w in weights:
+                if not (w >= 0 and math.isfinite(w)):
+                    raise ValueError(f"Invalid weight {w}: a weight must be finite and >= 0")
+            if divisor is None:
+                # float(sum(weights)) over the k entries in weight_ups order: the S_t entries weigh
+                # 1.0 each, every other entry its array's weight
+                if events is None:
+                    full = [1.0] * int(c) + weights
+                else:
+                    full = [1.0] * int(k)
+                    for pos, j in events:
+                        full[pos] = weights[j]
+                divisor = float(sum(full))
+            divisor = float(divisor)
+            if divisor != divisor or math.isinf(divisor):
+                raise ValueError(f"Invalid divisor {divisor}")
+            if not divisor > 0:
+                raise ZeroDivisionError(f"weighted rule divisor {divisor}")
+            self.weights, self.divisor = weights, divisor
         if len(arrays) > MAX_ARRAYS:
             raise NotImplementedError(f"{len(arrays)} distinct weight_ups arrays in one step "
                                       f"(max {MAX_ARRAYS})")
@@ -589,6 +632,38 @@ class Rule:
             for j in range(4):
                 r.info[j] = int(info[j])
         self.c_rule = r
+        if self.weights is not None and len(arrays) <= MAX_ARRAYS:
+            cw = FlsimRuleWeights()
+            cw.n = len(arrays)
+            for q, w in enumerate(self.weights):
+                cw.w[q] = w
+            cw.divisor = self.divisor
+            self.c_weights = cw
+
+
+def staleness_weight(spec):
+    """The discount s(tau) of a stale entry of age tau epochs as a function tau -> float (host,
+    double).  spec: None (no discount: 1.0), a callable (returned as it is), or
+      ("poly", a)      (1.0 + tau) ** (-a)                                   (FedAsync)
+      ("hinge", a, b)  1.0 if tau <= b else 1.0 / (a * (tau - b) + 1.0)      (FedAsync)
+      ("const", a)     a"""
+    if spec is None:
+        return lambda tau: 1.0
+    if callable(spec):
+        return spec
+    spec = tuple(spec)
+    kind, args = spec[0], [float(x) for x in spec[1:]]
+    if kind == "poly" and len(args) == 1:
+        a, = args
+        return lambda tau: (1.0 + tau) ** (-a)
+    if kind == "hinge" and len(args) == 2:
+        a, b = args
+        return lambda tau: 1.0 if tau <= b else 1.0 / (a * (tau - b) + 1.0)
+    if kind == "const" and len(args) == 1:
+        a, = args
+        return lambda tau: a
+    raise ValueError(f"stale weight {spec!r} (supported: ('poly', a), ('hinge', a, b), "
+                     "('const', a) or a callable)")
 
 
 class ProgramStager:
@@ -629,6 +704,14 @@ def aggregate_rule(S, rule, theta, m, v, step, sizes, lr=1e-3, betas=(0.9, 0.999
     (flsim_aggregate_optim_rule_push); m / v may be None where the kind owns no such array (SGD:
     v; SGD without momentum: m and v) and are left untouched when given."""
     csz = (ctypes.c_long * len(sizes))(*[int(n) for n in sizes])
+    if rule.c_weights is not None:      # the staleness-weighted rule
+        o = (as_optim(optim) if optim is not None else
+             Optim(lr=lr, betas=tuple(betas), eps=eps)).c_struct()
+        check(lib().flsim_aggregate_optim_wrule_push(
+            ptr(S), ptr(S_out), ctypes.byref(rule.c_rule), ctypes.byref(rule.c_weights),
+            ptr(theta), ptr(m), ptr(v), sum(int(n) for n in sizes), csz, len(sizes), int(step),
+            ctypes.byref(o), stream_ptr()))
+        return
     if optim is not None:
         o = as_optim(optim).c_struct()
         check(lib().flsim_aggregate_optim_rule_push(

@@ -15,6 +15,11 @@ Per epoch t (one "server step"):
      are the stale gradients S_{t-d};
   5. fused rule() + Adam on the device: c_t copies of S_t and the stale entries (main.py:184,188);
   6. 'Avg. Loss' = np.mean of the fast workers' losses (main.py:172,185).
+
+stale_weight (None, ("poly", a), ("hinge", a, b), ("const", a) or a callable tau -> float) discounts
+a popped FIFO entry by its age tau = t - (the epoch it was pushed) before the average (FedAsync's
+alternative to the throttle): rule() becomes sum_j w_j * entry_j / W, w = 1.0 for every S_t entry,
+W = the sum of the weights (stale_normalize="weights") or the entry count ("count").
 """
 from __future__ import annotations
 
@@ -24,10 +29,12 @@ import numpy as np
 import torch
 
 from .data import DevicePool, make_test_pool
-from .engine import PN1_SIZES, Optim, ProgramStager, Rule, engine_class, padded, split_views
+from .engine import (PN1_SIZES, Optim, ProgramStager, Rule, engine_class, padded, split_views,
+                     staleness_weight)
 from .schedule import Schedule, reference_delays
 
 SEMANTICS = ("reference", "torch1", "independent")
+STEP_MAX_WARR = 16      # arrays of a weighted rule the fused step takes (csrc/slabstep.h)
 # checkpoint format: 2 records the model, the optimizer hyper-parameters and the throttle cap, and
 # the reference's --delay 0 slow worker as DELAY_ZERO (restore() migrates format 1)
 CKPT_FORMAT = "flsim-checkpoint-2"
@@ -62,9 +69,21 @@ class FLSimulation:
                  engine=None, device_pool=None, test_pool=None, model="PerformantNet1",
                  fused=True, keep_S=False, batch_size=128, distributed=None,
                  collective="torch", optimizer="adam", weight_decay=0.0, momentum=0.0,
-                 dampening=0.0, nesterov=False):
+                 dampening=0.0, nesterov=False, stale_weight=None, stale_normalize="weights"):
         if semantics not in SEMANTICS:
             raise NotImplementedError(f"semantics {semantics!r} (supported: {SEMANTICS})")
+        # the discount of a popped entry's age; a replicated host computation (every rank derives
+        # the same weights from the schedule)
+        if stale_normalize not in ("weights", "count"):
+            raise ValueError(f"stale_normalize {stale_normalize!r} (supported: 'weights', 'count')")
+        if isinstance(stale_weight, str):
+            stale_weight = None if stale_weight == "none" else (stale_weight,)
+        self.stale_weight = stale_weight if stale_weight is None or callable(stale_weight) \
+            else tuple(stale_weight)
+        self.stale_normalize = stale_normalize
+        self._stale_fn = None if stale_weight is None else staleness_weight(self.stale_weight)
+        if self._stale_fn is not None and semantics == "independent":
+            raise NotImplementedError("independent entries with a staleness discount")
         self.n = int(n_workers)
         if self.n < 1:
             raise ValueError("n_workers must be >= 1")
@@ -263,16 +282,48 @@ class FLSimulation:
         array index."""
         k = plan.c_t + plan.s_t
         order = self._entry_order(plan)
+        ws = self._entry_weights(plan)      # per popped entry, or None: the plain mean
         if order is None:       # reference order: c_t copies of S_t, then the stale entries
-            return Rule(k, stale, c=plan.c_t)
-        uniq, ev = [], []
-        for pos, a in zip(order[0], stale):
+            if ws is None:
+                return Rule(k, stale, c=plan.c_t)
+            full = [1.0] * plan.c_t + ws
+            return Rule(k, stale, c=plan.c_t, **self._weighted(k, full, ws))
+        uniq, ev, uw = [], [], []
+        for j0, (pos, a) in enumerate(zip(order[0], stale)):
+            # entries of one source epoch share an array, and their age, hence their weight (the
+            # torch-1.x zero entries share one null array: a zero stays zero under any weight,
+            # and the divisor below is summed over the entries, not the arrays)
             j = next((q for q, u in enumerate(uniq) if u is a), None)
             if j is None:
                 uniq.append(a)
+                uw.append(None if ws is None else ws[j0])
                 j = len(uniq) - 1
             ev.append((pos, j))
-        return Rule(k, uniq, events=ev, stager=self._stager)
+        arrays = uniq
+        if ws is None:
+            return Rule(k, arrays, events=ev, stager=self._stager)
+        full = [1.0] * k
+        for (pos, _), w in zip(ev, ws):
+            full[pos] = w
+        return Rule(k, arrays, events=ev, stager=self._stager, **self._weighted(k, full, uw))
+
+    def _entry_weights(self, plan):
+        """s(tau) of every popped FIFO entry in append order, tau = t - (the epoch it was
+        pushed); None when the epoch's rule is the plain mean: no discount, nothing popped, or
+        all weights 1.0 (then the divisor is k under either normalisation)."""
+        if self._stale_fn is None or not plan.stale:
+            return None
+        ws = [float(self._stale_fn(int(plan.t) - int(src))) for (_, src) in plan.stale]
+        for w in ws:
+            if not (w >= 0 and np.isfinite(w)):
+                raise ValueError(f"Invalid weight {w}: a weight must be finite and >= 0")
+        return None if all(w == 1.0 for w in ws) else ws
+
+    def _weighted(self, k, full, weights):
+        """Rule's weights / divisor arguments: full = the k entries' weights in weight_ups
+        order (the rule text's `weights`)."""
+        W = float(sum(full)) if self.stale_normalize == "weights" else float(k)
+        return dict(weights=weights, divisor=W)
 
     @staticmethod
     def _entry_order(plan):
@@ -316,6 +367,9 @@ class FLSimulation:
         eng = self.engine
         G = self.G                               # 128-sample groups (units) per worker-step
         fused = self.fused and not self.distributed and hasattr(eng, "server_step")
+        # (a weighted rule over more arrays than the fused step takes: reduce, then stream)
+        keep_S = self.keep_S or (fused and self._stale_fn is not None and
+                                 len({int(src) for (_, src) in plan.stale}) > STEP_MAX_WARR)
         pushes = plan.pushed and self.semantics == "reference"
         # An epoch that pushes S_t onto the FIFO and ends with the streaming server step (world > 1,
         # or an engine without the fused step) builds S_t -- and all-reduces it -- straight in the
@@ -323,7 +377,7 @@ class FLSimulation:
         # and writes no second copy (4P fewer HBM bytes at every tick).  BatchNorm runs
         # keep the shared buffer (their comm buffer also holds n x the per-call statistics).
         # (keep_S: S_t stays in comm[:P], where the caller reads it)
-        in_slot = pushes and not fused and not self.nstat and not self.keep_S
+        in_slot = pushes and not fused and not self.nstat and not keep_S
         comm = self._slot(self.stats_off) if in_slot else self.comm
         S = comm[:self.P]
         losses = comm[self.Ppad:self.Ppad + len(active) * G]
@@ -347,7 +401,7 @@ class FLSimulation:
             kw = {"stats_out": stats[c0:c1]} if self.nstat else {}
             eng.run_chunk(self.theta, self.pool, wt[c0 - lo * G:c1 - lo * G], c1 - c0, self.n,
                           self.seed, self.dropout, losses[c0:c1], **kw)
-        if not fused or self.keep_S:
+        if not fused or keep_S:
             eng.end_epoch(S)
         self.rank_worker_steps.append(hi - lo)
         if self.distributed:
@@ -360,7 +414,7 @@ class FLSimulation:
         if pushes:
             n_push = int(sum(1 for i in range(self.n) if self.delays[i] != 0 and plan.computes[i]))
             push = comm if in_slot else self._slot()
-            if fused and self.keep_S:
+            if fused and keep_S:
                 push[:self.P].copy_(S)
             # otherwise the server step writes S_t into the slot in its own pass: the fused
             # slab step (world = 1) or the stream after the all-reduce (world > 1)
@@ -377,7 +431,7 @@ class FLSimulation:
         hp = dict(lr=self.lr, betas=self.betas, eps=self.eps)
         if self._optim_arg is not None:
             hp = dict(optim=self._optim_arg)
-        if fused and not self.keep_S:
+        if fused and not keep_S:
             eng.server_step(push, rule, self.theta, self.m, self.v, self.step, **hp)
         elif fused:
             eng.aggregate_rule(S, rule, self.theta, self.m, self.v, self.step, **hp)
@@ -546,7 +600,8 @@ class FLSimulation:
                        "throttle": self.throttle, "seed": self.seed, "semantics": self.semantics,
                        "dropout": self.dropout, "lr": self.lr, "betas": list(self.betas),
                        "eps": self.eps, "max_throttle": self.max_throttle,
-                       "batch_size": self.batch_size, **self._optim_config()},
+                       "batch_size": self.batch_size, **self._optim_config(),
+                       **self._stale_config()},
             "epoch": len(self.trace), "step": self.step,
             "theta": self.theta.detach().cpu(),
             # the state arrays the optimizer owns (SGD: no v; without momentum no m either)
@@ -561,6 +616,17 @@ class FLSimulation:
         o = self.optim
         return {"optimizer": o.kind, "weight_decay": o.weight_decay, "momentum": o.momentum,
                 "dampening": o.dampening, "nesterov": o.nesterov}
+
+    def _stale_config(self):
+        """The discount as the checkpoint records it: its spec as a list (None: no discount) and
+        the normaliser.  The weights themselves are no state: they depend only on (t, src)."""
+        if callable(self.stale_weight):
+            raise NotImplementedError("checkpoint of a run whose stale_weight is a callable: "
+                                      "only a spec (('poly', a), ('hinge', a, b), ('const', a)) "
+                                      "can be recorded and checked at restore")
+        spec = None if self.stale_weight is None else \
+            [self.stale_weight[0]] + [float(x) for x in self.stale_weight[1:]]
+        return {"stale_weight": spec, "stale_normalize": self.stale_normalize}
 
     def save_checkpoint(self, path):
         torch.save(self.checkpoint(), path)
@@ -578,10 +644,12 @@ class FLSimulation:
                 "semantics": self.semantics, "dropout": self.dropout, "model": self.model,
                 "lr": self.lr, "betas": list(self.betas), "eps": self.eps,
                 "max_throttle": self.max_throttle, "batch_size": self.batch_size,
-                **self._optim_config()}
+                **self._optim_config(), **self._stale_config()}
         # a checkpoint from before the optimizer was recorded: Adam without weight decay
         for k, v in (("optimizer", "adam"), ("weight_decay", 0.0), ("momentum", 0.0),
-                     ("dampening", 0.0), ("nesterov", False)):
+                     ("dampening", 0.0), ("nesterov", False),
+                     # ... and from before the staleness discount: none
+                     ("stale_weight", None), ("stale_normalize", "weights")):
             cfg.setdefault(k, v)
         delays = cfg["delays"].numpy().astype(np.int32)
         if fmt == "flsim-checkpoint-1":

@@ -2,7 +2,9 @@
 
 Same flags and defaults (main.py:38-53): --n_workers --n_epochs --batch_size --learning_rate
 --delay --model_file --throttle.  --optimizer {adam,adamw,sgd} with --momentum --dampening
---nesterov --weight_decay picks the central optimizer (main.py:106 hard-wires Adam(lr)).  The training loop (main.py:126-188) runs as flsim.sim
+--nesterov --weight_decay picks the central optimizer (main.py:106 hard-wires Adam(lr)).
+--stale_weight {none,poly,hinge,const} with --stale_a --stale_b --stale_normalize discounts a stale
+entry by its age before the average (the alternative to --throttle).  The training loop (main.py:126-188) runs as flsim.sim
 .FLSimulation: host schedule, worker-batched HIP forward/backward, fused rule()+Adam; with
 `torchrun --nproc-per-node N` the computing workers are sharded over N GPUs with one RCCL
 all-reduce per epoch.  'Avg. Loss' per epoch (main.py:185) goes to --log (JSONL; tensorboard is
@@ -48,6 +50,13 @@ def parse(argv=None):
     p.add_argument('--dampening', type=float, default=0.0, help='SGD dampening')
     p.add_argument('--nesterov', action='store_true', help='SGD Nesterov momentum')
     p.add_argument('--weight_decay', type=float, default=0.0, help='weight decay')
+    p.add_argument('--stale_weight', default='none', choices=['none', 'poly', 'hinge', 'const'],
+                   help='discount of a stale entry of age tau before the average: poly '
+                        '(1+tau)^-a, hinge 1 if tau <= b else 1/(a(tau-b)+1), const a')
+    p.add_argument('--stale_a', type=float, default=0.5, help='a of --stale_weight')
+    p.add_argument('--stale_b', type=float, default=0.0, help='b of --stale_weight hinge')
+    p.add_argument('--stale_normalize', default='weights', choices=['weights', 'count'],
+                   help='divide the weighted sum by the sum of the weights or the entry count')
     p.add_argument('--seed', type=int, default=0)
     p.add_argument('--semantics', default='reference', choices=['reference', 'torch1', 'independent'],
                    help='stale entry = S_{t-d} (torch>=2 aliasing), zeros (torch 1.x) or the slow '
@@ -68,6 +77,15 @@ def parse(argv=None):
     p.add_argument('--checkpoint_every', type=int, default=0)
     p.add_argument('--resume', type=str, default=None, help='continue from a checkpoint')
     return p.parse_args(argv)
+
+
+def stale_spec(args):
+    """--stale_weight / --stale_a / --stale_b as FLSimulation's stale_weight spec."""
+    if args.stale_weight == 'none':
+        return None
+    if args.stale_weight == 'hinge':
+        return ('hinge', args.stale_a, args.stale_b)
+    return (args.stale_weight, args.stale_a)
 
 
 def main(argv=None):
@@ -98,7 +116,8 @@ def main(argv=None):
                        theta0=theta0, pool=pool, test_pool=test_pool, model=args.model,
                        batch_size=args.batch_size, optimizer=args.optimizer,
                        weight_decay=args.weight_decay, momentum=args.momentum,
-                       dampening=args.dampening, nesterov=args.nesterov)
+                       dampening=args.dampening, nesterov=args.nesterov,
+                       stale_weight=stale_spec(args), stale_normalize=args.stale_normalize)
     if buffers:
         sim.engine.load_buffers(buffers)
     if args.resume:

@@ -396,6 +396,47 @@ int flsim_vgg11_bn_server_step_optim(void* gradstate, float* S_out, const flsim_
                                      const flsim_optim* optim, flsim_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Staleness-weighted rule: Agg(rule) (agents.py:43-45) takes any rule; these entry points run
+ *
+ *   [torch.stack([x[i] * w for x, w in zip(ups_list, weights)]).sum(0) / W for i in ...]
+ *
+ * fused with the update, bit-exact with torch 2.10 CPU: w = 1.0 for every entry that is S_t,
+ * wts->w[q] for arrays[q] (a popped FIFO entry discounted by its age), W = wts->divisor (the sum
+ * of the weights, or the entry count).  Each weight and the divisor are rounded to fp32 once; a
+ * stale value is multiplied by its weight in fp32 where it is loaded, the cascade sums the
+ * products, one IEEE fp32 division follows.  A NULL array stays zero and still counts in the
+ * divisor.  wts == NULL is the plain mean (the entry points above are these with wts = NULL).
+ * Checked before any pointer, status 1: a weight that is not finite and >= 0; a divisor that is
+ * not > 0 (message "ZeroDivisionError: ...") or not finite.  Then: wts->n != rule->n_arrays; an
+ * array that is S_t itself (the S or S_out buffer) with a weight other than 1.0, and a fused step
+ * with more than 16 arrays (message "NotImplementedError: ..."; the streaming step takes all 64).
+ * ------------------------------------------------------------------------------------------- */
+typedef struct flsim_rule_weights {
+    int32_t n;                   /* == rule->n_arrays */
+    double w[FLSIM_MAX_ARRAYS];  /* weight of arrays[q]; rounded to fp32 once */
+    double divisor;              /* rounded to fp32 once; > 0 */
+} flsim_rule_weights;
+
+int flsim_aggregate_optim_wrule_push(const float* S, float* S_out, const flsim_rule* rule,
+                                     const flsim_rule_weights* wts, float* p, float* m, float* v,
+                                     long P, const long* tensor_sizes, int n_tensors, long step,
+                                     const flsim_optim* optim, flsim_stream_t stream);
+int flsim_pn1_server_step_wrule(void* gradstate, float* S_out, const flsim_rule* rule,
+                                const flsim_rule_weights* wts, float* p, float* m, float* v,
+                                long step, const flsim_optim* optim, flsim_stream_t stream);
+int flsim_vgg11_server_step_wrule(void* gradstate, float* S_out, const flsim_rule* rule,
+                                  const flsim_rule_weights* wts, float* p, float* m, float* v,
+                                  long step, const flsim_optim* optim, flsim_stream_t stream);
+int flsim_vgg11_bn_server_step_wrule(void* gradstate, float* S_out, const flsim_rule* rule,
+                                     const flsim_rule_weights* wts, float* p, float* m, float* v,
+                                     long step, const flsim_optim* optim, flsim_stream_t stream);
+/* host (testing): flsim_cascade_eval_host with the weighted rule's arithmetic: entry array q
+ * enters as ys[q][e] * (float)w[q], out[e] = sum / (float)divisor */
+int flsim_cascade_eval_host_w(const int32_t* prog, const int32_t* info, const float* S,
+                              const float* const* ys, const double* w, int n_arrays,
+                              double divisor, const uint8_t* tail, long n, float* out);
+
+/* ---------------------------------------------------------------------------------------------
  * Measurement (no reference counterpart): HIP events around every worker-batched GEMM launch on
  * its stream, for bench.py's live roofline figure.  read() fills flsim_probe_kernel_count()
  * entries per kernel id (launches, total ms, total algorithmic FLOPs) and resets the record.
