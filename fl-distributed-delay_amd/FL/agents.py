@@ -417,11 +417,13 @@ def _context(model):
 class _LazyMean(list):
     """What FL.agents.rule returns: the weight_ups list, reduced inside Central.update_model."""
 
-    def __init__(self, ups_list, weights=None, normalize="weights"):
+    def __init__(self, ups_list, weights=None, normalize="weights", snaps=None, lam=None):
         super().__init__()
         self.ups_list = ups_list
         self.weights = weights          # one Python float per entry, or None: the plain mean
         self.normalize = normalize
+        self.snaps = snaps              # delay compensation: one snapshot or None per entry
+        self.lam = lam
 
 
 def rule(ups_list):
@@ -449,6 +451,43 @@ def weighted_rule(ups_list, weights, normalize="weights"):
     if normalize not in ("weights", "count"):
         raise ValueError(f"normalize {normalize!r} (supported: 'weights', 'count')")
     return _LazyMean(ups_list, weights, normalize)
+
+
+def snapshot_parameters(model):
+    """A flat device copy of the model's parameters (theta, named_parameters order): the snapshot a
+    slow worker keeps beside the gradient it pushes, for compensated_rule."""
+    ctx = _context(model)
+    return ctx.theta[:ctx.P].detach().clone()
+
+
+def compensated_rule(ups_list, snaps, lam, weights=None, normalize="weights"):
+    """Delay compensation (DC-ASGD) in front of rule() / weighted_rule(), for Agg(rule) with the
+    extra arguments bound:
+
+        def compensate(x, theta_now, theta_src, lam):
+            return x + (x * x) * lam * (theta_now - theta_src)
+        ys = [u if s is None else [compensate(u[i], theta_now[i], s[i], lam) for i in ...]
+              for u, s in zip(ups_list, snaps)]
+        return rule(ys) if weights is None else weighted_rule(ys, weights, normalize)
+
+    evaluated lazily and fused with the optimizer step in Central.update_model (theta_now = the
+    model's parameters before that step), bit-exact with that text on torch CPU.  snaps: per entry
+    a snapshot_parameters() result or None (not compensated; required for an entry that is this
+    epoch's gradient).  An entry is a sum over its epoch's workers, so x * x grows with the square
+    of the worker count: choose lam with that in mind."""
+    if len(ups_list) == 0:
+        raise IndexError("list index out of range")
+    snaps = list(snaps)
+    if len(snaps) != len(ups_list):
+        raise ValueError(f"{len(snaps)} snapshots for {len(ups_list)} entries")
+    lam = float(lam)
+    if not (lam >= 0 and lam != float("inf")):
+        raise ValueError(f"Invalid delay compensation lambda {lam}: it must be finite and >= 0")
+    if weights is None:
+        return _LazyMean(ups_list, snaps=snaps, lam=lam)
+    lazy = weighted_rule(ups_list, weights, normalize)
+    lazy.snaps, lazy.lam = snaps, lam
+    return lazy
 
 
 class Central:
@@ -505,19 +544,26 @@ class Central:
         S = ctx.G if ctx.G is not None else torch.zeros(padded(ctx.P), device=ctx.device)
         sbase = S.untyped_storage().data_ptr()
         wts = ups.weights
-        arrays, bases, events, aw = [], [], [], []
+        sn = ups.snaps
+        arrays, bases, events, aw, asn = [], [], [], [], []
         for pos, e in enumerate(entries):
             b = e.untyped_storage().data_ptr()
             if b == sbase:
                 if wts is not None and wts[pos] != 1.0:
                     raise NotImplementedError(f"entry {pos} is this epoch's gradient: its weight "
                                               f"must be 1.0 (is {wts[pos]})")
+                if sn is not None and sn[pos] is not None:
+                    raise NotImplementedError(f"entry {pos} is this epoch's gradient: it takes no "
+                                              "snapshot")
                 continue
             if b not in bases:
                 bases.append(b)
                 arrays.append(_flat_of(e, ctx))
                 aw.append(None if wts is None else wts[pos])
+                asn.append(None if sn is None else sn[pos])
             j = bases.index(b)
+            if sn is not None and sn[pos] is not asn[j]:
+                raise NotImplementedError("entries of one gradient buffer with different snapshots")
             if wts is not None and wts[pos] != aw[j]:
                 raise NotImplementedError(f"entries of one gradient buffer with different weights "
                                           f"({aw[j]} and {wts[pos]})")
@@ -528,12 +574,17 @@ class Central:
         if wts is not None and not all(w == 1.0 for w in wts):   # else: the plain mean
             W = float(sum(wts)) if ups.normalize == "weights" else float(k)
             kw = dict(divisor=W)
+        comp = sn is not None and any(x is not None for x in asn)
         if len(events) <= 8 and all(p >= c for p, _ in events):    # reference order
             if kw:
                 kw["weights"] = [aw[j] for _, j in events]
+            if comp:
+                kw.update(snapshots=[asn[j] for _, j in events], delay_comp=ups.lam)
             return S, Rule(k, [arrays[j] for _, j in events], c=c, **kw)
         if kw:
             kw["weights"] = aw
+        if comp:
+            kw.update(snapshots=asn, delay_comp=ups.lam)
         return S, Rule(k, arrays, events=events, stager=ctx.stager, **kw)
 
     def update_model(self, ups):
@@ -557,7 +608,7 @@ class Central:
             hp = dict(optim=o)
         if isinstance(ups, _LazyMean) and ctx.G is not None and ctx.carry is None and \
                 not ctx.touched and hasattr(eng, "server_step") and \
-                not (r.c_weights is not None and len(r.arrays) > 16):
+                not ((r.c_weights is not None or r.c_comp is not None) and len(r.arrays) > 16):
             # fused: this epoch's slabs -> S_t (also written into G, which the FIFO entries of
             # main.py:156,161 alias) -> rule() + Adam, one pass
             ctx.flush_backward()

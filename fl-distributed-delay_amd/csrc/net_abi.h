@@ -239,12 +239,18 @@ static int net_end_epoch(void* gradstate, float* grad_out, hipStream_t stream) {
 // the same reduction fused with rule() + the update rule of `optim` (include/flsim.h: SGD, Adam
 // with weight decay, AdamW), world = 1
 // wts (nullable): the staleness-weighted rule (include/flsim.h)
+// comp (nullable), theta_out (nullable): delay compensation and the snapshot write; either one
+// selects the compensated step, which runs in the weighted form (wts == NULL: weights 1.0 and the
+// divisor k)
 template <class N>
-static int net_server_step_wrule(void* gradstate, float* S_out, const flsim_rule* rule,
-                                 const flsim_rule_weights* wts, float* p, float* m, float* v,
+static int net_server_step_crule(void* gradstate, float* S_out, float* theta_out,
+                                 const flsim_rule* rule, const flsim_rule_weights* wts,
+                                 const flsim_rule_comp* comp, float* p, float* m, float* v,
                                  long step, const flsim_optim* optim, hipStream_t stream) {
     RC(check_optim(optim));
     RC(check_weights(wts));
+    RC(check_comp(comp, rule));
+    const bool cform = comp != nullptr || theta_out != nullptr;
     const int nstate = optim_n_state(optim);
     FLSIM_REQUIRE(gradstate && rule && p && (m || nstate < 1) && (v || nstate < 2),
                   "null pointer");
@@ -256,8 +262,24 @@ static int net_server_step_wrule(void* gradstate, float* S_out, const flsim_rule
     RC(make_opt_launch(optim, wts ? wts->divisor : (double)rule->k, step, &ol));
     float w[STEP_MAX_WARR];
     if (wts) RC(make_weights(rule, wts, S_out, nullptr, w, STEP_MAX_WARR));
+    CompLaunch cl;
+    if (cform) {
+        FLSIM_REQUIRE(rule->n_arrays <= STEP_MAX_WARR, "NotImplementedError: compensated rule "
+                      "with %d arrays in this step (max %d)", rule->n_arrays, STEP_MAX_WARR);
+        if (!wts) unit_weights(rule->n_arrays, w);
+        RC(make_comp(rule, comp, nullptr, S_out, theta_out, p, STEP_MAX_CARR, &cl));
+    }
     return slab_step_launch_optim((float*)gradstate, N::plan(g, gradstate), g.cnt_off, g.part_off,
-                                  S_out, &R, ol, p, m, v, N::params(), stream, wts ? w : nullptr);
+                                  S_out, &R, ol, p, m, v, N::params(), stream,
+                                  (wts || cform) ? w : nullptr, cform ? &cl : nullptr);
+}
+
+template <class N>
+static int net_server_step_wrule(void* gradstate, float* S_out, const flsim_rule* rule,
+                                 const flsim_rule_weights* wts, float* p, float* m, float* v,
+                                 long step, const flsim_optim* optim, hipStream_t stream) {
+    return net_server_step_crule<N>(gradstate, S_out, nullptr, rule, wts, nullptr, p, m, v, step,
+                                    optim, stream);
 }
 
 template <class N>

@@ -1113,4 +1113,12 @@ int flsim_pn1_server_step_wrule(void* gradstate, float* S_out, const flsim_rule*
     return net_server_step_wrule<PN1>(gradstate, S_out, rule, wts, p, m, v, step, optim, stream);
 }
 
+int flsim_pn1_server_step_crule(void* gradstate, float* S_out, float* theta_out,
+                                const flsim_rule* rule, const flsim_rule_weights* wts,
+                                const flsim_rule_comp* comp, float* p, float* m, float* v,
+                                long step, const flsim_optim* optim, hipStream_t stream) {
+    return net_server_step_crule<PN1>(gradstate, S_out, theta_out, rule, wts, comp, p, m, v,
+                                      step, optim, stream);
+}
+
 }  // extern "C"

@@ -17,6 +17,10 @@
 // staleness-weighted rule sum_j w_j * entry_j / W with w = 1 for the S_t entries (a stale value is
 // multiplied by its array's fp32 weight where it is loaded, the same cascade sums the products,
 // one IEEE division follows); bit-exact with torch.stack([x * w ...]).sum(0) / W.
+// On top of the weighted form every rule-carrying kernel has a delay-compensated form (C): a stale
+// value with a snapshot theta_src is first corrected to x + ((x*x)*lam) * (p - theta_src) with the
+// p the kernel holds (compensate()), and a launch that writes S_out can write that pre-update p to
+// theta_out, the snapshot of the entry being pushed.
 //
 // Two kernels:
 //   k_agg_stream  S_t already in a buffer (after the all-reduce at world > 1, or the facade):
@@ -96,6 +100,16 @@ __device__ __forceinline__ float rule_div(const AdamConst& A, float s) {
     else return div_const(s, A.fk, A.rk);
 }
 
+// Delay compensation (DC-ASGD) of a stale value x pushed when the model was th and popped when it
+// is p (the pre-update parameter): x + ((x*x) * lam) * (p - th), five fp32 roundings in the rule
+// text's order (no contraction: -ffp-contract=off).  T = float or a float vector.
+template <class T>
+__host__ __device__ __forceinline__ T compensate(T x, T p, T th, float lam) {
+    const T h = (x * x) * lam;
+    const T d = p - th;
+    return x + h * d;
+}
+
 template <bool W = false>
 __device__ __forceinline__ void adam_elem(const AdamConst& A, float s, float& p, float& m,
                                           float& v) {
@@ -142,6 +156,9 @@ __device__ __forceinline__ void opt_elem(const AdamConst& A, const OptConst& X, 
 // multi_row_sum: the weighted kernels follow it (they are pinned to torch itself); the
 // unweighted ones keep the 32-column rule for every tensor, as the oracle states it (no
 // supported model has a tensor of 4 .. 7 elements, where the two differ).
+// The compensated kernels (C) exist in the weighted form only, which keeps the instantiation count
+// down; without a discount they run with weights 1.0 and the divisor k.  That is exact: x * 1.0f
+// is x, and the IEEE division by an integer k is what div_const gives.
 __host__ __device__ inline long rule_body(int numel, bool weighted) {
     return (weighted && numel < 8) ? (long)(numel / 4 * 4) : (long)(numel / 32) * 32;
 }
@@ -200,6 +217,8 @@ struct AggArgs {
     RuleProg R;
     OptConst oc;                    // after R: the OK_ADAM kernels' argument offsets stay as they were
     float w[RULE_MAX_ARR];          // weighted rule (W kernels only): the weight of R.arr[q]
+    float* theta_out;               // C kernels only, nullable: the pre-update p also written here
+    const float* snap[RULE_MAX_ARR];   // C kernels only: theta_src of R.arr[q]; nullptr = as it is
 };
 static_assert(sizeof(AggArgs) <= 4096, "kernel argument block");
 
@@ -230,8 +249,13 @@ __device__ __forceinline__ bool block_touch(const AggArgs& A, long blo, long spa
 // its array's weight once, where it is loaded (before the staging, and in the on-demand path); the
 // program then runs on the products as it runs on the values.  The multiply is a plain fp32
 // multiply (no contraction), a null array stays 0.
-template <bool INL, int OK = OK_ADAM, bool W = false>
+//
+// C (on W only): delay compensation.  The snapshot of a stale array is loaded with the array; once
+// p is there the value becomes compensate(value, p, snapshot) -- before its weight, so the staging
+// and the program see it as they see any weighted value.  theta_out receives the pre-update p.
+template <bool INL, int OK = OK_ADAM, bool W = false, bool C = false>
 __global__ void __launch_bounds__(256) k_agg_stream(AggArgs A) {
+    static_assert(W || !C, "the compensated form is built on the weighted one");
     constexpr bool HAS_M = opt_n_state(OK) >= 1, HAS_V = opt_n_state(OK) == 2;
     __shared__ f32x4 ys_lds[NYR * 256];
     const ProgRef<INL> prog{A.R};
@@ -243,9 +267,14 @@ __global__ void __launch_bounds__(256) k_agg_stream(AggArgs A) {
         float p = A.p[e], m = 0.f, v = 0.f;
         if constexpr (HAS_M) m = A.m[e];
         if constexpr (HAS_V) v = A.v[e];
+        const float p0 = p;             // the pre-update p (C)
         auto yf = [&](int q) -> float {
             if (!A.R.arr[q]) return 0.f;
-            if constexpr (W) return A.R.arr[q][e] * A.w[q];
+            if constexpr (C) {
+                float y = A.R.arr[q][e];
+                if (A.snap[q]) y = compensate(y, p0, A.snap[q][e], A.ac.lam);
+                return y * A.w[q];
+            } else if constexpr (W) return A.R.arr[q][e] * A.w[q];
             else return A.R.arr[q][e];
         };
         const CascVals<float> cv = casc_values(x, A.R.info.need, A.R.info.lp);
@@ -258,6 +287,9 @@ __global__ void __launch_bounds__(256) k_agg_stream(AggArgs A) {
         if constexpr (HAS_M) A.m[e] = m;
         if constexpr (HAS_V) A.v[e] = v;
         if (A.S_out) A.S_out[e] = x;
+        if constexpr (C) {
+            if (A.theta_out) A.theta_out[e] = p0;
+        }
         return;
     }
     const long e0 = 4 * (A.g0 + (long)(blockIdx.x - A.nedge) * 256) + 4 * tid;
@@ -273,7 +305,13 @@ __global__ void __launch_bounds__(256) k_agg_stream(AggArgs A) {
 #pragma unroll
     for (int q = 0; q < NYR; ++q)
         ys[q] = (q < nst && A.R.arr[q]) ? ld(A.R.arr[q] + e0) : f32x4{0.f, 0.f, 0.f, 0.f};
-    if constexpr (W) {
+    f32x4 ts[C ? NYR : 1];
+    if constexpr (C) {
+#pragma unroll
+        for (int q = 0; q < NYR; ++q)
+            ts[q] = (q < nst && A.R.arr[q] && A.snap[q]) ? ld(A.snap[q] + e0)
+                                                         : f32x4{0.f, 0.f, 0.f, 0.f};
+    } else if constexpr (W) {
 #pragma unroll
         for (int q = 0; q < NYR; ++q)
             if (q < nst) ys[q] = ys[q] * A.w[q];
@@ -282,13 +320,26 @@ __global__ void __launch_bounds__(256) k_agg_stream(AggArgs A) {
     f32x4 p = ld(A.p + e0), m = {0.f, 0.f, 0.f, 0.f}, v = m;
     if constexpr (HAS_M) m = ld(A.m + e0);
     if constexpr (HAS_V) v = ld(A.v + e0);
+    const f32x4 p0 = p;                 // the pre-update p (C)
+    if constexpr (C) {
+#pragma unroll
+        for (int q = 0; q < NYR; ++q)
+            if (q < nst) {
+                if (A.R.arr[q] && A.snap[q]) ys[q] = compensate(ys[q], p0, ts[q], A.ac.lam);
+                ys[q] = ys[q] * A.w[q];
+            }
+    }
 #pragma unroll
     for (int q = 0; q < NYR; ++q)
         if (q < nst) ys_lds[q * 256 + tid] = ys[q];
     auto yf = [&](int q) -> f32x4 {
         if (q < NYR) return ys_lds[q * 256 + tid];
         if (!A.R.arr[q]) return f32x4{0.f, 0.f, 0.f, 0.f};
-        if constexpr (W) return ld(A.R.arr[q] + e0) * A.w[q];
+        if constexpr (C) {
+            f32x4 y = ld(A.R.arr[q] + e0);
+            if (A.snap[q]) y = compensate(y, p0, ld(A.snap[q] + e0), A.ac.lam);
+            return y * A.w[q];
+        } else if constexpr (W) return ld(A.R.arr[q] + e0) * A.w[q];
         else return ld(A.R.arr[q] + e0);
     };
     const f32x4 sum = casc_run_macro<true>(
@@ -305,6 +356,9 @@ __global__ void __launch_bounds__(256) k_agg_stream(AggArgs A) {
     if constexpr (HAS_M) st(A.m + e0, m);
     if constexpr (HAS_V) st(A.v + e0, v);
     if (A.S_out) st(A.S_out + e0, x);
+    if constexpr (C) {
+        if (A.theta_out) st(A.theta_out + e0, p0);
+    }
 }
 
 // The reference-order stream with its few entry arrays (NY <= 2: the popped FIFO entries of the
@@ -321,8 +375,9 @@ struct AggVec<1> { typedef float T __attribute__((ext_vector_type(4))); };
 template <>
 struct AggVec<2> { typedef float T __attribute__((ext_vector_type(8))); };
 
-template <int G, int NY, int OK = OK_ADAM, bool W = false>
+template <int G, int NY, int OK = OK_ADAM, bool W = false, bool C = false>
 __global__ void __launch_bounds__(256) k_agg_stream_reg(AggArgs A) {
+    static_assert(W || !C, "the compensated form is built on the weighted one");
     constexpr bool HAS_M = opt_n_state(OK) >= 1, HAS_V = opt_n_state(OK) == 2;
     typedef typename AggVec<G>::T T;
     const ProgRef<true> prog{A.R};
@@ -334,9 +389,14 @@ __global__ void __launch_bounds__(256) k_agg_stream_reg(AggArgs A) {
         float p = A.p[e], m = 0.f, v = 0.f;
         if constexpr (HAS_M) m = A.m[e];
         if constexpr (HAS_V) v = A.v[e];
+        const float p0 = p;             // the pre-update p (C)
         auto yf = [&](int q) -> float {
             if (!A.R.arr[q]) return 0.f;
-            if constexpr (W) return A.R.arr[q][e] * A.w[q];
+            if constexpr (C) {
+                float y = A.R.arr[q][e];
+                if (A.snap[q]) y = compensate(y, p0, A.snap[q][e], A.ac.lam);
+                return y * A.w[q];
+            } else if constexpr (W) return A.R.arr[q][e] * A.w[q];
             else return A.R.arr[q][e];
         };
         const CascVals<float> cv = casc_values(x, A.R.info.need, A.R.info.lp);
@@ -349,6 +409,9 @@ __global__ void __launch_bounds__(256) k_agg_stream_reg(AggArgs A) {
         if constexpr (HAS_M) A.m[e] = m;
         if constexpr (HAS_V) A.v[e] = v;
         if (A.S_out) A.S_out[e] = x;
+        if constexpr (C) {
+            if (A.theta_out) A.theta_out[e] = p0;
+        }
         return;
     }
     const long b0 = 4 * (A.g0 + (long)(blockIdx.x - A.nedge) * 256 * G);   // block's first element
@@ -368,7 +431,15 @@ __global__ void __launch_bounds__(256) k_agg_stream_reg(AggArgs A) {
 #pragma unroll
         for (int j = 0; j < G; ++j)
             ys[q][j] = A.R.arr[q] ? ld(A.R.arr[q] + e[j]) : f32x4{0.f, 0.f, 0.f, 0.f};
-    if constexpr (W) {
+    f32x4 ts[C && NY > 0 ? NY : 1][G];
+    if constexpr (C) {
+#pragma unroll
+        for (int q = 0; q < NY; ++q)
+#pragma unroll
+            for (int j = 0; j < G; ++j)
+                ts[q][j] = (A.R.arr[q] && A.snap[q]) ? ld(A.snap[q] + e[j])
+                                                     : f32x4{0.f, 0.f, 0.f, 0.f};
+    } else if constexpr (W) {
 #pragma unroll
         for (int q = 0; q < NY; ++q)
 #pragma unroll
@@ -382,6 +453,16 @@ __global__ void __launch_bounds__(256) k_agg_stream_reg(AggArgs A) {
         else ms[j] = f32x4{0.f, 0.f, 0.f, 0.f};
         if constexpr (HAS_V) vs[j] = ld(A.v + e[j]);
         else vs[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    if constexpr (C) {                  // ps is still the pre-update p
+#pragma unroll
+        for (int q = 0; q < NY; ++q)
+#pragma unroll
+            for (int j = 0; j < G; ++j) {
+                if (A.R.arr[q] && A.snap[q])
+                    ys[q][j] = compensate(ys[q][j], ps[j], ts[q][j], A.ac.lam);
+                ys[q][j] = ys[q][j] * A.w[q];
+            }
     }
     auto widen = [](const f32x4 (&a)[G]) -> T {
         T t;
@@ -403,6 +484,9 @@ __global__ void __launch_bounds__(256) k_agg_stream_reg(AggArgs A) {
                                        yf);
 #pragma unroll
     for (int j = 0; j < G; ++j) {
+        if constexpr (C) {
+            if (A.theta_out) st(A.theta_out + e[j], ps[j]);
+        }
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             float pp = ps[j][u], mm = ms[j][u], vv = vs[j][u];
@@ -436,6 +520,8 @@ struct StepArgs {
     SlabSeg seg[STEP_MAX_SEG];
     OptConst oc;                    // after seg: the OK_ADAM kernels' argument offsets stay as they were
     float w[STEP_MAX_WARR];         // weighted rule (W kernels only): the weight of R.arr[q]
+    float* theta_out;               // C kernels only, nullable: the pre-update p also written here
+    // (C kernels: lambda is ac.lam, the snapshot of R.arr[q] is R.arr[STEP_SNAP0 + q]; slabstep.h)
 };
 static_assert(sizeof(StepArgs) <= 4096, "kernel argument block");
 
@@ -538,7 +624,7 @@ __device__ __forceinline__ bool col_to_param(const SlabSeg& g, long col, long& t
 // Identity-layout segments (the linear layers): tiles of 1024 elements, thread t owns the float4
 // column 4t; it sums its Z slab rows itself (small Z, four accumulators) and finishes with 16-B
 // parameter-side loads and stores; the parameter loads are issued before the slab reads.
-template <bool ADAM, bool INL, int OK, bool W>
+template <bool ADAM, bool INL, int OK, bool W, bool C>
 __device__ __forceinline__ void slab_step_wide(const StepArgs& A, const SlabSeg& g, int u, int ul,
                                                float* lds) {
     constexpr bool HAS_M = opt_n_state(OK) >= 1, HAS_V = opt_n_state(OK) == 2;
@@ -573,7 +659,13 @@ __device__ __forceinline__ void slab_step_wide(const StepArgs& A, const SlabSeg&
 #pragma unroll
             for (int q = 0; q < NYW; ++q)
                 ys[q] = (q < A.R.narr && A.R.arr[q]) ? ld(A.R.arr[q] + e) : f32x4{0.f, 0.f, 0.f, 0.f};
-            if constexpr (W) {
+            f32x4 ts[C ? NYW : 1];
+            if constexpr (C) {
+#pragma unroll
+                for (int q = 0; q < NYW; ++q)
+                    ts[q] = (q < A.R.narr && A.R.arr[q] && A.R.arr[STEP_SNAP0 + q])
+                                ? ld(A.R.arr[STEP_SNAP0 + q] + e) : f32x4{0.f, 0.f, 0.f, 0.f};
+            } else if constexpr (W) {
 #pragma unroll
                 for (int q = 0; q < NYW; ++q)
                     if (q < A.R.narr) ys[q] = ys[q] * A.w[q];
@@ -583,6 +675,15 @@ __device__ __forceinline__ void slab_step_wide(const StepArgs& A, const SlabSeg&
             else m = f32x4{0.f, 0.f, 0.f, 0.f};
             if constexpr (HAS_V) v = ld(A.v + e);
             else v = f32x4{0.f, 0.f, 0.f, 0.f};
+            if constexpr (C) {              // p is the pre-update p
+#pragma unroll
+                for (int q = 0; q < NYW; ++q)
+                    if (q < A.R.narr) {
+                        if (A.R.arr[q] && A.R.arr[STEP_SNAP0 + q])
+                            ys[q] = compensate(ys[q], p, ts[q], A.ac.lam);
+                        ys[q] = ys[q] * A.w[q];
+                    }
+            }
         };
         // reference order: the parameter side is loaded ahead of the slab rows (both round trips
         // overlap); general order: after them, so the registers are free during the reduction and
@@ -654,7 +755,11 @@ __device__ __forceinline__ void slab_step_wide(const StepArgs& A, const SlabSeg&
         }
         if (!valid) continue;
         if (A.S_out) *reinterpret_cast<f32x4*>(A.S_out + e) = a0;
+        if constexpr (C) {
+            if (A.theta_out) *reinterpret_cast<f32x4*>(A.theta_out + e) = p;
+        }
         if constexpr (ADAM) {
+            const f32x4 p0 = p;             // the pre-update p (C)
             auto yf = [&](int q) -> f32x4 {
                 // q is uniform: a scalar switch picks the register, no indexed access
                 static_assert(NYW == 8, "one case per register-held entry array");
@@ -669,7 +774,12 @@ __device__ __forceinline__ void slab_step_wide(const StepArgs& A, const SlabSeg&
                     case 7: return ys[7];
                     default:
                         if (!A.R.arr[q]) return f32x4{0.f, 0.f, 0.f, 0.f};
-                        if constexpr (W) return ld(A.R.arr[q] + e) * A.w[q];
+                        if constexpr (C) {
+                            f32x4 y = ld(A.R.arr[q] + e);
+                            if (A.R.arr[STEP_SNAP0 + q])
+                                y = compensate(y, p0, ld(A.R.arr[STEP_SNAP0 + q] + e), A.ac.lam);
+                            return y * A.w[q];
+                        } else if constexpr (W) return ld(A.R.arr[q] + e) * A.w[q];
                         else return ld(A.R.arr[q] + e);
                 }
             };
@@ -695,7 +805,7 @@ __device__ __forceinline__ void slab_step_wide(const StepArgs& A, const SlabSeg&
 // loads, whose cost does not depend on which XCD the last arriver sits on.  Each thread's
 // parameter-side loads (p, m, v, staged entry arrays) are issued before the slab reduction (whole
 // tiles) or together with the partial loads (split tiles), so the two memory round trips overlap.
-template <bool ADAM, bool INL, int OK, bool W>
+template <bool ADAM, bool INL, int OK, bool W, bool C>
 __device__ __forceinline__ void slab_step_body(const StepArgs& A, float* lds) {
     constexpr bool HAS_M = opt_n_state(OK) >= 1, HAS_V = opt_n_state(OK) == 2;
     const int tid = threadIdx.x;
@@ -721,7 +831,7 @@ __device__ __forceinline__ void slab_step_body(const StepArgs& A, float* lds) {
     const SlabSeg& g = A.seg[si];
     const int ul = u - g.unit0;
     if (g.wide) {
-        slab_step_wide<ADAM, INL, OK, W>(A, g, u, ul, lds);
+        slab_step_wide<ADAM, INL, OK, W, C>(A, g, u, ul, lds);
         return;
     }
     int tile, t_end, j;
@@ -749,7 +859,13 @@ __device__ __forceinline__ void slab_step_body(const StepArgs& A, float* lds) {
 #pragma unroll
             for (int q = 0; q < NYR; ++q)
                 ys[q] = (q < nst && A.R.arr[q]) ? A.R.arr[q][e] : 0.f;
-            if constexpr (W) {
+            float ts[C ? NYR : 1];
+            if constexpr (C) {
+#pragma unroll
+                for (int q = 0; q < NYR; ++q)
+                    ts[q] = (q < nst && A.R.arr[q] && A.R.arr[STEP_SNAP0 + q])
+                                ? A.R.arr[STEP_SNAP0 + q][e] : 0.f;
+            } else if constexpr (W) {
 #pragma unroll
                 for (int q = 0; q < NYR; ++q)
                     if (q < nst) ys[q] = ys[q] * A.w[q];
@@ -757,6 +873,15 @@ __device__ __forceinline__ void slab_step_body(const StepArgs& A, float* lds) {
             p = A.p[e];
             if constexpr (HAS_M) m = A.m[e];
             if constexpr (HAS_V) v = A.v[e];
+            if constexpr (C) {              // p is the pre-update p
+#pragma unroll
+                for (int q = 0; q < NYR; ++q)
+                    if (q < nst) {
+                        if (A.R.arr[q] && A.R.arr[STEP_SNAP0 + q])
+                            ys[q] = compensate(ys[q], p, ts[q], A.ac.lam);
+                        ys[q] = ys[q] * A.w[q];
+                    }
+            }
         };
         if (ADAM && valid && g.nz == 1) load_param_side();
         __syncthreads();                       // LDS reuse across the unit's tiles
@@ -807,6 +932,9 @@ __device__ __forceinline__ void slab_step_body(const StepArgs& A, float* lds) {
             // Tiles holding row_sum tail elements, or more arrays than NYR, take the per-element
             // path below.
             if (valid && A.S_out) A.S_out[e] = s;
+            if constexpr (C) {
+                if (valid && A.theta_out) A.theta_out[e] = p;
+            }
             const bool tail = valid && tl >= rule_body(g.numel, W);
             lds[L_S + tid] = valid ? s : 0.f;
             lds[L_P + tid] = p;
@@ -875,14 +1003,23 @@ __device__ __forceinline__ void slab_step_body(const StepArgs& A, float* lds) {
         }
         if (!valid) continue;
         if (A.S_out && (INL || !ADAM)) A.S_out[e] = s;
+        if constexpr (C && INL) {
+            if (A.theta_out) A.theta_out[e] = p;
+        }
         if constexpr (ADAM) {
+            const float p0 = p;             // the pre-update p (C)
 #pragma unroll
             for (int q = 0; q < NYR; ++q)
                 if (q < nst) lds[L_Y + q * 256 + tid] = ys[q];
             auto yf = [&](int q) -> float {
                 if (q < NYR) return lds[L_Y + q * 256 + tid];
                 if (!A.R.arr[q]) return 0.f;
-                if constexpr (W) return A.R.arr[q][e] * A.w[q];
+                if constexpr (C) {
+                    float y = A.R.arr[q][e];
+                    if (A.R.arr[STEP_SNAP0 + q])
+                        y = compensate(y, p0, A.R.arr[STEP_SNAP0 + q][e], A.ac.lam);
+                    return y * A.w[q];
+                } else if constexpr (W) return A.R.arr[q][e] * A.w[q];
                 else return A.R.arr[q][e];
             };
             const CascVals<float> cv = casc_values(s, A.R.info.need, A.R.info.lp);
@@ -898,10 +1035,11 @@ __device__ __forceinline__ void slab_step_body(const StepArgs& A, float* lds) {
     }
 }
 
-template <bool ADAM, bool INL, int OK = OK_ADAM, bool W = false>
+template <bool ADAM, bool INL, int OK = OK_ADAM, bool W = false, bool C = false>
 __global__ void __launch_bounds__(256) k_slab_step(StepArgs A) {
+    static_assert((W && ADAM) || !C, "the compensated form is built on the weighted one");
     __shared__ float lds[L_Y + NYR * 256];
-    slab_step_body<ADAM, INL, OK, W>(A, lds);
+    slab_step_body<ADAM, INL, OK, W, C>(A, lds);
 }
 
 // General-order programs: the interpreter's chains of dependent adds want many resident waves to
@@ -909,11 +1047,12 @@ __global__ void __launch_bounds__(256) k_slab_step(StepArgs A) {
 #ifndef SEQ_WAVES
 #define SEQ_WAVES 4
 #endif
-template <int OK = OK_ADAM, bool W = false>
+template <int OK = OK_ADAM, bool W = false, bool C = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SEQ_WAVES, 8)))
 k_slab_step_seq(StepArgs A) {
+    static_assert(W || !C, "the compensated form is built on the weighted one");
     __shared__ float lds[L_END];
-    slab_step_body<true, false, OK, W>(A, lds);
+    slab_step_body<true, false, OK, W, C>(A, lds);
 }
 
 // ================================================================================================
@@ -996,6 +1135,45 @@ int make_weights(const flsim_rule* r, const flsim_rule_weights* w, const float* 
                       "weight must be 1.0 (is %g)", q, w->w[q]);
         out[q] = (float)w->w[q];
     }
+    return 0;
+}
+
+// Delay compensation's lambda and array count; before any pointer check, like check_weights.
+// Negated comparisons: a NaN is refused too.
+int check_comp(const flsim_rule_comp* c, const flsim_rule* r) {
+    if (!c) return 0;
+    FLSIM_REQUIRE(c->lambda >= 0.0 && c->lambda <= 3.0e38, "Invalid delay compensation lambda %g",
+                  c->lambda);
+    FLSIM_REQUIRE(r, "null rule");
+    FLSIM_REQUIRE(c->n == r->n_arrays, "snapshots for %d arrays, the rule has %d", c->n,
+                  r->n_arrays);
+    return 0;
+}
+
+int make_comp(const flsim_rule* r, const flsim_rule_comp* comp, const float* S, const float* S_out,
+              float* theta_out, const float* p, int cap, CompLaunch* out) {
+    memset(out, 0, sizeof(*out));
+    out->theta_out = theta_out;
+    FLSIM_REQUIRE(((uintptr_t)theta_out & 15) == 0, "theta_out must be 16-byte aligned");
+    FLSIM_REQUIRE(!theta_out || theta_out != p, "theta_out aliases p");
+    if (!comp) return 0;
+    out->lam = (float)comp->lambda;                  // rounded to fp32 once
+    int n_comp = 0;
+    for (int q = 0; q < comp->n; ++q) {
+        const float* t = comp->theta_src[q];
+        if (!t) continue;
+        FLSIM_REQUIRE(((uintptr_t)t & 15) == 0, "snapshots must be 16-byte aligned");
+        const bool alias = r->arrays[q] && (r->arrays[q] == S || r->arrays[q] == S_out);
+        FLSIM_REQUIRE(!alias, "array %d is S_t itself: it takes no snapshot", q);
+        FLSIM_REQUIRE(t != theta_out, "theta_out aliases the snapshot of array %d", q);
+        out->snap[q] = t;
+        ++n_comp;
+        bool seen = false;
+        for (int s = 0; s < q && !seen; ++s) seen = comp->theta_src[s] == t;
+        out->nsnap += !seen;
+    }
+    FLSIM_REQUIRE(n_comp <= cap, "NotImplementedError: compensated rule with %d snapshots in this "
+                  "step (max %d)", n_comp, cap);
     return 0;
 }
 
@@ -1082,31 +1260,32 @@ int slab_step_launch(float* gradstate, const StepPlan& plan, long cnt_off, long 
 }
 
 // the fused step's two rule() + update launches of one kind
-template <int OK, bool W>
+template <int OK, bool W, bool C>
 static void launch_slab_rule(bool seq, unsigned nblk, hipStream_t stream, const ProbeSlot& ps,
                              const StepArgs& A) {
     if (!seq)
-        hipExtLaunchKernelGGL((k_slab_step<true, true, OK, W>), dim3(nblk), dim3(256), 0, stream,
+        hipExtLaunchKernelGGL((k_slab_step<true, true, OK, W, C>), dim3(nblk), dim3(256), 0, stream,
                               ps.start, ps.stop, 0, A);
     else
-        hipExtLaunchKernelGGL((k_slab_step_seq<OK, W>), dim3(nblk), dim3(256), 0, stream, ps.start,
-                              ps.stop, 0, A);
+        hipExtLaunchKernelGGL((k_slab_step_seq<OK, W, C>), dim3(nblk), dim3(256), 0, stream,
+                              ps.start, ps.stop, 0, A);
 }
 
-template <bool W>
+template <bool W, bool C = false>
 static void launch_slab_kind(int ok, bool seq, unsigned nblk, hipStream_t stream,
                              const ProbeSlot& ps, const StepArgs& A) {
     switch (ok) {
-        case OK_ADAM: launch_slab_rule<OK_ADAM, W>(seq, nblk, stream, ps, A); break;
-        case OK_ADAMD: launch_slab_rule<OK_ADAMD, W>(seq, nblk, stream, ps, A); break;
-        case OK_SGDM: launch_slab_rule<OK_SGDM, W>(seq, nblk, stream, ps, A); break;
-        default: launch_slab_rule<OK_SGD, W>(seq, nblk, stream, ps, A); break;
+        case OK_ADAM: launch_slab_rule<OK_ADAM, W, C>(seq, nblk, stream, ps, A); break;
+        case OK_ADAMD: launch_slab_rule<OK_ADAMD, W, C>(seq, nblk, stream, ps, A); break;
+        case OK_SGDM: launch_slab_rule<OK_SGDM, W, C>(seq, nblk, stream, ps, A); break;
+        default: launch_slab_rule<OK_SGD, W, C>(seq, nblk, stream, ps, A); break;
     }
 }
 
 int slab_step_launch_optim(float* gradstate, const StepPlan& plan, long cnt_off, long part_off,
                            float* S_out, const RuleProg* rule, const OptLaunch& ol, float* p,
-                           float* m, float* v, long P, hipStream_t stream, const float* weights) {
+                           float* m, float* v, long P, hipStream_t stream, const float* weights,
+                           const CompLaunch* comp) {
     const int nstate = opt_n_state(ol.ok);
     StepArgs A{};
     A.base = gradstate;
@@ -1127,6 +1306,12 @@ int slab_step_launch_optim(float* gradstate, const StepPlan& plan, long cnt_off,
         if (weights) {
             FLSIM_REQUIRE(rule->narr <= STEP_MAX_WARR, "weighted rule with %d arrays", rule->narr);
             for (int q = 0; q < rule->narr; ++q) A.w[q] = weights[q];
+        }
+        if (comp) {
+            FLSIM_REQUIRE(weights, "the compensated step is built on the weighted one");
+            A.ac.lam = comp->lam;
+            A.theta_out = comp->theta_out;
+            for (int q = 0; q < rule->narr; ++q) A.R.arr[STEP_SNAP0 + q] = comp->snap[q];
         }
     }
     // FLSIM_STEP_UNITS="lo,hi" (measurement only): run units [lo, hi) of the plan -- whole
@@ -1157,6 +1342,8 @@ int slab_step_launch_optim(float* gradstate, const StepPlan& plan, long cnt_off,
                      plan.seg[i].n;
     double bytes = 4.0 * slab_read + (S_out ? 4.0 * P : 0.0);
     if (rule) bytes += 4.0 * (double)P * (2 + 2 * nstate + rule->distinct);
+    // ... each distinct snapshot read once, theta_out written
+    if (rule && comp) bytes += 4.0 * (double)P * (comp->nsnap + (comp->theta_out ? 1 : 0));
     const ProbeSlot ps = probe_begin();
     if (!rule) {
         hipExtLaunchKernelGGL(k_slab_step<false, true>, dim3(nblk), dim3(256), 0, stream, ps.start,
@@ -1164,7 +1351,8 @@ int slab_step_launch_optim(float* gradstate, const StepPlan& plan, long cnt_off,
     } else {
         const bool seq = rule->prog != nullptr;
         if (seq) RC(stage_program(*rule, stream));
-        if (weights) launch_slab_kind<true>(ol.ok, seq, nblk, stream, ps, A);
+        if (comp) launch_slab_kind<true, true>(ol.ok, seq, nblk, stream, ps, A);
+        else if (weights) launch_slab_kind<true>(ol.ok, seq, nblk, stream, ps, A);
         else launch_slab_kind<false>(ol.ok, seq, nblk, stream, ps, A);
     }
     FLSIM_LAUNCH_CHECK();
@@ -1174,33 +1362,33 @@ int slab_step_launch_optim(float* gradstate, const StepPlan& plan, long cnt_off,
 
 // the streaming launch of one kind: the register-array form (reference order, <= 2 entry arrays,
 // G groups per thread) or the LDS-staged one (inline or staged program)
-template <int OK, bool W>
+template <int OK, bool W, bool C>
 static void launch_agg(bool reg, int G, dim3 grid, hipStream_t stream, const ProbeSlot& ps,
                        const AggArgs& A) {
     if (reg) {
-        auto k = G == 2 ? (A.R.narr == 0 ? k_agg_stream_reg<2, 0, OK, W>
-                           : A.R.narr == 1 ? k_agg_stream_reg<2, 1, OK, W>
-                                           : k_agg_stream_reg<2, 2, OK, W>)
-                        : (A.R.narr == 0 ? k_agg_stream_reg<1, 0, OK, W>
-                           : A.R.narr == 1 ? k_agg_stream_reg<1, 1, OK, W>
-                                           : k_agg_stream_reg<1, 2, OK, W>);
+        auto k = G == 2 ? (A.R.narr == 0 ? k_agg_stream_reg<2, 0, OK, W, C>
+                           : A.R.narr == 1 ? k_agg_stream_reg<2, 1, OK, W, C>
+                                           : k_agg_stream_reg<2, 2, OK, W, C>)
+                        : (A.R.narr == 0 ? k_agg_stream_reg<1, 0, OK, W, C>
+                           : A.R.narr == 1 ? k_agg_stream_reg<1, 1, OK, W, C>
+                                           : k_agg_stream_reg<1, 2, OK, W, C>);
         hipExtLaunchKernelGGL(k, grid, dim3(256), 0, stream, ps.start, ps.stop, 0, A);
     } else if (A.R.prog == nullptr)
-        hipExtLaunchKernelGGL((k_agg_stream<true, OK, W>), grid, dim3(256), 0, stream, ps.start,
+        hipExtLaunchKernelGGL((k_agg_stream<true, OK, W, C>), grid, dim3(256), 0, stream, ps.start,
                               ps.stop, 0, A);
     else
-        hipExtLaunchKernelGGL((k_agg_stream<false, OK, W>), grid, dim3(256), 0, stream, ps.start,
-                              ps.stop, 0, A);
+        hipExtLaunchKernelGGL((k_agg_stream<false, OK, W, C>), grid, dim3(256), 0, stream,
+                              ps.start, ps.stop, 0, A);
 }
 
-template <bool W>
+template <bool W, bool C = false>
 static void launch_agg_kind(int ok, bool reg, int G, dim3 grid, hipStream_t stream,
                             const ProbeSlot& ps, const AggArgs& A) {
     switch (ok) {
-        case OK_ADAM: launch_agg<OK_ADAM, W>(reg, G, grid, stream, ps, A); break;
-        case OK_ADAMD: launch_agg<OK_ADAMD, W>(reg, G, grid, stream, ps, A); break;
-        case OK_SGDM: launch_agg<OK_SGDM, W>(reg, G, grid, stream, ps, A); break;
-        default: launch_agg<OK_SGD, W>(reg, G, grid, stream, ps, A); break;
+        case OK_ADAM: launch_agg<OK_ADAM, W, C>(reg, G, grid, stream, ps, A); break;
+        case OK_ADAMD: launch_agg<OK_ADAMD, W, C>(reg, G, grid, stream, ps, A); break;
+        case OK_SGDM: launch_agg<OK_SGDM, W, C>(reg, G, grid, stream, ps, A); break;
+        default: launch_agg<OK_SGD, W, C>(reg, G, grid, stream, ps, A); break;
     }
 }
 
@@ -1247,8 +1435,22 @@ int flsim_aggregate_optim_wrule_push(const float* S, float* S_out, const flsim_r
                                      const flsim_rule_weights* wts, float* p, float* m, float* v,
                                      long P, const long* tensor_sizes, int n_tensors, long step,
                                      const flsim_optim* optim, hipStream_t stream) {
+    return flsim_aggregate_optim_crule_push(S, S_out, nullptr, rule, wts, nullptr, p, m, v, P,
+                                            tensor_sizes, n_tensors, step, optim, stream);
+}
+
+// the same with delay compensation (include/flsim.h): comp->theta_src[q] (nullable) is the
+// snapshot of arrays[q]; theta_out (nullable) receives the pre-update p in the same pass.  Either
+// one selects the C kernels, which run in the weighted form (wts == NULL: weights 1.0, divisor k)
+int flsim_aggregate_optim_crule_push(const float* S, float* S_out, float* theta_out,
+                                     const flsim_rule* rule, const flsim_rule_weights* wts,
+                                     const flsim_rule_comp* comp, float* p, float* m, float* v,
+                                     long P, const long* tensor_sizes, int n_tensors, long step,
+                                     const flsim_optim* optim, hipStream_t stream) {
     RC(check_optim(optim));
     RC(check_weights(wts));
+    RC(check_comp(comp, rule));
+    const bool cform = comp != nullptr || theta_out != nullptr;
     const int nstate = optim_n_state(optim);
     FLSIM_REQUIRE(S && p && (m || nstate < 1) && (v || nstate < 2) && tensor_sizes && rule,
                   "null pointer");
@@ -1267,6 +1469,16 @@ int flsim_aggregate_optim_wrule_push(const float* S, float* S_out, const flsim_r
     A.ac = ol.ac;
     A.oc = ol.oc;
     if (wts) RC(make_weights(rule, wts, S, S_out, A.w, RULE_MAX_ARR));
+    else if (cform) unit_weights(A.R.narr, A.w);
+    int nsnap = 0;
+    if (cform) {
+        CompLaunch cl;
+        RC(make_comp(rule, comp, S, S_out, theta_out, p, RULE_MAX_ARR, &cl));
+        A.ac.lam = cl.lam;
+        A.theta_out = cl.theta_out;
+        for (int q = 0; q < A.R.narr; ++q) A.snap[q] = cl.snap[q];
+        nsnap = cl.nsnap;
+    }
     // the register-array stream for the reference order with <= 2 entry arrays: 2 float4 groups
     // per thread without a stale array, 1 with (tools/agg_bench.py, profiles/r03a/agg_bench.txt:
     // 28.2 vs 28.4 us for k = 512; 32.0 vs 33.1 us for k = 513 with the stale S_{t-d});
@@ -1296,7 +1508,7 @@ int flsim_aggregate_optim_wrule_push(const float* S, float* S_out, const flsim_r
         long hi = lo;
         while (t < n_tensors) {
             const long n = tensor_sizes[t];
-            const long body = rule_body((int)n, wts != nullptr);
+            const long body = rule_body((int)n, wts != nullptr || cform);
             const bool tail = body != n;
             if (tail && A.ntail == MAX_TAILS) break;
             if (tail) {
@@ -1335,11 +1547,13 @@ int flsim_aggregate_optim_wrule_push(const float* S, float* S_out, const flsim_r
         // algorithmic HBM bytes: read S_t + the distinct entry arrays + p and the kind's state
         // arrays (m, v: 2, 1 or 0 of them); write p and the state arrays [+ S_out]
         const double bytes =
-            4.0 * (double)(hi - lo) * (3 + 2 * nstate + A.R.distinct + (S_out ? 1 : 0));
+            4.0 * (double)(hi - lo) * (3 + 2 * nstate + A.R.distinct + (S_out ? 1 : 0) + nsnap +
+                                       (theta_out ? 1 : 0));
         const ProbeSlot ps = probe_begin();
         const dim3 grid((unsigned)(nblk + A.nedge));
         if (!reg && A.R.prog != nullptr) RC(stage_program(A.R, stream));
-        if (wts) launch_agg_kind<true>(ol.ok, reg, G, grid, stream, ps, A);
+        if (cform) launch_agg_kind<true, true>(ol.ok, reg, G, grid, stream, ps, A);
+        else if (wts) launch_agg_kind<true>(ol.ok, reg, G, grid, stream, ps, A);
         else launch_agg_kind<false>(ol.ok, reg, G, grid, stream, ps, A);
         FLSIM_LAUNCH_CHECK();
         if (probe_end(ps, A.R.prog == nullptr ? K_AGG : K_AGG_SEQ, bytes)) return 2;
@@ -1404,9 +1618,11 @@ int flsim_cascade_program(int k, const int32_t* pos, const int32_t* arr, int n_e
 // host interpreter of a macro program (testing): out[e] = the cascade sum of element e, x = S[e],
 // entry arrays ys[q][e]; tail[e] != 0 selects the row_sum program.  wf (nullable): entry array q
 // enters as ys[q][e] * wf[q]; fdiv != 0: out[e] = sum / fdiv.
+// theta_now / theta_src / lam (nullable): the C kernels' compensation in front of the weight.
 static void eval_host(const int32_t* prog, const int32_t* info, const float* S,
                       const float* const* ys, const float* wf, int n_arrays, float fdiv,
-                      const uint8_t* tail, long n, float* out) {
+                      const uint8_t* tail, long n, float* out, const float* theta_now = nullptr,
+                      const float* const* theta_src = nullptr, float lam = 0.f) {
     struct HostPairs {
         const int32_t* w;
         uint32_t lo(int i) const { return (uint32_t)w[2 * i]; }
@@ -1416,7 +1632,9 @@ static void eval_host(const int32_t* prog, const int32_t* info, const float* S,
         const CascVals<float> cv = casc_values(S[e], info[2], info[3]);
         auto yf = [&](int q) -> float {
             if (!(q < n_arrays && ys[q])) return 0.f;
-            return wf ? ys[q][e] * wf[q] : ys[q][e];
+            float y = ys[q][e];
+            if (theta_src && theta_src[q]) y = compensate(y, theta_now[e], theta_src[q][e], lam);
+            return wf ? y * wf[q] : y;
         };
         const float s = casc_run_macro(hp, (tail && tail[e]) ? info[1] : 0, cv, yf);
         out[e] = fdiv != 0.f ? s / fdiv : s;
@@ -1450,6 +1668,34 @@ int flsim_cascade_eval_host_w(const int32_t* prog, const int32_t* info, const fl
     float wf[RULE_MAX_ARR];
     for (int q = 0; q < n_arrays; ++q) wf[q] = (float)w[q];
     eval_host(prog, info, S, ys, wf, n_arrays, ac.fk, tail, n, out);
+    return 0;
+}
+
+// the compensated twin of the C kernels (testing): flsim_cascade_eval_host_w with
+// compensate(ys[q][e], theta_now[e], theta_src[q][e], (float)lambda) in front of the weight for
+// every array with a snapshot; w == NULL: weights 1.0.  lambda is refused as the entry points
+// refuse it.
+int flsim_cascade_eval_host_c(const int32_t* prog, const int32_t* info, const float* S,
+                              const float* const* ys, const double* w, int n_arrays,
+                              double divisor, const float* theta_now,
+                              const float* const* theta_src, double lambda, const uint8_t* tail,
+                              long n, float* out) {
+    FLSIM_REQUIRE(n_arrays >= 0 && n_arrays <= RULE_MAX_ARR, "n_arrays = %d", n_arrays);
+    flsim_rule_weights rw{};
+    rw.n = n_arrays;
+    for (int q = 0; q < n_arrays; ++q) rw.w[q] = w ? w[q] : 1.0;
+    rw.divisor = divisor;
+    RC(check_weights(&rw));
+    FLSIM_REQUIRE(lambda >= 0.0 && lambda <= 3.0e38, "Invalid delay compensation lambda %g",
+                  lambda);
+    FLSIM_REQUIRE(prog && info && S && out && (ys || n_arrays == 0) && (theta_now || !theta_src),
+                  "null pointer");
+    AdamConst ac;
+    RC(make_divisor(divisor, &ac));
+    float wf[RULE_MAX_ARR];
+    for (int q = 0; q < n_arrays; ++q) wf[q] = (float)rw.w[q];
+    eval_host(prog, info, S, ys, wf, n_arrays, ac.fk, tail, n, out, theta_now, theta_src,
+              (float)lambda);
     return 0;
 }
 

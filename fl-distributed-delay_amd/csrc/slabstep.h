@@ -28,6 +28,14 @@ constexpr int RULE_INL_PROG = 192;    // program words carried in the kernel arg
 // arrays of a weighted rule in the fused step: its argument block (the segments take 2.5 KB of the
 // 4 KB) has room for this many weights; the streaming step carries RULE_MAX_ARR
 constexpr int STEP_MAX_WARR = 16;
+// Delay compensation (the C kernels): the fused step takes a snapshot for each of its (at most
+// STEP_MAX_WARR) arrays.  Its argument block has 8 bytes left, which theta_out takes, so the
+// snapshot of R.arr[q] rides in the unused upper part of R.arr, at R.arr[STEP_SNAP0 + q]; the
+// streaming step carries RULE_MAX_ARR snapshots in a field of its own.
+constexpr int STEP_MAX_CARR = 16;
+constexpr int STEP_SNAP0 = 32;
+static_assert(STEP_MAX_CARR <= STEP_MAX_WARR && STEP_SNAP0 >= STEP_MAX_WARR &&
+              STEP_SNAP0 + STEP_MAX_CARR <= RULE_MAX_ARR, "snapshots in the free part of R.arr");
 constexpr long STEP_UNIT_FLOATS = 65536;
 
 // host description of one parameter tensor's gradient slabs (offsets in floats)
@@ -134,6 +142,8 @@ inline int plan_step(const SegSpec* s_in, int nseg, StepPlan* P) {
 // Adam hyper-parameters + rule() divisor, prepared on the host (agents.py:9-21, main.py:106)
 struct AdamConst {
     float w1, b2, w2, bc2s, rbc2s, eps, neg_ss, fk, rk;
+    float lam;      // delay compensation's lambda (C kernels only); sits in what was padding, so
+                    // no argument offset of the other kernels moves
 };
 
 // The update rule a launch applies (compile-time: the kinds differ in the arrays they stream).
@@ -187,10 +197,19 @@ struct OptLaunch {
 // the same with a chosen update rule; m / v may be null where the kind does not own them
 // weights (nullable): the staleness-weighted rule, weights[q] (fp32) of rule->arr[q], at most
 // STEP_MAX_WARR arrays; ol's divisor is then the weighted rule's
+// comp (nullable): the delay-compensated step (on top of the weighted form: weights must be given);
+// comp->snap[q] (nullable) = the snapshot of rule->arr[q], comp->theta_out (nullable) receives the
+// pre-update p, comp->lam = f32(lambda)
+struct CompLaunch {
+    float lam;
+    float* theta_out;
+    const float* snap[RULE_MAX_ARR];
+    int nsnap;                      // distinct non-null snapshots (algorithmic bytes)
+};
 int slab_step_launch_optim(float* gradstate, const StepPlan& plan, long cnt_off, long part_off,
                            float* S_out, const RuleProg* rule, const OptLaunch& ol, float* p,
                            float* m, float* v, long P, hipStream_t stream,
-                           const float* weights = nullptr);
+                           const float* weights = nullptr, const CompLaunch* comp = nullptr);
 
 // host helpers shared with server.hip's C-ABI
 int make_rule(const flsim_rule* r, RuleProg* out);
@@ -204,6 +223,17 @@ int check_weights(const flsim_rule_weights* w);
 // the weights in launch form (fp32); alias0 / alias1: buffers that are S_t (their weight must be 1)
 int make_weights(const flsim_rule* r, const flsim_rule_weights* w, const float* alias0,
                  const float* alias1, float* out, int cap);
+// delay compensation (include/flsim.h): lambda and the array count, before any pointer check
+int check_comp(const flsim_rule_comp* c, const flsim_rule* r);
+// the compensation in launch form.  S / S_out: the buffers that are S_t (never compensated); p:
+// the parameters (theta_out must not alias them, nor a snapshot); cap: compensated arrays the step
+// takes.  comp == nullptr: no snapshots (theta_out only)
+int make_comp(const flsim_rule* r, const flsim_rule_comp* comp, const float* S, const float* S_out,
+              float* theta_out, const float* p, int cap, CompLaunch* out);
+// unit weights for a compensated rule without a discount (the C kernels exist in the weighted form)
+inline void unit_weights(int n, float* w) {
+    for (int q = 0; q < n; ++q) w[q] = 1.f;
+}
 inline flsim_optim adam_optim(double lr, double beta1, double beta2, double eps) {
     flsim_optim o{};
     o.kind = FLSIM_OPT_ADAM;

@@ -616,6 +616,14 @@ int flsim_vgg11_server_step_wrule(void* gradstate, float* S_out, const flsim_rul
     return net_server_step_wrule<V11>(gradstate, S_out, rule, wts, p, m, v, step, optim, stream);
 }
 
+int flsim_vgg11_server_step_crule(void* gradstate, float* S_out, float* theta_out,
+                                  const flsim_rule* rule, const flsim_rule_weights* wts,
+                                  const flsim_rule_comp* comp, float* p, float* m, float* v,
+                                  long step, const flsim_optim* optim, hipStream_t stream) {
+    return net_server_step_crule<V11>(gradstate, S_out, theta_out, rule, wts, comp, p, m, v,
+                                      step, optim, stream);
+}
+
 // ---- vgg11_bn -------------------------------------------------------------------------------
 long flsim_vgg11_bn_param_count(void) { return voff(true).total; }
 
@@ -695,6 +703,14 @@ int flsim_vgg11_bn_server_step_wrule(void* gradstate, float* S_out, const flsim_
                                      long step, const flsim_optim* optim, hipStream_t stream) {
     return net_server_step_wrule<V11BN>(gradstate, S_out, rule, wts, p, m, v, step, optim,
                                         stream);
+}
+
+int flsim_vgg11_bn_server_step_crule(void* gradstate, float* S_out, float* theta_out,
+                                     const flsim_rule* rule, const flsim_rule_weights* wts,
+                                     const flsim_rule_comp* comp, float* p, float* m, float* v,
+                                     long step, const flsim_optim* optim, hipStream_t stream) {
+    return net_server_step_crule<V11BN>(gradstate, S_out, theta_out, rule, wts, comp, p, m, v,
+                                        step, optim, stream);
 }
 
 int flsim_vgg11_bn_update_running(float* running, const float* bn_stats, int n_workers,

@@ -46,6 +46,9 @@ EXPORTS = [
     "flsim_aggregate_optim_wrule_push", "flsim_pn1_server_step_wrule",
     "flsim_vgg11_server_step_wrule", "flsim_vgg11_bn_server_step_wrule",
     "flsim_cascade_eval_host_w",
+    "flsim_aggregate_optim_crule_push", "flsim_pn1_server_step_crule",
+    "flsim_vgg11_server_step_crule", "flsim_vgg11_bn_server_step_crule",
+    "flsim_cascade_eval_host_c",
 ]
 COMM_ID_BYTES = 128      # FLSIM_COMM_ID_BYTES
 
@@ -68,6 +71,13 @@ class FlsimRuleWeights(ctypes.Structure):
     """flsim_rule_weights (include/flsim.h): the weights of a rule's arrays and its divisor."""
     _fields_ = [("n", ctypes.c_int32), ("w", ctypes.c_double * MAX_ARRAYS),
                 ("divisor", ctypes.c_double)]
+
+
+class FlsimRuleComp(ctypes.Structure):
+    """flsim_rule_comp (include/flsim.h): delay compensation's lambda and the snapshot of each of
+    a rule's arrays (NULL: not compensated)."""
+    _fields_ = [("n", ctypes.c_int32), ("lam", ctypes.c_double),
+                ("theta_src", ctypes.c_void_p * MAX_ARRAYS)]
 
 
 OPT_KINDS = {"adam": 0, "adamw": 1, "sgd": 2}      # FLSIM_OPT_ADAM / _ADAMW / _SGD
@@ -127,6 +137,8 @@ def lib():
                                      ctypes.c_double, ctypes.c_double, ctypes.c_double, vp]
         f("server_step_optim").argtypes = [vp, vp, vp, vp, vp, vp, ctypes.c_long, vp, vp]
         f("server_step_wrule").argtypes = [vp, vp, vp, vp, vp, vp, vp, ctypes.c_long, vp, vp]
+        f("server_step_crule").argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, ctypes.c_long, vp,
+                                           vp]
         f("eval_pool").argtypes = [vp, vp, ctypes.c_int, vp, vp, ctypes.c_int, ctypes.c_int,
                                    vp] + bn + [vp, vp]
     L.flsim_pn1_workspace_split_part.argtypes = [ctypes.c_int]
@@ -178,6 +190,10 @@ def lib():
         vp, vp, vp, vp, vp, vp, vp, ctypes.c_long, vp, ctypes.c_int, ctypes.c_long, vp, vp]
     L.flsim_cascade_eval_host_w.argtypes = [vp, vp, vp, vp, vp, ctypes.c_int, ctypes.c_double, vp,
                                             ctypes.c_long, vp]
+    L.flsim_aggregate_optim_crule_push.argtypes = [
+        vp, vp, vp, vp, vp, vp, vp, vp, vp, ctypes.c_long, vp, ctypes.c_int, ctypes.c_long, vp, vp]
+    L.flsim_cascade_eval_host_c.argtypes = [vp, vp, vp, vp, vp, ctypes.c_int, ctypes.c_double, vp,
+                                            vp, ctypes.c_double, vp, ctypes.c_long, vp]
     L.flsim_cascade_program.argtypes = [ctypes.c_int, vp, vp, ctypes.c_int, vp, ctypes.c_int, vp]
     L.flsim_cascade_eval_host.argtypes = [vp, vp, vp, vp, ctypes.c_int, vp, ctypes.c_long, vp]
     L.flsim_probe_enable.argtypes = [ctypes.c_int]

@@ -20,8 +20,8 @@ import torch
 
 import math
 
-from ._lib import (MAX_ARRAYS, OPT_KINDS, FlsimOptim, FlsimRule, FlsimRuleWeights, WorkerRec, check,
-                   lib, ptr, stream_ptr)
+from ._lib import (MAX_ARRAYS, OPT_KINDS, FlsimOptim, FlsimRule, FlsimRuleComp, FlsimRuleWeights,
+                   WorkerRec, check, lib, ptr, stream_ptr)
 
 # named_parameters() order of models.py:PerformantNet1 (models.py:13-25)
 PN1_SHAPES = [
@@ -314,12 +314,22 @@ class NetEngine:
         check(self._fn("end_epoch")(ptr(self.gradstate), ptr(grad_out), stream_ptr()))
 
     def server_step(self, S_out, rule, theta, m, v, step, lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
-                    optim=None):
+                    optim=None, theta_out=None):
         """world = 1: the epoch's slabs -> S_t [-> S_out] -> rule() + Adam in one launch
         (flsim_<net>_server_step).  rule: a Rule.  optim (an Optim or a dict of its fields): that
         update rule instead (flsim_<net>_server_step_optim); m / v may be None where the kind
         owns no such array.  A rule with weights runs the staleness-weighted step
-        (flsim_<net>_server_step_wrule)."""
+        (flsim_<net>_server_step_wrule).  A rule with snapshots, or theta_out (the pre-update
+        theta is also written there: the snapshot of the entry pushed into S_out), runs the
+        delay-compensated step (flsim_<net>_server_step_crule)."""
+        if rule.c_comp is not None or theta_out is not None:
+            o = (as_optim(optim) if optim is not None else
+                 Optim(lr=lr, betas=tuple(betas), eps=eps)).c_struct()
+            check(self._fn("server_step_crule")(
+                ptr(self.gradstate), ptr(S_out), ptr(theta_out), ctypes.byref(rule.c_rule),
+                _byref(rule.c_weights), _byref(rule.c_comp), ptr(theta), ptr(m), ptr(v),
+                int(step), ctypes.byref(o), stream_ptr()))
+            return
         if rule.c_weights is not None:
             o = (as_optim(optim) if optim is not None else
                  Optim(lr=lr, betas=tuple(betas), eps=eps)).c_struct()
@@ -396,11 +406,12 @@ class NetEngine:
         aggregate_adam_sum(S, k, theta, m, v, step, self.SIZES, lr, betas, eps, optim=optim)
 
     def aggregate_rule(self, S, rule, theta, m, v, step, lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
-                       S_out=None, optim=None):
+                       S_out=None, optim=None, theta_out=None):
         """rule() + Adam (or the update rule `optim`) from S_t in a buffer; S_out (optional): S_t
-        is also written there in the same pass (the FIFO slot of a tick epoch at world > 1)."""
+        is also written there in the same pass (the FIFO slot of a tick epoch at world > 1);
+        theta_out (optional): so is the pre-update theta (that slot's snapshot)."""
         aggregate_rule(S, rule, theta, m, v, step, self.SIZES, lr, betas, eps, S_out=S_out,
-                       optim=optim)
+                       optim=optim, theta_out=theta_out)
 
 
 class PN1Engine(NetEngine):
@@ -579,12 +590,29 @@ class Rule:
     weights (one Python float per array; None = the plain mean) make it the staleness-weighted
     rule sum_j w_j * entry_j / divisor with w = 1.0 for every S_t entry: divisor defaults to the
     sum of all k weights ("weights" normalisation; pass k for "count").  A weight must be finite
-    and >= 0 (ValueError), the divisor > 0 (ZeroDivisionError)."""
+    and >= 0 (ValueError), the divisor > 0 (ZeroDivisionError).
+
+    snapshots (one device tensor or None per array) with delay_comp = lambda make it the
+    delay-compensated rule (DC-ASGD): array j enters as x + (x * x) * lambda * (theta_now -
+    snapshots[j]) with theta_now the parameters before the step; None leaves an array as it
+    stands.  Compensation comes before the weight.  lambda must be finite and >= 0 (ValueError).
+    An entry is S_src, a sum over that epoch's workers, so x * x grows with the square of the
+    worker count: choose lambda with that in mind."""
 
     def __init__(self, k, arrays=(), c=None, events=None, stager=None, weights=None,
-                 divisor=None):
+                 divisor=None, snapshots=None, delay_comp=None):
         arrays = list(arrays)
         self.weights, self.divisor, self.c_weights = None, None, None
+        self.snapshots, self.delay_comp, self.c_comp = None, None, None
+        if snapshots is not None or delay_comp is not None:
+            snapshots = [None] * len(arrays) if snapshots is None else list(snapshots)
+            if len(snapshots) != len(arrays):
+                raise ValueError(f"{len(snapshots)} snapshots for {len(arrays)} arrays")
+            lam = 0.0 if delay_comp is None else float(delay_comp)
+            if not (lam >= 0 and math.isfinite(lam)):
+                raise ValueError(f"Invalid delay compensation lambda {lam}: it must be finite "
+                                 "and >= 0")
+            self.snapshots, self.delay_comp = snapshots, lam
         if weights is None and divisor is not None:
             weights = [1.0] * len(arrays)
         if weights is not None:
@@ -639,6 +667,13 @@ class Rule:
                 cw.w[q] = w
             cw.divisor = self.divisor
             self.c_weights = cw
+        if self.snapshots is not None and len(arrays) <= MAX_ARRAYS:
+            cc = FlsimRuleComp()
+            cc.n = len(arrays)
+            cc.lam = self.delay_comp
+            for q, t in enumerate(self.snapshots):      # (the rule keeps the tensors alive)
+                cc.theta_src[q] = t.data_ptr() if t is not None else None
+            self.c_comp = cc
 
 
 def staleness_weight(spec):
@@ -697,13 +732,27 @@ class ProgramStager:
         return self.dev[j]
 
 
+def _byref(struct):
+    return ctypes.byref(struct) if struct is not None else None
+
+
 def aggregate_rule(S, rule, theta, m, v, step, sizes, lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
-                   S_out=None, optim=None):
+                   S_out=None, optim=None, theta_out=None):
     """rule() + Adam from S_t in a buffer (flsim_aggregate_adam_rule_push; S_out may be None).
     optim (an Optim or a dict of its fields): that update rule instead of Adam(lr, betas, eps)
     (flsim_aggregate_optim_rule_push); m / v may be None where the kind owns no such array (SGD:
     v; SGD without momentum: m and v) and are left untouched when given."""
     csz = (ctypes.c_long * len(sizes))(*[int(n) for n in sizes])
+    if rule.c_comp is not None or theta_out is not None:
+        # the delay-compensated rule (rule.snapshots) and / or the snapshot write (theta_out: the
+        # pre-update theta, in the same pass)
+        o = (as_optim(optim) if optim is not None else
+             Optim(lr=lr, betas=tuple(betas), eps=eps)).c_struct()
+        check(lib().flsim_aggregate_optim_crule_push(
+            ptr(S), ptr(S_out), ptr(theta_out), ctypes.byref(rule.c_rule), _byref(rule.c_weights),
+            _byref(rule.c_comp), ptr(theta), ptr(m), ptr(v), sum(int(n) for n in sizes), csz,
+            len(sizes), int(step), ctypes.byref(o), stream_ptr()))
+        return
     if rule.c_weights is not None:      # the staleness-weighted rule
         o = (as_optim(optim) if optim is not None else
              Optim(lr=lr, betas=tuple(betas), eps=eps)).c_struct()

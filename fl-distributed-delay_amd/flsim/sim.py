@@ -20,6 +20,12 @@ stale_weight (None, ("poly", a), ("hinge", a, b), ("const", a) or a callable tau
 a popped FIFO entry by its age tau = t - (the epoch it was pushed) before the average (FedAsync's
 alternative to the throttle): rule() becomes sum_j w_j * entry_j / W, w = 1.0 for every S_t entry,
 W = the sum of the weights (stale_normalize="weights") or the entry count ("count").
+
+delay_comp (None or lambda >= 0) compensates a popped FIFO entry for the distance the model has
+moved since the entry was pushed (DC-ASGD, Zheng et al. 2017), before any discount: x becomes
+x + (x * x) * lambda * (theta_t - theta_src).  Every pushed slot carries the theta it was pushed
+at; the server step writes that snapshot in its own pass.  An entry is S_src, a sum over that
+epoch's workers, so x * x grows with the square of the worker count: choose lambda accordingly.
 """
 from __future__ import annotations
 
@@ -34,7 +40,9 @@ from .engine import (PN1_SIZES, Optim, ProgramStager, Rule, engine_class, padded
 from .schedule import Schedule, reference_delays
 
 SEMANTICS = ("reference", "torch1", "independent")
-STEP_MAX_WARR = 16      # arrays of a weighted rule the fused step takes (csrc/slabstep.h)
+# arrays of a weighted or compensated rule the fused step takes (csrc/slabstep.h: STEP_MAX_WARR,
+# STEP_MAX_CARR)
+STEP_MAX_WARR = 16
 # checkpoint format: 2 records the model, the optimizer hyper-parameters and the throttle cap, and
 # the reference's --delay 0 slow worker as DELAY_ZERO (restore() migrates format 1)
 CKPT_FORMAT = "flsim-checkpoint-2"
@@ -69,9 +77,20 @@ class FLSimulation:
                  engine=None, device_pool=None, test_pool=None, model="PerformantNet1",
                  fused=True, keep_S=False, batch_size=128, distributed=None,
                  collective="torch", optimizer="adam", weight_decay=0.0, momentum=0.0,
-                 dampening=0.0, nesterov=False, stale_weight=None, stale_normalize="weights"):
+                 dampening=0.0, nesterov=False, stale_weight=None, stale_normalize="weights",
+                 delay_comp=None):
         if semantics not in SEMANTICS:
             raise NotImplementedError(f"semantics {semantics!r} (supported: {SEMANTICS})")
+        # delay compensation's lambda (None: off); theta is replicated, so at world > 1 every rank
+        # keeps the same snapshots locally
+        self.delay_comp = None if delay_comp is None else float(delay_comp)
+        if self.delay_comp is not None:
+            if not (self.delay_comp >= 0 and np.isfinite(self.delay_comp)):
+                raise ValueError(f"Invalid delay compensation lambda {self.delay_comp}: it must "
+                                 "be finite and >= 0")
+            if semantics == "independent":
+                # its popped slots are added with a torch add_ before the all-reduce: another path
+                raise NotImplementedError("independent entries with delay compensation")
         # the discount of a popped entry's age; a replicated host computation (every rank derives
         # the same weights from the schedule)
         if stale_normalize not in ("weights", "count"):
@@ -187,7 +206,9 @@ class FLSimulation:
         self.comm = torch.zeros(self.stats_off + self.n * self.nstat, device=self.device)
         self._stager = ProgramStager(self.device)
         self.stale_store = {}     # epoch -> [slot tensor, refcount]
+        self.stale_theta = {}     # epoch -> the slot's theta snapshot (delay_comp only)
         self.free_slots = []
+        self.free_snaps = []
         self.trace = []
         self.loss_log = []        # per epoch: float (synced) or (device tensor, fast mask)
         self._test_src = test_pool  # (imgs, labels) of the test split, or None = synthetic
@@ -210,6 +231,11 @@ class FLSimulation:
         slot = torch.empty(n, device=self.device)
         slot[self.P:].zero_()     # the [P, Ppad) padding and the tail enter the all-reduce
         return slot
+
+    def _snap(self):
+        """A theta snapshot buffer for a pushed slot (delay_comp); recycled with the slot."""
+        return self.free_snaps.pop() if self.free_snaps else \
+            torch.empty(self.Ppad, device=self.device)
 
     def _worker_table(self, t, workers, ks):
         """WorkerRec (t, i, k, 0) of this rank's computing workers, copied host->device from a
@@ -283,12 +309,16 @@ class FLSimulation:
         k = plan.c_t + plan.s_t
         order = self._entry_order(plan)
         ws = self._entry_weights(plan)      # per popped entry, or None: the plain mean
+        # delay compensation: the snapshot of every popped entry (None: as it stands -- a zero
+        # entry, or this epoch's own S_t, for which theta has not moved)
+        snaps = self._entry_snapshots(plan)
         if order is None:       # reference order: c_t copies of S_t, then the stale entries
+            ckw = {} if snaps is None else dict(snapshots=snaps, delay_comp=self.delay_comp)
             if ws is None:
-                return Rule(k, stale, c=plan.c_t)
+                return Rule(k, stale, c=plan.c_t, **ckw)
             full = [1.0] * plan.c_t + ws
-            return Rule(k, stale, c=plan.c_t, **self._weighted(k, full, ws))
-        uniq, ev, uw = [], [], []
+            return Rule(k, stale, c=plan.c_t, **self._weighted(k, full, ws), **ckw)
+        uniq, ev, uw, usn = [], [], [], []
         for j0, (pos, a) in enumerate(zip(order[0], stale)):
             # entries of one source epoch share an array, and their age, hence their weight (the
             # torch-1.x zero entries share one null array: a zero stays zero under any weight,
@@ -297,15 +327,27 @@ class FLSimulation:
             if j is None:
                 uniq.append(a)
                 uw.append(None if ws is None else ws[j0])
+                usn.append(None if snaps is None else snaps[j0])   # ... and their snapshot
                 j = len(uniq) - 1
             ev.append((pos, j))
         arrays = uniq
+        ckw = {} if snaps is None else dict(snapshots=usn, delay_comp=self.delay_comp)
         if ws is None:
-            return Rule(k, arrays, events=ev, stager=self._stager)
+            return Rule(k, arrays, events=ev, stager=self._stager, **ckw)
         full = [1.0] * k
         for (pos, _), w in zip(ev, ws):
             full[pos] = w
-        return Rule(k, arrays, events=ev, stager=self._stager, **self._weighted(k, full, uw))
+        return Rule(k, arrays, events=ev, stager=self._stager, **self._weighted(k, full, uw),
+                    **ckw)
+
+    def _entry_snapshots(self, plan):
+        """theta_src of every popped FIFO entry in append order (None for an entry that is not
+        compensated); None when the epoch's rule carries no compensation at all."""
+        if self.delay_comp is None or self.semantics != "reference" or not plan.stale:
+            return None
+        snaps = [None if int(src) == int(plan.t) else self.stale_theta[src]
+                 for (_, src) in plan.stale]
+        return None if all(x is None for x in snaps) else snaps
 
     def _entry_weights(self, plan):
         """s(tau) of every popped FIFO entry in append order, tau = t - (the epoch it was
@@ -367,8 +409,10 @@ class FLSimulation:
         eng = self.engine
         G = self.G                               # 128-sample groups (units) per worker-step
         fused = self.fused and not self.distributed and hasattr(eng, "server_step")
-        # (a weighted rule over more arrays than the fused step takes: reduce, then stream)
-        keep_S = self.keep_S or (fused and self._stale_fn is not None and
+        # (a weighted or compensated rule over more arrays than the fused step takes: reduce, then
+        # stream)
+        keep_S = self.keep_S or (fused and
+                                 (self._stale_fn is not None or self.delay_comp is not None) and
                                  len({int(src) for (_, src) in plan.stale}) > STEP_MAX_WARR)
         pushes = plan.pushed and self.semantics == "reference"
         # An epoch that pushes S_t onto the FIFO and ends with the streaming server step (world > 1,
@@ -410,15 +454,22 @@ class FLSimulation:
             self._all_reduce(comm[:end])
         if self.nstat:   # BatchNorm running buffers: every computing worker's call, in order
             eng.update_running(stats, len(active))
-        push = None
+        push = snap = None
         if pushes:
             n_push = int(sum(1 for i in range(self.n) if self.delays[i] != 0 and plan.computes[i]))
             push = comm if in_slot else self._slot()
+            if self.delay_comp is not None:
+                snap = self._snap()
             if fused and keep_S:
                 push[:self.P].copy_(S)
-            # otherwise the server step writes S_t into the slot in its own pass: the fused
-            # slab step (world = 1) or the stream after the all-reduce (world > 1)
+                if snap is not None:
+                    snap[:self.P].copy_(self.theta)
+            # otherwise the server step writes S_t into the slot (and theta_t into its snapshot)
+            # in its own pass: the fused slab step (world = 1) or the stream after the
+            # all-reduce (world > 1)
             self.stale_store[t] = [push, n_push]
+            if snap is not None:
+                self.stale_theta[t] = snap
         stale = []
         for (_, src) in plan.stale:
             if self.semantics == "reference":
@@ -431,6 +482,8 @@ class FLSimulation:
         hp = dict(lr=self.lr, betas=self.betas, eps=self.eps)
         if self._optim_arg is not None:
             hp = dict(optim=self._optim_arg)
+        if snap is not None and not (fused and keep_S):
+            hp["theta_out"] = snap
         if fused and not keep_S:
             eng.server_step(push, rule, self.theta, self.m, self.v, self.step, **hp)
         elif fused:
@@ -444,6 +497,8 @@ class FLSimulation:
                 entry[1] -= 1
                 if entry[1] == 0:
                     self.free_slots.append(entry[0])
+                    if src in self.stale_theta:
+                        self.free_snaps.append(self.stale_theta.pop(src))
                     del self.stale_store[src]
         fast_pos = np.nonzero(plan.fast[active])[0]
         self.trace.append(plan)
@@ -608,6 +663,9 @@ class FLSimulation:
             **{k: a.detach().cpu() for k, a in (("m", self.m), ("v", self.v)) if a is not None},
             "stale": {int(src): (slot[:self.P].detach().cpu(), int(rc))
                       for src, (slot, rc) in self.stale_store.items()},
+            # delay compensation: the theta snapshot of every live slot
+            "stale_theta": {int(src): snap[:self.P].detach().cpu()
+                            for src, snap in self.stale_theta.items()},
             "loss_log": [float(x) for x in self.losses()],
             "buffers": dict(getattr(self.engine, "buffer_state", list)()),
         }
@@ -626,7 +684,8 @@ class FLSimulation:
                                       "can be recorded and checked at restore")
         spec = None if self.stale_weight is None else \
             [self.stale_weight[0]] + [float(x) for x in self.stale_weight[1:]]
-        return {"stale_weight": spec, "stale_normalize": self.stale_normalize}
+        return {"stale_weight": spec, "stale_normalize": self.stale_normalize,
+                "delay_comp": self.delay_comp}
 
     def save_checkpoint(self, path):
         torch.save(self.checkpoint(), path)
@@ -649,7 +708,9 @@ class FLSimulation:
         for k, v in (("optimizer", "adam"), ("weight_decay", 0.0), ("momentum", 0.0),
                      ("dampening", 0.0), ("nesterov", False),
                      # ... and from before the staleness discount: none
-                     ("stale_weight", None), ("stale_normalize", "weights")):
+                     ("stale_weight", None), ("stale_normalize", "weights"),
+                     # ... and from before delay compensation: off
+                     ("delay_comp", None)):
             cfg.setdefault(k, v)
         delays = cfg["delays"].numpy().astype(np.int32)
         if fmt == "flsim-checkpoint-1":
@@ -685,6 +746,12 @@ class FLSimulation:
             slot = self._slot()
             slot[:self.P].copy_(vals.to(self.device))
             self.stale_store[int(src)] = [slot, int(rc)]
+        self.stale_theta = {}
+        if self.delay_comp is not None:
+            for src, vals in ck["stale_theta"].items():
+                snap = self._snap()
+                snap[:self.P].copy_(vals.to(self.device))
+                self.stale_theta[int(src)] = snap
         self.loss_log = list(ck["loss_log"])
         if ck.get("buffers"):
             self.engine.load_buffers(ck["buffers"])

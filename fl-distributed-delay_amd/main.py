@@ -4,8 +4,10 @@ Same flags and defaults (main.py:38-53): --n_workers --n_epochs --batch_size --l
 --delay --model_file --throttle.  --optimizer {adam,adamw,sgd} with --momentum --dampening
 --nesterov --weight_decay picks the central optimizer (main.py:106 hard-wires Adam(lr)).
 --stale_weight {none,poly,hinge,const} with --stale_a --stale_b --stale_normalize discounts a stale
-entry by its age before the average (the alternative to --throttle).  The training loop (main.py:126-188) runs as flsim.sim
-.FLSimulation: host schedule, worker-batched HIP forward/backward, fused rule()+Adam; with
+entry by its age before the average (the alternative to --throttle).  --delay_comp LAMBDA
+compensates a stale entry for the distance the model has moved since it was computed (DC-ASGD).
+The training loop (main.py:126-188) runs as flsim.sim.FLSimulation: host schedule,
+worker-batched HIP forward/backward, fused rule()+Adam; with
 `torchrun --nproc-per-node N` the computing workers are sharded over N GPUs with one RCCL
 all-reduce per epoch.  'Avg. Loss' per epoch (main.py:185) goes to --log (JSONL; tensorboard is
 not installed) and stdout.
@@ -57,6 +59,11 @@ def parse(argv=None):
     p.add_argument('--stale_b', type=float, default=0.0, help='b of --stale_weight hinge')
     p.add_argument('--stale_normalize', default='weights', choices=['weights', 'count'],
                    help='divide the weighted sum by the sum of the weights or the entry count')
+    p.add_argument('--delay_comp', type=float, default=None, metavar='LAMBDA',
+                   help='delay compensation (DC-ASGD): a stale entry x becomes x + x*x*LAMBDA*'
+                        '(theta_now - theta_then) before the average (default: off).  An entry '
+                        'is the SUM of its epoch\'s worker gradients, so x*x grows with the '
+                        'square of the worker count: choose LAMBDA with that in mind')
     p.add_argument('--seed', type=int, default=0)
     p.add_argument('--semantics', default='reference', choices=['reference', 'torch1', 'independent'],
                    help='stale entry = S_{t-d} (torch>=2 aliasing), zeros (torch 1.x) or the slow '
@@ -117,7 +124,8 @@ def main(argv=None):
                        batch_size=args.batch_size, optimizer=args.optimizer,
                        weight_decay=args.weight_decay, momentum=args.momentum,
                        dampening=args.dampening, nesterov=args.nesterov,
-                       stale_weight=stale_spec(args), stale_normalize=args.stale_normalize)
+                       stale_weight=stale_spec(args), stale_normalize=args.stale_normalize,
+                       delay_comp=args.delay_comp)
     if buffers:
         sim.engine.load_buffers(buffers)
     if args.resume:

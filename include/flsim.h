@@ -437,6 +437,65 @@ int flsim_cascade_eval_host_w(const int32_t* prog, const int32_t* info, const fl
                               double divisor, const uint8_t* tail, long n, float* out);
 
 /* ---------------------------------------------------------------------------------------------
+ * Delay-compensated rule (DC-ASGD, Zheng et al. 2017): a popped FIFO entry x = S_src, pushed when
+ * the model was theta_src and popped when it is theta_now, is corrected for the distance the model
+ * has moved before it enters the average.  These entry points run
+ *
+ *   def compensate(x, theta_now, theta_src, lam):          # per parameter tensor, fp32
+ *       return x + (x * x) * lam * (theta_now - theta_src)
+ *   def compensated_rule(ups_list, snaps, theta_now, lam, weights=None, normalize="weights"):
+ *       ys = [u if s is None else [compensate(u[i], theta_now[i], s[i], lam) ...]
+ *             for u, s in zip(ups_list, snaps)]
+ *       return rule(ys) if weights is None else weighted_rule(ys, weights, normalize)
+ *
+ * fused with the update, bit-exact with torch 2.10 CPU: five fp32 roundings per element (x*x,
+ * times f32(lambda), theta_now - theta_src, their product, the add), no contraction; lambda is
+ * rounded to fp32 once; theta_now is p before this step's update.  Compensation comes first, then
+ * the staleness weight (wts; NULL: none), the cascade sum and the division.  comp->theta_src[q] is
+ * the snapshot of arrays[q]; NULL leaves that array as it stands, and a NULL array stays zero.  An
+ * entry that is S_t is never compensated.  theta_out (nullable, 16-byte aligned): the pre-update p
+ * is also written there in the same pass -- the snapshot of the entry a tick pushes into S_out.
+ * comp == NULL and theta_out == NULL is the weighted entry point above.
+ * Note: under the reference's aliasing an entry is S_src, a sum over that epoch's workers, so
+ * x * x grows with the square of the worker count; lambda has to be chosen with that in mind.
+ * Checked before any pointer, status 1: a lambda that is not finite and >= 0; comp->n !=
+ * rule->n_arrays.  Then: a snapshot for an array that is the S or S_out buffer; theta_out aliasing
+ * p or a snapshot read in the same launch; a fused step with more than 16 arrays (message
+ * "NotImplementedError: ..."; the streaming step takes all 64).
+ * ------------------------------------------------------------------------------------------- */
+typedef struct flsim_rule_comp {
+    int32_t n;                                /* == rule->n_arrays */
+    double lambda;                            /* rounded to fp32 once; finite, >= 0 */
+    const float* theta_src[FLSIM_MAX_ARRAYS]; /* snapshot of arrays[q]; NULL = not compensated */
+} flsim_rule_comp;
+
+int flsim_aggregate_optim_crule_push(const float* S, float* S_out, float* theta_out,
+                                     const flsim_rule* rule, const flsim_rule_weights* wts,
+                                     const flsim_rule_comp* comp, float* p, float* m, float* v,
+                                     long P, const long* tensor_sizes, int n_tensors, long step,
+                                     const flsim_optim* optim, flsim_stream_t stream);
+int flsim_pn1_server_step_crule(void* gradstate, float* S_out, float* theta_out,
+                                const flsim_rule* rule, const flsim_rule_weights* wts,
+                                const flsim_rule_comp* comp, float* p, float* m, float* v,
+                                long step, const flsim_optim* optim, flsim_stream_t stream);
+int flsim_vgg11_server_step_crule(void* gradstate, float* S_out, float* theta_out,
+                                  const flsim_rule* rule, const flsim_rule_weights* wts,
+                                  const flsim_rule_comp* comp, float* p, float* m, float* v,
+                                  long step, const flsim_optim* optim, flsim_stream_t stream);
+int flsim_vgg11_bn_server_step_crule(void* gradstate, float* S_out, float* theta_out,
+                                     const flsim_rule* rule, const flsim_rule_weights* wts,
+                                     const flsim_rule_comp* comp, float* p, float* m, float* v,
+                                     long step, const flsim_optim* optim, flsim_stream_t stream);
+/* host (testing): flsim_cascade_eval_host_w with the compensation in front: entry array q with a
+ * snapshot theta_src[q] enters as compensate(ys[q][e], theta_now[e], theta_src[q][e], lambda),
+ * then times (float)w[q] (w == NULL: 1.0).  theta_src == NULL: no array is compensated. */
+int flsim_cascade_eval_host_c(const int32_t* prog, const int32_t* info, const float* S,
+                              const float* const* ys, const double* w, int n_arrays,
+                              double divisor, const float* theta_now,
+                              const float* const* theta_src, double lambda, const uint8_t* tail,
+                              long n, float* out);
+
+/* ---------------------------------------------------------------------------------------------
  * Measurement (no reference counterpart): HIP events around every worker-batched GEMM launch on
  * its stream, for bench.py's live roofline figure.  read() fills flsim_probe_kernel_count()
  * entries per kernel id (launches, total ms, total algorithmic FLOPs) and resets the record.
