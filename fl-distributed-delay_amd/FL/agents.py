@@ -53,8 +53,8 @@ import weakref
 import numpy as np
 import torch
 
-from flsim.engine import (Optim, ProgramStager, Rule, engine_for_parameters, padded, split_views,
-                          worker_table)
+from flsim.engine import (Clip, Optim, ProgramStager, Rule, engine_for_parameters, padded,
+                          split_views, worker_table)
 
 _CONTEXTS = weakref.WeakKeyDictionary()    # model -> _ModelContext (dies with the model)
 _NEXT_WORKER = [0]                          # Worker.index of the next Worker()
@@ -491,11 +491,16 @@ def compensated_rule(ups_list, snaps, lam, weights=None, normalize="weights"):
 
 
 class Central:
-    """agents.py:4-24."""
+    """agents.py:4-24.  clip_grad_norm (None or max_norm > 0): update_model clips the aggregated
+    gradient's global 2-norm between installing it and the optimizer step, what
+    torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm) would do there; total_norm then
+    holds the step's norm (a 0-d device tensor, the engine's correctly rounded one)."""
 
-    def __init__(self, model, optim, encryption=False):
+    def __init__(self, model, optim, encryption=False, clip_grad_norm=None):
         self.model = model
         self.optim = optim
+        self.clip = None if clip_grad_norm is None else Clip(clip_grad_norm)
+        self.total_norm = None
         g = optim.param_groups[0]
         if not isinstance(optim, (torch.optim.Adam, torch.optim.SGD)) or \
                 len(optim.param_groups) != 1 or g.get("amsgrad", False) or \
@@ -607,7 +612,7 @@ class Central:
         else:
             hp = dict(optim=o)
         if isinstance(ups, _LazyMean) and ctx.G is not None and ctx.carry is None and \
-                not ctx.touched and hasattr(eng, "server_step") and \
+                not ctx.touched and hasattr(eng, "server_step") and self.clip is None and \
                 not ((r.c_weights is not None or r.c_comp is not None) and len(r.arrays) > 16):
             # fused: this epoch's slabs -> S_t (also written into G, which the FIFO entries of
             # main.py:156,161 alias) -> rule() + Adam, one pass
@@ -616,7 +621,11 @@ class Central:
             ctx.dirty = False
         else:
             ctx.flush()
+            if self.clip is not None:       # the clipped streaming step (three launches)
+                hp["clip"] = self.clip
             eng.aggregate_rule(S, r, ctx.theta, ctx.m, ctx.v, ctx.step, **hp)
+            if self.clip is not None:
+                self.total_norm = self.clip.total_norm
         for p in self.model.parameters():        # optim.zero_grad() (set_to_none, torch >= 2)
             p.grad = None
         self._sync_optimizer_state(o)

@@ -21,6 +21,10 @@
 // value with a snapshot theta_src is first corrected to x + ((x*x)*lam) * (p - theta_src) with the
 // p the kernel holds (compensate()), and a launch that writes S_out can write that pre-update p to
 // theta_out, the snapshot of the entry being pushed.
+// Global-norm clipping (torch.nn.utils.clip_grad_norm_ between `.grad = ...` and optim.step())
+// runs as three launches: the stream in a fifth kind, OK_GOUT, stores g = rule() to G and one fp64
+// sum of squares per block; k_clip_finish adds those in index order and writes the correctly
+// rounded norm and torch's coefficient; k_clip_apply runs the update on g * coef.
 //
 // Two kernels:
 //   k_agg_stream  S_t already in a buffer (after the all-reduce at world > 1, or the facade):
@@ -126,27 +130,45 @@ __device__ __forceinline__ void adam_elem(const AdamConst& A, float s, float& p,
 //                         p = fma(g, -lr, p)
 // The flags are launch-uniform (scalar branches).  m is SGD's momentum buffer; a kind never
 // touches an argument it does not own (the callers pass dummies).
+// opt_update: the update for a gradient g (what follows rule()'s division; the clipped step's
+// k_clip_apply enters here with g * coef); opt_elem: rule()'s division, then the update.
+template <int OK>
+__device__ __forceinline__ void opt_update(const AdamConst& A, const OptConst& X, float g,
+                                           float& p, float& m, float& v) {
+    if constexpr (OK == OK_ADAM) {
+        adam_update(A, g, p, m, v);
+    } else if constexpr (OK == OK_ADAMD) {
+        if (X.flags & OF_DECOUPLED) p = p * X.wd;
+        else g = __fmaf_rn(p, X.wd, g);
+        adam_update(A, g, p, m, v);
+    } else {
+        if (X.flags & OF_WD) g = __fmaf_rn(p, X.wd, g);
+        if constexpr (OK == OK_SGDM) {
+            const float buf = (X.flags & OF_FIRST) ? g : __fmaf_rn(g, X.omd, m * X.mu);
+            g = (X.flags & OF_NESTEROV) ? __fmaf_rn(buf, X.mu, g) : buf;
+            m = buf;
+        }
+        p = __fmaf_rn(g, X.neg_lr, p);
+    }
+}
+
 template <int OK, bool W = false>
 __device__ __forceinline__ void opt_elem(const AdamConst& A, const OptConst& X, float s, float& p,
                                          float& m, float& v) {
-    if constexpr (OK == OK_ADAM) {
-        adam_elem<W>(A, s, p, m, v);
-    } else {
-        float g = rule_div<W>(A, s);                        // rule(): mean = sum / k
-        if constexpr (OK == OK_ADAMD) {
-            if (X.flags & OF_DECOUPLED) p = p * X.wd;
-            else g = __fmaf_rn(p, X.wd, g);
-            adam_update(A, g, p, m, v);
-        } else {
-            if (X.flags & OF_WD) g = __fmaf_rn(p, X.wd, g);
-            if constexpr (OK == OK_SGDM) {
-                const float buf = (X.flags & OF_FIRST) ? g : __fmaf_rn(g, X.omd, m * X.mu);
-                g = (X.flags & OF_NESTEROV) ? __fmaf_rn(buf, X.mu, g) : buf;
-                m = buf;
-            }
-            p = __fmaf_rn(g, X.neg_lr, p);
-        }
-    }
+    static_assert(OK != OK_GOUT, "OK_GOUT has no update (gout_store)");
+    opt_update<OK>(A, X, rule_div<W>(A, s), p, m, v);      // rule(): mean = sum / k
+}
+
+// Deterministic block sum (256 threads) of one double per thread: the 64 lanes of a wave by a
+// butterfly (every lane adds the same pairs: one result in all lanes), then the four waves as
+// (w0 + w1) + (w2 + w3) through red[4] in LDS.  Every thread of the block must call it (one
+// barrier); every thread gets the sum.
+__device__ __forceinline__ double block_sum_f64(double a, double* red) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = a;
+    __syncthreads();
+    return (red[0] + red[1]) + (red[2] + red[3]);
 }
 
 // The leading elements of a tensor of `numel` elements that rule()'s sum takes as multi_row_sum
@@ -219,8 +241,28 @@ struct AggArgs {
     float w[RULE_MAX_ARR];          // weighted rule (W kernels only): the weight of R.arr[q]
     float* theta_out;               // C kernels only, nullable: the pre-update p also written here
     const float* snap[RULE_MAX_ARR];   // C kernels only: theta_src of R.arr[q]; nullptr = as it is
+    float* G;                       // OK_GOUT kernels only: g = rule() is stored here
+    double* partials;               // OK_GOUT kernels only: block b's sum of g * g (fp64) goes to
+    long part0;                     //   partials[part0 + b]
 };
 static_assert(sizeof(AggArgs) <= 4096, "kernel argument block");
+
+// OK_GOUT: the block's sum of squares, one double per block (every thread of the block calls).
+// k_agg_stream_reg has no LDS of its own: the four wave sums get 32 B here.  k_agg_stream lends
+// the head of its staging array (one more barrier first: wave 0 may still be reading it), so its
+// 32 KB per block stay 32 KB and five blocks still fit a CU.
+__device__ __forceinline__ void gout_block(const AggArgs& A, double sq, double* red) {
+    const double t = block_sum_f64(sq, red);
+    if (threadIdx.x == 0) A.partials[A.part0 + blockIdx.x] = t;
+}
+__device__ __forceinline__ void gout_block(const AggArgs& A, double sq) {
+    __shared__ double red[4];
+    gout_block(A, sq, red);
+}
+__device__ __forceinline__ void gout_block_lent(const AggArgs& A, double sq, f32x4* staging) {
+    __syncthreads();
+    gout_block(A, sq, reinterpret_cast<double*>(staging));
+}
 
 __device__ __forceinline__ bool in_tail(const AggArgs& A, long e) {
     bool r = false;
@@ -261,10 +303,17 @@ __global__ void __launch_bounds__(256) k_agg_stream(AggArgs A) {
     const ProgRef<INL> prog{A.R};
     const int tid = threadIdx.x;
     if ((int)blockIdx.x < A.nedge) {
-        const long e = A.edge_lo[blockIdx.x] + tid;
-        if (e < A.lo || e >= A.hi) return;
+        long e = A.edge_lo[blockIdx.x] + tid;
+        bool live = true;
+        if constexpr (OK == OK_GOUT) {
+            // every thread stays for the block's sum: one out of range works on element lo and
+            // stores nothing
+            live = e >= A.lo && e < A.hi;
+            if (!live) e = A.lo;
+        } else if (e < A.lo || e >= A.hi) return;
         const float x = A.S[e];
-        float p = A.p[e], m = 0.f, v = 0.f;
+        float p = 0.f, m = 0.f, v = 0.f;
+        if constexpr (OK != OK_GOUT || C) p = A.p[e];
         if constexpr (HAS_M) m = A.m[e];
         if constexpr (HAS_V) v = A.v[e];
         const float p0 = p;             // the pre-update p (C)
@@ -282,8 +331,21 @@ __global__ void __launch_bounds__(256) k_agg_stream(AggArgs A) {
         float s = 0.f;
         if (!tail) s = casc_run_macro(prog, 0, cv, yf);
         if (tail) s = casc_run_macro(prog, A.R.info.tail_off, cv, yf);
-        opt_elem<OK, W>(A.ac, A.oc, s, p, m, v);
-        A.p[e] = p;
+        if constexpr (OK == OK_GOUT) {
+            const float g = rule_div<W>(A.ac, s);
+            if (live) {
+                A.G[e] = g;
+                if (A.S_out) A.S_out[e] = x;
+                if constexpr (C) {
+                    if (A.theta_out) A.theta_out[e] = p0;
+                }
+            }
+            gout_block_lent(A, live ? (double)g * (double)g : 0.0, ys_lds);
+            return;
+        } else {
+            opt_elem<OK, W>(A.ac, A.oc, s, p, m, v);
+            A.p[e] = p;
+        }
         if constexpr (HAS_M) A.m[e] = m;
         if constexpr (HAS_V) A.v[e] = v;
         if (A.S_out) A.S_out[e] = x;
@@ -293,7 +355,12 @@ __global__ void __launch_bounds__(256) k_agg_stream(AggArgs A) {
         return;
     }
     const long e0 = 4 * (A.g0 + (long)(blockIdx.x - A.nedge) * 256) + 4 * tid;
-    if (block_touch(A, e0 - 4 * tid)) return;
+    if (block_touch(A, e0 - 4 * tid)) {
+        if constexpr (OK == OK_GOUT) {
+            if (tid == 0) A.partials[A.part0 + blockIdx.x] = 0.0;      // its edge pieces hold the sum
+        }
+        return;
+    }
     auto ld = [](const float* ptr) -> f32x4 {
         return __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(ptr));
     };
@@ -317,7 +384,8 @@ __global__ void __launch_bounds__(256) k_agg_stream(AggArgs A) {
             if (q < nst) ys[q] = ys[q] * A.w[q];
     }
     const f32x4 x = ld(A.S + e0);
-    f32x4 p = ld(A.p + e0), m = {0.f, 0.f, 0.f, 0.f}, v = m;
+    f32x4 p = {0.f, 0.f, 0.f, 0.f}, m = p, v = p;
+    if constexpr (OK != OK_GOUT || C) p = ld(A.p + e0);
     if constexpr (HAS_M) m = ld(A.m + e0);
     if constexpr (HAS_V) v = ld(A.v + e0);
     const f32x4 p0 = p;                 // the pre-update p (C)
@@ -344,15 +412,27 @@ __global__ void __launch_bounds__(256) k_agg_stream(AggArgs A) {
     };
     const f32x4 sum = casc_run_macro<true>(
         prog, 0, casc_values(x, A.R.info.need, A.R.info.lp), yf);
+    if constexpr (OK == OK_GOUT) {
+        f32x4 g;
+        double sq = 0.0;
 #pragma unroll
-    for (int u = 0; u < 4; ++u) {
-        float pp = p[u], mm = m[u], vv = v[u];
-        opt_elem<OK, W>(A.ac, A.oc, sum[u], pp, mm, vv);
-        p[u] = pp;
-        m[u] = mm;
-        v[u] = vv;
+        for (int u = 0; u < 4; ++u) {
+            g[u] = rule_div<W>(A.ac, sum[u]);
+            sq += (double)g[u] * (double)g[u];
+        }
+        st(A.G + e0, g);
+        gout_block_lent(A, sq, ys_lds);
+    } else {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            float pp = p[u], mm = m[u], vv = v[u];
+            opt_elem<OK, W>(A.ac, A.oc, sum[u], pp, mm, vv);
+            p[u] = pp;
+            m[u] = mm;
+            v[u] = vv;
+        }
+        st(A.p + e0, p);
     }
-    st(A.p + e0, p);
     if constexpr (HAS_M) st(A.m + e0, m);
     if constexpr (HAS_V) st(A.v + e0, v);
     if (A.S_out) st(A.S_out + e0, x);
@@ -383,10 +463,17 @@ __global__ void __launch_bounds__(256) k_agg_stream_reg(AggArgs A) {
     const ProgRef<true> prog{A.R};
     const int tid = threadIdx.x;
     if ((int)blockIdx.x < A.nedge) {
-        const long e = A.edge_lo[blockIdx.x] + tid;
-        if (e < A.lo || e >= A.hi) return;
+        long e = A.edge_lo[blockIdx.x] + tid;
+        bool live = true;
+        if constexpr (OK == OK_GOUT) {
+            // every thread stays for the block's sum: one out of range works on element lo and
+            // stores nothing
+            live = e >= A.lo && e < A.hi;
+            if (!live) e = A.lo;
+        } else if (e < A.lo || e >= A.hi) return;
         const float x = A.S[e];
-        float p = A.p[e], m = 0.f, v = 0.f;
+        float p = 0.f, m = 0.f, v = 0.f;
+        if constexpr (OK != OK_GOUT || C) p = A.p[e];
         if constexpr (HAS_M) m = A.m[e];
         if constexpr (HAS_V) v = A.v[e];
         const float p0 = p;             // the pre-update p (C)
@@ -404,8 +491,21 @@ __global__ void __launch_bounds__(256) k_agg_stream_reg(AggArgs A) {
         float s = 0.f;
         if (!tail) s = casc_run_macro(prog, 0, cv, yf);
         if (tail) s = casc_run_macro(prog, A.R.info.tail_off, cv, yf);
-        opt_elem<OK, W>(A.ac, A.oc, s, p, m, v);
-        A.p[e] = p;
+        if constexpr (OK == OK_GOUT) {
+            const float g = rule_div<W>(A.ac, s);
+            if (live) {
+                A.G[e] = g;
+                if (A.S_out) A.S_out[e] = x;
+                if constexpr (C) {
+                    if (A.theta_out) A.theta_out[e] = p0;
+                }
+            }
+            gout_block(A, live ? (double)g * (double)g : 0.0);
+            return;
+        } else {
+            opt_elem<OK, W>(A.ac, A.oc, s, p, m, v);
+            A.p[e] = p;
+        }
         if constexpr (HAS_M) A.m[e] = m;
         if constexpr (HAS_V) A.v[e] = v;
         if (A.S_out) A.S_out[e] = x;
@@ -415,7 +515,12 @@ __global__ void __launch_bounds__(256) k_agg_stream_reg(AggArgs A) {
         return;
     }
     const long b0 = 4 * (A.g0 + (long)(blockIdx.x - A.nedge) * 256 * G);   // block's first element
-    if (block_touch(A, b0, 1024L * G)) return;
+    if (block_touch(A, b0, 1024L * G)) {
+        if constexpr (OK == OK_GOUT) {
+            if (tid == 0) A.partials[A.part0 + blockIdx.x] = 0.0;      // its edge pieces hold the sum
+        }
+        return;
+    }
     auto ld = [](const float* ptr) -> f32x4 {
         return __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(ptr));
     };
@@ -448,7 +553,8 @@ __global__ void __launch_bounds__(256) k_agg_stream_reg(AggArgs A) {
 #pragma unroll
     for (int j = 0; j < G; ++j) {
         xs[j] = ld(A.S + e[j]);
-        ps[j] = ld(A.p + e[j]);
+        if constexpr (OK != OK_GOUT || C) ps[j] = ld(A.p + e[j]);
+        else ps[j] = f32x4{0.f, 0.f, 0.f, 0.f};
         if constexpr (HAS_M) ms[j] = ld(A.m + e[j]);
         else ms[j] = f32x4{0.f, 0.f, 0.f, 0.f};
         if constexpr (HAS_V) vs[j] = ld(A.v + e[j]);
@@ -482,23 +588,120 @@ __global__ void __launch_bounds__(256) k_agg_stream_reg(AggArgs A) {
     };
     const T sum = casc_run_macro<true>(prog, 0, casc_values(widen(xs), A.R.info.need, A.R.info.lp),
                                        yf);
+    double sq = 0.0;                    // OK_GOUT: this thread's squares, group by group
 #pragma unroll
     for (int j = 0; j < G; ++j) {
         if constexpr (C) {
             if (A.theta_out) st(A.theta_out + e[j], ps[j]);
         }
+        if constexpr (OK == OK_GOUT) {
+            f32x4 g;
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            float pp = ps[j][u], mm = ms[j][u], vv = vs[j][u];
-            opt_elem<OK, W>(A.ac, A.oc, sum[4 * j + u], pp, mm, vv);
-            ps[j][u] = pp;
-            ms[j][u] = mm;
-            vs[j][u] = vv;
+            for (int u = 0; u < 4; ++u) {
+                g[u] = rule_div<W>(A.ac, sum[4 * j + u]);
+                sq += (double)g[u] * (double)g[u];
+            }
+            st(A.G + e[j], g);
+        } else {
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                float pp = ps[j][u], mm = ms[j][u], vv = vs[j][u];
+                opt_elem<OK, W>(A.ac, A.oc, sum[4 * j + u], pp, mm, vv);
+                ps[j][u] = pp;
+                ms[j][u] = mm;
+                vs[j][u] = vv;
+            }
+            st(A.p + e[j], ps[j]);
         }
-        st(A.p + e[j], ps[j]);
         if constexpr (HAS_M) st(A.m + e[j], ms[j]);
         if constexpr (HAS_V) st(A.v + e[j], vs[j]);
         if (A.S_out) st(A.S_out + e[j], xs[j]);
+    }
+    if constexpr (OK == OK_GOUT) gout_block(A, sq);
+}
+
+// ================================================================================================
+// The clipped step's second and third launches (include/flsim.h)
+// ================================================================================================
+// One block: thread t adds partials[t], partials[t + 256], ... in index order, block_sum_f64 adds
+// the 256 threads; thread 0 writes out[0] = total_norm = (float)sqrt(sum) and out[1] = coef =
+// min(RN(1 / (total_norm + f32(1e-6))) * max_norm, 1.0f).  The comparison keeps a NaN (fminf
+// would drop it); the reciprocal is the IEEE division 1 / x, as torch's reciprocal().
+__global__ void __launch_bounds__(256) k_clip_finish(const double* partials, long n, float max_norm,
+                                                     float* out) {
+    double a = 0.0;
+    long i = threadIdx.x;
+    for (; i + 7 * 256 < n; i += 8 * 256) {     // eight loads in flight, added in index order
+        double x[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) x[u] = partials[i + 256 * u];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) a += x[u];
+    }
+    for (; i < n; i += 256) a += partials[i];
+    __shared__ double red[4];
+    const double tot = block_sum_f64(a, red);
+    if (threadIdx.x == 0) {
+        const float t = (float)sqrt(tot);
+        float c = __fdiv_rn(1.0f, t + 1e-6f) * max_norm;
+        c = c > 1.0f ? 1.0f : c;
+        out[0] = t;
+        out[1] = c;
+    }
+}
+
+struct ClipApplyArgs {
+    const float* G;
+    const float* coef;              // the device scalar k_clip_finish wrote
+    float* p;
+    float* m;
+    float* v;
+    long P;
+    AdamConst ac;
+    OptConst oc;
+};
+
+// g' = G * coef (one fp32 multiply, always applied), then the update of kind OK on g' (opt_update:
+// no cascade program in between, so a -0 gradient stays -0).  One float4 group per thread,
+// non-temporal like the stream; the last P % 4 elements one by one.
+template <int OK>
+__global__ void __launch_bounds__(256) k_clip_apply(ClipApplyArgs A) {
+    constexpr bool HAS_M = opt_n_state(OK) >= 1, HAS_V = opt_n_state(OK) == 2;
+    const long e0 = 4 * ((long)blockIdx.x * 256 + threadIdx.x);
+    if (e0 >= A.P) return;
+    const float coef = *A.coef;
+    if (e0 + 4 <= A.P) {
+        auto ld = [](const float* ptr) -> f32x4 {
+            return __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(ptr));
+        };
+        auto st = [](float* ptr, f32x4 val) {
+            __builtin_nontemporal_store(val, reinterpret_cast<f32x4*>(ptr));
+        };
+        const f32x4 g = ld(A.G + e0);
+        f32x4 p = ld(A.p + e0), m = {0.f, 0.f, 0.f, 0.f}, v = m;
+        if constexpr (HAS_M) m = ld(A.m + e0);
+        if constexpr (HAS_V) v = ld(A.v + e0);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            float pp = p[u], mm = m[u], vv = v[u];
+            opt_update<OK>(A.ac, A.oc, g[u] * coef, pp, mm, vv);
+            p[u] = pp;
+            m[u] = mm;
+            v[u] = vv;
+        }
+        st(A.p + e0, p);
+        if constexpr (HAS_M) st(A.m + e0, m);
+        if constexpr (HAS_V) st(A.v + e0, v);
+        return;
+    }
+    for (long e = e0; e < A.P; ++e) {
+        float p = A.p[e], m = 0.f, v = 0.f;
+        if constexpr (HAS_M) m = A.m[e];
+        if constexpr (HAS_V) v = A.v[e];
+        opt_update<OK>(A.ac, A.oc, A.G[e] * coef, p, m, v);
+        A.p[e] = p;
+        if constexpr (HAS_M) A.m[e] = m;
+        if constexpr (HAS_V) A.v[e] = v;
     }
 }
 
@@ -1388,8 +1591,67 @@ static void launch_agg_kind(int ok, bool reg, int G, dim3 grid, hipStream_t stre
         case OK_ADAM: launch_agg<OK_ADAM, W, C>(reg, G, grid, stream, ps, A); break;
         case OK_ADAMD: launch_agg<OK_ADAMD, W, C>(reg, G, grid, stream, ps, A); break;
         case OK_SGDM: launch_agg<OK_SGDM, W, C>(reg, G, grid, stream, ps, A); break;
+        case OK_GOUT: launch_agg<OK_GOUT, W, C>(reg, G, grid, stream, ps, A); break;
         default: launch_agg<OK_SGD, W, C>(reg, G, grid, stream, ps, A); break;
     }
+}
+
+// Clipping's max_norm (the values for which torch's clip would flip or zero the gradient, or
+// turn it into NaN); before any pointer check, like check_optim.  Negated: a NaN is refused too.
+static int check_clip(const flsim_clip* c) {
+    if (!c) return 0;
+    FLSIM_REQUIRE(c->max_norm > 0.f, "Invalid clipping max_norm %g: it must be > 0",
+                  (double)c->max_norm);
+    return 0;
+}
+
+// [a, a + n) and [b, b + n) floats share an element
+static bool overlaps(const float* a, const float* b, long n) {
+    return a && b && (uintptr_t)a < (uintptr_t)(b + n) && (uintptr_t)b < (uintptr_t)(a + n);
+}
+
+// the clipped step's second and third launches
+static int clip_finish_apply(const flsim_clip* clip, long n_part, const OptLaunch& ol, float* p,
+                             float* m, float* v, long P, hipStream_t stream) {
+    {
+        const ProbeSlot ps = probe_begin();
+        hipExtLaunchKernelGGL(k_clip_finish, dim3(1), dim3(256), 0, stream, ps.start, ps.stop, 0,
+                              (const double*)clip->partials, n_part, clip->max_norm, clip->out);
+        FLSIM_LAUNCH_CHECK();
+        if (probe_end(ps, K_CLIP_FIN, 8.0 * (double)n_part + 8.0)) return 2;
+    }
+    ClipApplyArgs A{};
+    A.G = clip->G;
+    A.coef = clip->out + 1;
+    A.p = p;
+    A.m = m;
+    A.v = v;
+    A.P = P;
+    A.ac = ol.ac;
+    A.oc = ol.oc;
+    const dim3 grid((unsigned)((P + 1023) / 1024));
+    const ProbeSlot ps = probe_begin();
+    switch (ol.ok) {
+        case OK_ADAM:
+            hipExtLaunchKernelGGL(k_clip_apply<OK_ADAM>, grid, dim3(256), 0, stream, ps.start,
+                                  ps.stop, 0, A);
+            break;
+        case OK_ADAMD:
+            hipExtLaunchKernelGGL(k_clip_apply<OK_ADAMD>, grid, dim3(256), 0, stream, ps.start,
+                                  ps.stop, 0, A);
+            break;
+        case OK_SGDM:
+            hipExtLaunchKernelGGL(k_clip_apply<OK_SGDM>, grid, dim3(256), 0, stream, ps.start,
+                                  ps.stop, 0, A);
+            break;
+        default:
+            hipExtLaunchKernelGGL(k_clip_apply<OK_SGD>, grid, dim3(256), 0, stream, ps.start,
+                                  ps.stop, 0, A);
+            break;
+    }
+    FLSIM_LAUNCH_CHECK();
+    // algorithmic HBM bytes: G read; p and the kind's state arrays read + written
+    return probe_end(ps, K_CLIP_APPLY, 4.0 * (double)P * (3 + 2 * opt_n_state(ol.ok)));
 }
 
 }  // namespace flsim
@@ -1447,9 +1709,32 @@ int flsim_aggregate_optim_crule_push(const float* S, float* S_out, float* theta_
                                      const flsim_rule_comp* comp, float* p, float* m, float* v,
                                      long P, const long* tensor_sizes, int n_tensors, long step,
                                      const flsim_optim* optim, hipStream_t stream) {
+    return flsim_aggregate_optim_clip_push(S, S_out, theta_out, rule, wts, comp, nullptr, p, m, v,
+                                           P, tensor_sizes, n_tensors, step, optim, stream);
+}
+
+// the doubles a clipped step over P elements writes, for any layout of at most 4096 tensors: a
+// launch covers at most MAX_TAILS tensor tails, so at most 513 launches; a launch over n
+// elements has at most n / 1024 + 2 streaming blocks, and each streaming block that is an edge
+// block adds 4 * G <= 8 edge pieces
+long flsim_clip_partials(long P) {
+    if (P < 0) return 0;
+    return 9 * (P / 1024 + 2 * (4096 / MAX_TAILS + 1));
+}
+
+// the same with global-norm clipping between rule() and the update (include/flsim.h): the stream
+// runs as OK_GOUT (g -> clip->G, one fp64 sum of squares per block -> clip->partials), then
+// k_clip_finish and k_clip_apply of the optimizer's kind; clip == NULL: the entry point above
+int flsim_aggregate_optim_clip_push(const float* S, float* S_out, float* theta_out,
+                                    const flsim_rule* rule, const flsim_rule_weights* wts,
+                                    const flsim_rule_comp* comp, const flsim_clip* clip, float* p,
+                                    float* m, float* v, long P, const long* tensor_sizes,
+                                    int n_tensors, long step, const flsim_optim* optim,
+                                    hipStream_t stream) {
     RC(check_optim(optim));
     RC(check_weights(wts));
     RC(check_comp(comp, rule));
+    RC(check_clip(clip));
     const bool cform = comp != nullptr || theta_out != nullptr;
     const int nstate = optim_n_state(optim);
     FLSIM_REQUIRE(S && p && (m || nstate < 1) && (v || nstate < 2) && tensor_sizes && rule,
@@ -1499,7 +1784,25 @@ int flsim_aggregate_optim_crule_push(const float* S, float* S_out, float* theta_
         off += tensor_sizes[t];
     }
     FLSIM_REQUIRE(off == P, "tensor sizes sum to %ld, P = %ld", off, P);
-    // one launch per <= MAX_TAILS tensor tails (the last numel % 32 elements of each tensor)
+    if (clip) {
+        FLSIM_REQUIRE(clip->G && clip->partials && clip->out, "null clip buffer");
+        FLSIM_REQUIRE((((uintptr_t)clip->G | (uintptr_t)clip->partials | (uintptr_t)clip->out) &
+                       15) == 0, "clip G/partials/out must be 16-byte aligned");
+        const float* others[] = {S, S_out, theta_out, p, m, v};
+        for (const float* o : others)
+            FLSIM_REQUIRE(!overlaps(clip->G, o, P), "clip G overlaps S/S_out/theta_out/p/m/v");
+        for (int q = 0; q < A.R.narr; ++q)
+            FLSIM_REQUIRE(!overlaps(clip->G, A.R.arr[q], P) && !overlaps(clip->G, A.snap[q], P),
+                          "clip G overlaps entry array %d or its snapshot", q);
+        A.G = clip->G;
+        A.partials = clip->partials;
+    }
+    // one launch per <= MAX_TAILS tensor tails (the last numel % 32 elements of each tensor);
+    // a clipped step first walks the launches without launching, for the partials it will write
+    const int ok_launch = clip ? (int)OK_GOUT : ol.ok;
+    long n_part = 0;                // blocks launched so far (a clipped step: partials written)
+    auto walk = [&](bool dry) -> int {
+    n_part = 0;
     off = 0;
     long lo = 0;
     int t = 0;
@@ -1546,20 +1849,34 @@ int flsim_aggregate_optim_crule_push(const float* S, float* S_out, float* theta_
         }
         // algorithmic HBM bytes: read S_t + the distinct entry arrays + p and the kind's state
         // arrays (m, v: 2, 1 or 0 of them); write p and the state arrays [+ S_out]
-        const double bytes =
-            4.0 * (double)(hi - lo) * (3 + 2 * nstate + A.R.distinct + (S_out ? 1 : 0) + nsnap +
-                                       (theta_out ? 1 : 0));
+        // (a clipped step's first launch: S_t + the entry arrays [+ p: C form] read, G written)
+        const double bytes = clip
+            ? 4.0 * (double)(hi - lo) * (2 + (cform ? 1 : 0) + A.R.distinct + (S_out ? 1 : 0) +
+                                         nsnap + (theta_out ? 1 : 0))
+            : 4.0 * (double)(hi - lo) * (3 + 2 * nstate + A.R.distinct + (S_out ? 1 : 0) + nsnap +
+                                         (theta_out ? 1 : 0));
+        A.part0 = n_part;
+        n_part += nblk + A.nedge;
+        lo = hi;
+        if (dry) continue;
         const ProbeSlot ps = probe_begin();
         const dim3 grid((unsigned)(nblk + A.nedge));
         if (!reg && A.R.prog != nullptr) RC(stage_program(A.R, stream));
-        if (cform) launch_agg_kind<true, true>(ol.ok, reg, G, grid, stream, ps, A);
-        else if (wts) launch_agg_kind<true>(ol.ok, reg, G, grid, stream, ps, A);
-        else launch_agg_kind<false>(ol.ok, reg, G, grid, stream, ps, A);
+        if (cform) launch_agg_kind<true, true>(ok_launch, reg, G, grid, stream, ps, A);
+        else if (wts) launch_agg_kind<true>(ok_launch, reg, G, grid, stream, ps, A);
+        else launch_agg_kind<false>(ok_launch, reg, G, grid, stream, ps, A);
         FLSIM_LAUNCH_CHECK();
-        if (probe_end(ps, A.R.prog == nullptr ? K_AGG : K_AGG_SEQ, bytes)) return 2;
-        lo = hi;
+        if (probe_end(ps, clip ? K_AGG_GOUT : (A.R.prog == nullptr ? K_AGG : K_AGG_SEQ), bytes))
+            return 2;
     }
     return 0;
+    };
+    if (!clip) return walk(false);
+    RC(walk(true));
+    FLSIM_REQUIRE(clip->n_partials >= n_part, "clip n_partials = %ld, this step writes %ld",
+                  clip->n_partials, n_part);
+    RC(walk(false));
+    return clip_finish_apply(clip, n_part, ol, p, m, v, P, stream);
 }
 
 // reference order: weight_ups = [S] * c + stale[0 .. n_stale) (main.py:161-172)
@@ -1696,6 +2013,42 @@ int flsim_cascade_eval_host_c(const int32_t* prog, const int32_t* info, const fl
     for (int q = 0; q < n_arrays; ++q) wf[q] = (float)rw.w[q];
     eval_host(prog, info, S, ys, wf, n_arrays, ac.fk, tail, n, out, theta_now, theta_src,
               (float)lambda);
+    return 0;
+}
+
+// the clipped step's twin (testing): g as the twins above give it (w == NULL and theta_src ==
+// NULL: the plain mean), then total_norm = (float)sqrt(sum of the fp64 squares, in element
+// order), coef = min(RN(1 / (total_norm + f32(1e-6))) * f32(max_norm), 1) with a NaN kept, and
+// g_out = g * coef.  max_norm is refused as the entry point refuses it.
+int flsim_cascade_eval_host_clip(const int32_t* prog, const int32_t* info, const float* S,
+                                 const float* const* ys, const double* w, int n_arrays,
+                                 double divisor, const float* theta_now,
+                                 const float* const* theta_src, double lambda, const uint8_t* tail,
+                                 long n, double max_norm, float* g_out, float* norm_coef) {
+    flsim_clip c{};
+    c.max_norm = (float)max_norm;
+    RC(check_clip(&c));
+    FLSIM_REQUIRE(g_out && norm_coef, "null pointer");
+    if (w || theta_src) {
+        RC(flsim_cascade_eval_host_c(prog, info, S, ys, w, n_arrays, divisor, theta_now,
+                                     theta_src, lambda, tail, n, g_out));
+    } else {
+        FLSIM_REQUIRE(n_arrays >= 0 && n_arrays <= RULE_MAX_ARR, "n_arrays = %d", n_arrays);
+        FLSIM_REQUIRE(prog && info && S && (ys || n_arrays == 0), "null pointer");
+        AdamConst ac;
+        RC(make_divisor(divisor, &ac));
+        eval_host(prog, info, S, ys, nullptr, n_arrays, ac.fk, tail, n, g_out);
+    }
+    double tot = 0.0;
+    for (long e = 0; e < n; ++e) tot += (double)g_out[e] * (double)g_out[e];
+    volatile float t = (float)sqrt(tot), one = 1.f, eps = 1e-6f;
+    volatile float den = t + eps;
+    volatile float rcp = one / den;
+    float coef = rcp * c.max_norm;
+    coef = coef > 1.0f ? 1.0f : coef;
+    for (long e = 0; e < n; ++e) g_out[e] = g_out[e] * coef;
+    norm_coef[0] = t;
+    norm_coef[1] = coef;
     return 0;
 }
 

@@ -151,7 +151,9 @@ struct AdamConst {
 //   OK_ADAMD  Adam with weight_decay (coupled L2) or AdamW (decoupled): p, m, v
 //   OK_SGDM   torch.optim.SGD with momentum != 0: p and the momentum buffer in m; v untouched
 //   OK_SGD    torch.optim.SGD with momentum == 0: p only; m and v untouched
-enum OptKind { OK_ADAM = 0, OK_ADAMD = 1, OK_SGDM = 2, OK_SGD = 3 };
+//   OK_GOUT   no update (the clipped step's first launch, k_agg_stream only): g = rule() is stored
+//             to G and its squares are summed per block; p is read by the C form alone
+enum OptKind { OK_ADAM = 0, OK_ADAMD = 1, OK_SGDM = 2, OK_SGD = 3, OK_GOUT = 4 };
 constexpr int opt_n_state(int ok) { return ok <= OK_ADAMD ? 2 : (ok == OK_SGDM ? 1 : 0); }
 // the same count from a checked flsim_optim (check_optim), before its OptLaunch is made
 inline int optim_n_state(const flsim_optim* o) {

@@ -49,6 +49,7 @@ EXPORTS = [
     "flsim_aggregate_optim_crule_push", "flsim_pn1_server_step_crule",
     "flsim_vgg11_server_step_crule", "flsim_vgg11_bn_server_step_crule",
     "flsim_cascade_eval_host_c",
+    "flsim_clip_partials", "flsim_aggregate_optim_clip_push", "flsim_cascade_eval_host_clip",
 ]
 COMM_ID_BYTES = 128      # FLSIM_COMM_ID_BYTES
 
@@ -78,6 +79,13 @@ class FlsimRuleComp(ctypes.Structure):
     a rule's arrays (NULL: not compensated)."""
     _fields_ = [("n", ctypes.c_int32), ("lam", ctypes.c_double),
                 ("theta_src", ctypes.c_void_p * MAX_ARRAYS)]
+
+
+class FlsimClip(ctypes.Structure):
+    """flsim_clip (include/flsim.h): max_norm and the caller's scratch of a clipped step."""
+    _fields_ = [("max_norm", ctypes.c_float), ("G", ctypes.c_void_p),
+                ("partials", ctypes.c_void_p), ("n_partials", ctypes.c_long),
+                ("out", ctypes.c_void_p)]
 
 
 OPT_KINDS = {"adam": 0, "adamw": 1, "sgd": 2}      # FLSIM_OPT_ADAM / _ADAMW / _SGD
@@ -194,6 +202,14 @@ def lib():
         vp, vp, vp, vp, vp, vp, vp, vp, vp, ctypes.c_long, vp, ctypes.c_int, ctypes.c_long, vp, vp]
     L.flsim_cascade_eval_host_c.argtypes = [vp, vp, vp, vp, vp, ctypes.c_int, ctypes.c_double, vp,
                                             vp, ctypes.c_double, vp, ctypes.c_long, vp]
+    L.flsim_clip_partials.restype = ctypes.c_long
+    L.flsim_clip_partials.argtypes = [ctypes.c_long]
+    L.flsim_aggregate_optim_clip_push.argtypes = [
+        vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ctypes.c_long, vp, ctypes.c_int, ctypes.c_long, vp,
+        vp]
+    L.flsim_cascade_eval_host_clip.argtypes = [
+        vp, vp, vp, vp, vp, ctypes.c_int, ctypes.c_double, vp, vp, ctypes.c_double, vp,
+        ctypes.c_long, ctypes.c_double, vp, vp]
     L.flsim_cascade_program.argtypes = [ctypes.c_int, vp, vp, ctypes.c_int, vp, ctypes.c_int, vp]
     L.flsim_cascade_eval_host.argtypes = [vp, vp, vp, vp, ctypes.c_int, vp, ctypes.c_long, vp]
     L.flsim_probe_enable.argtypes = [ctypes.c_int]

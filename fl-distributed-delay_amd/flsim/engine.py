@@ -20,8 +20,8 @@ import torch
 
 import math
 
-from ._lib import (MAX_ARRAYS, OPT_KINDS, FlsimOptim, FlsimRule, FlsimRuleComp, FlsimRuleWeights,
-                   WorkerRec, check, lib, ptr, stream_ptr)
+from ._lib import (MAX_ARRAYS, OPT_KINDS, FlsimClip, FlsimOptim, FlsimRule, FlsimRuleComp,
+                   FlsimRuleWeights, WorkerRec, check, lib, ptr, stream_ptr)
 
 # named_parameters() order of models.py:PerformantNet1 (models.py:13-25)
 PN1_SHAPES = [
@@ -402,16 +402,18 @@ class NetEngine:
         aggregate_adam(S, c, stale, theta, m, v, step, self.SIZES, lr, betas, eps, optim=optim)
 
     def aggregate_adam_sum(self, S, k, theta, m, v, step, lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
-                           optim=None):
-        aggregate_adam_sum(S, k, theta, m, v, step, self.SIZES, lr, betas, eps, optim=optim)
+                           optim=None, clip=None):
+        aggregate_adam_sum(S, k, theta, m, v, step, self.SIZES, lr, betas, eps, optim=optim,
+                           clip=clip)
 
     def aggregate_rule(self, S, rule, theta, m, v, step, lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
-                       S_out=None, optim=None, theta_out=None):
+                       S_out=None, optim=None, theta_out=None, clip=None):
         """rule() + Adam (or the update rule `optim`) from S_t in a buffer; S_out (optional): S_t
         is also written there in the same pass (the FIFO slot of a tick epoch at world > 1);
-        theta_out (optional): so is the pre-update theta (that slot's snapshot)."""
+        theta_out (optional): so is the pre-update theta (that slot's snapshot); clip (a Clip):
+        the rule's output is clipped to clip.max_norm before the update."""
         aggregate_rule(S, rule, theta, m, v, step, self.SIZES, lr, betas, eps, S_out=S_out,
-                       optim=optim, theta_out=theta_out)
+                       optim=optim, theta_out=theta_out, clip=clip)
 
 
 class PN1Engine(NetEngine):
@@ -550,13 +552,15 @@ def aggregate_adam(S, c, stale, theta, m, v, step, sizes, lr=1e-3, betas=(0.9, 0
 
 
 def aggregate_adam_sum(S, k, theta, m, v, step, sizes, lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
-                       optim=None):
+                       optim=None, clip=None):
     """Independent-entry semantics: S = the sum of the k distinct weight_ups entries; mean = S / k
-    then the same Adam step (flsim_aggregate_adam_sum), or the update rule `optim`."""
-    if optim is not None:
+    then the same Adam step (flsim_aggregate_adam_sum), or the update rule `optim`; clip (a Clip):
+    the mean is clipped first (the same stream with the sum rule)."""
+    if optim is not None or clip is not None:
         if k <= 0:
             raise IndexError("empty weight_ups (reference: IndexError in rule, main.py:25)")
-        aggregate_rule(S, Rule(k, [], c=1), theta, m, v, step, sizes, optim=optim)
+        aggregate_rule(S, Rule(k, [], c=1), theta, m, v, step, sizes, lr, betas, eps, optim=optim,
+                       clip=clip)
         return
     csz = (ctypes.c_long * len(sizes))(*[int(n) for n in sizes])
     check(lib().flsim_aggregate_adam_sum(
@@ -736,13 +740,63 @@ def _byref(struct):
     return ctypes.byref(struct) if struct is not None else None
 
 
+class Clip:
+    """Global-norm gradient clipping of a server step (flsim_clip, include/flsim.h): what
+    torch.nn.utils.clip_grad_norm_(parameters, max_norm) does between `p.grad = ...` and
+    optim.step(), on the rule's output.  max_norm > 0; float("inf") clips nothing and only reports
+    the norm.  The object owns its scratch per device (the rule's output G, the per-block partial
+    sums, the two result scalars), allocated at the first step on that device.  After a step,
+    total_norm (the correctly rounded 2-norm of the rule's output) and coef (the factor the
+    gradient was multiplied by) are 0-d device tensors; reading them needs no synchronisation
+    beyond the stream's order, and the next step overwrites them (clone to keep)."""
+
+    def __init__(self, max_norm):
+        self.max_norm = float(max_norm)
+        if not self.max_norm > 0:
+            raise ValueError(f"Invalid clipping max_norm {self.max_norm}: it must be > 0")
+        self._scratch = {}
+        self.total_norm = None
+        self.coef = None
+
+    def c_struct(self, device, P):
+        """flsim_clip over this device's scratch for a step over P elements."""
+        key = (str(device), int(P))
+        if key not in self._scratch:
+            n = int(lib().flsim_clip_partials(int(P)))
+            self._scratch[key] = (torch.empty(padded(int(P)), device=device),
+                                  torch.empty(n, dtype=torch.float64, device=device),
+                                  torch.empty(4, device=device))
+        G, partials, out = self._scratch[key]
+        c = FlsimClip()
+        c.max_norm = self.max_norm
+        c.G = G.data_ptr()
+        c.partials = partials.data_ptr()
+        c.n_partials = int(partials.numel())
+        c.out = out.data_ptr()
+        self.total_norm, self.coef = out[0], out[1]
+        return c
+
+
 def aggregate_rule(S, rule, theta, m, v, step, sizes, lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
-                   S_out=None, optim=None, theta_out=None):
+                   S_out=None, optim=None, theta_out=None, clip=None):
     """rule() + Adam from S_t in a buffer (flsim_aggregate_adam_rule_push; S_out may be None).
     optim (an Optim or a dict of its fields): that update rule instead of Adam(lr, betas, eps)
     (flsim_aggregate_optim_rule_push); m / v may be None where the kind owns no such array (SGD:
-    v; SGD without momentum: m and v) and are left untouched when given."""
+    v; SGD without momentum: m and v) and are left untouched when given.  clip (a Clip): the
+    rule's output is clipped to clip.max_norm before the update
+    (flsim_aggregate_optim_clip_push); clip.total_norm and clip.coef hold the step's norm and
+    factor afterwards."""
     csz = (ctypes.c_long * len(sizes))(*[int(n) for n in sizes])
+    if clip is not None:
+        o = (as_optim(optim) if optim is not None else
+             Optim(lr=lr, betas=tuple(betas), eps=eps)).c_struct()
+        P = sum(int(n) for n in sizes)
+        c = clip.c_struct(theta.device, P)
+        check(lib().flsim_aggregate_optim_clip_push(
+            ptr(S), ptr(S_out), ptr(theta_out), ctypes.byref(rule.c_rule), _byref(rule.c_weights),
+            _byref(rule.c_comp), ctypes.byref(c), ptr(theta), ptr(m), ptr(v), P, csz, len(sizes),
+            int(step), ctypes.byref(o), stream_ptr()))
+        return
     if rule.c_comp is not None or theta_out is not None:
         # the delay-compensated rule (rule.snapshots) and / or the snapshot write (theta_out: the
         # pre-update theta, in the same pass)

@@ -26,6 +26,13 @@ moved since the entry was pushed (DC-ASGD, Zheng et al. 2017), before any discou
 x + (x * x) * lambda * (theta_t - theta_src).  Every pushed slot carries the theta it was pushed
 at; the server step writes that snapshot in its own pass.  An entry is S_src, a sum over that
 epoch's workers, so x * x grows with the square of the worker count: choose lambda accordingly.
+
+clip_grad_norm (None or max_norm > 0) clips the rule's output to that global 2-norm before the
+update, what torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm) does between `p.grad = ...`
+and optim.step() (engine.Clip; float("inf") clips nothing and only records the norm).  It comes
+after the all-reduce and is replicated, so it adds no collective; at world = 1 the epoch then ends
+with the slab reduction and the clipped streaming step (three launches) instead of the one fused
+launch.  grad_norms() returns the norm of every epoch's aggregate.
 """
 from __future__ import annotations
 
@@ -35,8 +42,8 @@ import numpy as np
 import torch
 
 from .data import DevicePool, make_test_pool
-from .engine import (PN1_SIZES, Optim, ProgramStager, Rule, engine_class, padded, split_views,
-                     staleness_weight)
+from .engine import (PN1_SIZES, Clip, Optim, ProgramStager, Rule, engine_class, padded,
+                     split_views, staleness_weight)
 from .schedule import Schedule, reference_delays
 
 SEMANTICS = ("reference", "torch1", "independent")
@@ -78,7 +85,7 @@ class FLSimulation:
                  fused=True, keep_S=False, batch_size=128, distributed=None,
                  collective="torch", optimizer="adam", weight_decay=0.0, momentum=0.0,
                  dampening=0.0, nesterov=False, stale_weight=None, stale_normalize="weights",
-                 delay_comp=None):
+                 delay_comp=None, clip_grad_norm=None):
         if semantics not in SEMANTICS:
             raise NotImplementedError(f"semantics {semantics!r} (supported: {SEMANTICS})")
         # delay compensation's lambda (None: off); theta is replicated, so at world > 1 every rank
@@ -91,6 +98,10 @@ class FLSimulation:
             if semantics == "independent":
                 # its popped slots are added with a torch add_ before the all-reduce: another path
                 raise NotImplementedError("independent entries with delay compensation")
+        # global-norm clipping of the aggregate (None: off; today's code paths exactly)
+        self.clip_grad_norm = None if clip_grad_norm is None else float(clip_grad_norm)
+        self.clip = None if clip_grad_norm is None else Clip(self.clip_grad_norm)
+        self.norm_log = []        # per epoch: float (read back) or a 0-d device tensor
         # the discount of a popped entry's age; a replicated host computation (every rank derives
         # the same weights from the schedule)
         if stale_normalize not in ("weights", "count"):
@@ -408,7 +419,9 @@ class FLSimulation:
         lo, hi = self.shard(active)
         eng = self.engine
         G = self.G                               # 128-sample groups (units) per worker-step
-        fused = self.fused and not self.distributed and hasattr(eng, "server_step")
+        # (clipping: the slab reduction, then the clipped streaming step)
+        fused = self.fused and not self.distributed and hasattr(eng, "server_step") and \
+            self.clip is None
         # (a weighted or compensated rule over more arrays than the fused step takes: reduce, then
         # stream)
         keep_S = self.keep_S or (fused and
@@ -484,6 +497,8 @@ class FLSimulation:
             hp = dict(optim=self._optim_arg)
         if snap is not None and not (fused and keep_S):
             hp["theta_out"] = snap
+        if self.clip is not None:
+            hp["clip"] = self.clip
         if fused and not keep_S:
             eng.server_step(push, rule, self.theta, self.m, self.v, self.step, **hp)
         elif fused:
@@ -500,6 +515,7 @@ class FLSimulation:
                     if src in self.stale_theta:
                         self.free_snaps.append(self.stale_theta.pop(src))
                     del self.stale_store[src]
+        self._log_norm()
         fast_pos = np.nonzero(plan.fast[active])[0]
         self.trace.append(plan)
         if sync_loss:
@@ -582,7 +598,9 @@ class FLSimulation:
         self.step += 1
         eng.aggregate_adam_sum(S, len(fast) + len(plan.stale), self.theta, self.m, self.v,
                                self.step, self.lr, self.betas, self.eps,
-                               **({"optim": self._optim_arg} if self._optim_arg else {}))
+                               **({"optim": self._optim_arg} if self._optim_arg else {}),
+                               **({"clip": self.clip} if self.clip is not None else {}))
+        self._log_norm()
         self.trace.append(plan)
         if sync_loss:
             lv = losses.detach().cpu().numpy()
@@ -591,6 +609,17 @@ class FLSimulation:
             return val
         self.loss_log.append((losses.detach().clone(), np.arange(len(fast))))
         return None
+
+    def _log_norm(self):
+        """Keep this epoch's norm: a clone of the device scalar, read back only by grad_norms()."""
+        if self.clip is not None:
+            self.norm_log.append(self.clip.total_norm.detach().clone())
+
+    def grad_norms(self):
+        """The global 2-norm of every epoch's aggregate before clipping (clip_grad_norm runs
+        only; else []), as floats.  Synchronises on the first call after new epochs."""
+        self.norm_log = [float(x) for x in self.norm_log]
+        return list(self.norm_log)
 
     def losses(self):
         out = []
@@ -667,6 +696,7 @@ class FLSimulation:
             "stale_theta": {int(src): snap[:self.P].detach().cpu()
                             for src, snap in self.stale_theta.items()},
             "loss_log": [float(x) for x in self.losses()],
+            "grad_norms": self.grad_norms(),
             "buffers": dict(getattr(self.engine, "buffer_state", list)()),
         }
 
@@ -685,7 +715,7 @@ class FLSimulation:
         spec = None if self.stale_weight is None else \
             [self.stale_weight[0]] + [float(x) for x in self.stale_weight[1:]]
         return {"stale_weight": spec, "stale_normalize": self.stale_normalize,
-                "delay_comp": self.delay_comp}
+                "delay_comp": self.delay_comp, "clip_grad_norm": self.clip_grad_norm}
 
     def save_checkpoint(self, path):
         torch.save(self.checkpoint(), path)
@@ -710,7 +740,9 @@ class FLSimulation:
                      # ... and from before the staleness discount: none
                      ("stale_weight", None), ("stale_normalize", "weights"),
                      # ... and from before delay compensation: off
-                     ("delay_comp", None)):
+                     ("delay_comp", None),
+                     # ... and from before gradient clipping: off
+                     ("clip_grad_norm", None)):
             cfg.setdefault(k, v)
         delays = cfg["delays"].numpy().astype(np.int32)
         if fmt == "flsim-checkpoint-1":
@@ -753,6 +785,7 @@ class FLSimulation:
                 snap[:self.P].copy_(vals.to(self.device))
                 self.stale_theta[int(src)] = snap
         self.loss_log = list(ck["loss_log"])
+        self.norm_log = [float(x) for x in ck.get("grad_norms", [])]
         if ck.get("buffers"):
             self.engine.load_buffers(ck["buffers"])
 

@@ -6,6 +6,8 @@ Same flags and defaults (main.py:38-53): --n_workers --n_epochs --batch_size --l
 --stale_weight {none,poly,hinge,const} with --stale_a --stale_b --stale_normalize discounts a stale
 entry by its age before the average (the alternative to --throttle).  --delay_comp LAMBDA
 compensates a stale entry for the distance the model has moved since it was computed (DC-ASGD).
+--clip_grad_norm MAX_NORM clips the aggregated gradient's global 2-norm before the update
+(torch.nn.utils.clip_grad_norm_) and logs the norm as 'Grad Norm' per epoch.
 The training loop (main.py:126-188) runs as flsim.sim.FLSimulation: host schedule,
 worker-batched HIP forward/backward, fused rule()+Adam; with
 `torchrun --nproc-per-node N` the computing workers are sharded over N GPUs with one RCCL
@@ -64,6 +66,9 @@ def parse(argv=None):
                         '(theta_now - theta_then) before the average (default: off).  An entry '
                         'is the SUM of its epoch\'s worker gradients, so x*x grows with the '
                         'square of the worker count: choose LAMBDA with that in mind')
+    p.add_argument('--clip_grad_norm', type=float, default=None, metavar='MAX_NORM',
+                   help='clip the aggregated gradient to this global 2-norm before the update, '
+                        'as torch.nn.utils.clip_grad_norm_ (default: off; inf only logs the norm)')
     p.add_argument('--seed', type=int, default=0)
     p.add_argument('--semantics', default='reference', choices=['reference', 'torch1', 'independent'],
                    help='stale entry = S_{t-d} (torch>=2 aliasing), zeros (torch 1.x) or the slow '
@@ -125,7 +130,7 @@ def main(argv=None):
                        weight_decay=args.weight_decay, momentum=args.momentum,
                        dampening=args.dampening, nesterov=args.nesterov,
                        stale_weight=stale_spec(args), stale_normalize=args.stale_normalize,
-                       delay_comp=args.delay_comp)
+                       delay_comp=args.delay_comp, clip_grad_norm=args.clip_grad_norm)
     if buffers:
         sim.engine.load_buffers(buffers)
     if args.resume:
@@ -145,6 +150,8 @@ def main(argv=None):
     for t in range(len(sim.trace), args.n_epochs):
         loss = sim.epoch()
         emit("Avg. Loss", loss, t)                                     # main.py:185
+        if args.clip_grad_norm is not None:
+            emit("Grad Norm", sim.grad_norms()[-1], t)
         if rank == 0 and (t % 10 == 0 or t == args.n_epochs - 1):
             print(f"epoch {t} Avg. Loss {loss:.5f}", flush=True)
         if args.save_model and t % 100 == 0 and t > 0 and rank == 0:   # main.py:192-194

@@ -496,6 +496,61 @@ int flsim_cascade_eval_host_c(const int32_t* prog, const int32_t* info, const fl
                               long n, float* out);
 
 /* ---------------------------------------------------------------------------------------------
+ * Global-norm gradient clipping: Central.update_model (agents.py:9-21) sets p.grad and steps in one
+ * call; these entry points run what a torch user writes between the two,
+ *
+ *   total_norm = torch.nn.utils.get_total_norm(grads, 2.0)        # the engine's: see below
+ *   torch.nn.utils.clip_grads_with_norm_(parameters, max_norm, total_norm)
+ *   optim.step()
+ *
+ * on g = the rule's output (any of the rules above), in three launches: the rule streams g into
+ * clip->G and one fp64 sum of squares per block into clip->partials; a one-block launch adds the
+ * partials in index order and writes out[0] = total_norm, out[1] = coef; the update of `optim`
+ * then runs on g * coef.
+ *   total_norm = (float)sqrt(sum_e (double)g_e * (double)g_e): accumulated in fp64 (a square of an
+ *     fp32 value is exact there) in an order the launch geometry alone fixes (no atomics), so the
+ *     same shape gives the same bits on every run.  It is the correctly rounded norm; torch's own
+ *     get_total_norm accumulates in fp32 and is up to 1e-4 relative below it.
+ *   coef = min(RN(1 / (total_norm + f32(1e-6))) * f32(max_norm), 1.0f) in fp32, as
+ *     clip_grads_with_norm_ computes max_norm / (total_norm + 1e-6) (a reciprocal and a multiply)
+ *     and clamps it; a NaN norm gives a NaN coefficient.  max_norm = inf only reports the norm.
+ *   g' = g * coef: one fp32 multiply, always applied (as torch always multiplies).
+ * Only norm_type 2; error_if_nonfinite stays False.  S_out and theta_out are written by the first
+ * launch as the entry points above write them.  The library still never allocates: the caller
+ * provides G (P floats), partials (at least the doubles the launch sequence writes; the bound
+ * below holds for any layout of at most 4096 tensors) and out (2 floats), all 16-byte aligned;
+ * nothing depends on what they held before.  clip == NULL is the delay-compensated entry point
+ * above.
+ * Checked before any pointer, status 1: max_norm NaN or <= 0.  Then: a NULL or misaligned G /
+ * partials / out; n_partials too small; G overlapping S, S_out, theta_out, p, m, v, an entry array
+ * or a snapshot.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct flsim_clip {
+    float max_norm;   /* > 0; +inf: report the norm only */
+    float* G;         /* [P] the rule's output g (scratch between the launches) */
+    double* partials; /* [n_partials] per-block sums of squares */
+    long n_partials;
+    float* out;       /* [2]: total_norm, coef */
+} flsim_clip;
+
+long flsim_clip_partials(long P);
+int flsim_aggregate_optim_clip_push(const float* S, float* S_out, float* theta_out,
+                                    const flsim_rule* rule, const flsim_rule_weights* wts,
+                                    const flsim_rule_comp* comp, const flsim_clip* clip, float* p,
+                                    float* m, float* v, long P, const long* tensor_sizes,
+                                    int n_tensors, long step, const flsim_optim* optim,
+                                    flsim_stream_t stream);
+/* host (testing): the rule's g as the host twins above give it (w == NULL and theta_src == NULL:
+ * the plain mean sum / divisor), then the norm, the coefficient and g' of the text above:
+ * g_out[e] = g[e] * coef, norm_coef[0] = total_norm, norm_coef[1] = coef.  The squares are summed
+ * in fp64 in element order.  max_norm is refused as the entry point refuses it. */
+int flsim_cascade_eval_host_clip(const int32_t* prog, const int32_t* info, const float* S,
+                                 const float* const* ys, const double* w, int n_arrays,
+                                 double divisor, const float* theta_now,
+                                 const float* const* theta_src, double lambda, const uint8_t* tail,
+                                 long n, double max_norm, float* g_out, float* norm_coef);
+
+/* ---------------------------------------------------------------------------------------------
  * Measurement (no reference counterpart): HIP events around every worker-batched GEMM launch on
  * its stream, for bench.py's live roofline figure.  read() fills flsim_probe_kernel_count()
  * entries per kernel id (launches, total ms, total algorithmic FLOPs) and resets the record.
