@@ -12,7 +12,8 @@ Same classes, signatures and aliasing semantics; the arithmetic runs in libflsim
                                FL.agents.weighted_rule is the staleness-weighted alternative
   Central.update_model(ups)    agents.py:9-21 -> flsim_aggregate_optim_rule_push (cascade mean over
                                the entries in any order + the optimizer's step: torch.optim.Adam,
-                               AdamW or SGD with the hyper-parameters of its param_groups[0]);
+                               AdamW, SGD, Adagrad or flsim.optim.Yogi with the hyper-parameters
+                               of its param_groups[0]);
                                parameters live in one flat device buffer, model.parameters() are
                                views of it
 
@@ -41,9 +42,10 @@ worker-batched pass when a loss, a .grad view or a BatchNorm buffer is read, or 
 (FLSIM_FACADE_LAZY_LOSS=0: a call's forward runs at once).
 
 Requirements (raise otherwise): the model is FL.models.PerformantNet1, vgg11() or vgg11_bn() on
-a HIP device, the optimizer is torch.optim.Adam (weight_decay allowed), torch.optim.AdamW or
-torch.optim.SGD (momentum, dampening, weight_decay, nesterov) with one param group and without
-amsgrad / maximize.  There is no CPU fallback.
+a HIP device, the optimizer is torch.optim.Adam (weight_decay allowed), torch.optim.AdamW,
+torch.optim.SGD (momentum, dampening, weight_decay, nesterov), torch.optim.Adagrad (FedAdagrad) or
+flsim.optim.Yogi (FedYogi) with one param group and without amsgrad / maximize.  There is no CPU
+fallback.
 """
 from __future__ import annotations
 
@@ -55,6 +57,7 @@ import torch
 
 from flsim.engine import (Clip, Optim, ProgramStager, Rule, engine_for_parameters, padded,
                           split_views, worker_table)
+from flsim.optim import Yogi
 
 _CONTEXTS = weakref.WeakKeyDictionary()    # model -> _ModelContext (dies with the model)
 _NEXT_WORKER = [0]                          # Worker.index of the next Worker()
@@ -502,14 +505,22 @@ class Central:
         self.clip = None if clip_grad_norm is None else Clip(clip_grad_norm)
         self.total_norm = None
         g = optim.param_groups[0]
-        if not isinstance(optim, (torch.optim.Adam, torch.optim.SGD)) or \
+        if not isinstance(optim, (torch.optim.Adam, torch.optim.SGD, torch.optim.Adagrad,
+                                  Yogi)) or \
                 len(optim.param_groups) != 1 or g.get("amsgrad", False) or \
                 g.get("maximize", False):
             raise NotImplementedError("fused update implements torch.optim.Adam (weight_decay "
-                                      "allowed), torch.optim.AdamW and torch.optim.SGD with one "
+                                      "allowed), torch.optim.AdamW, torch.optim.SGD, "
+                                      "torch.optim.Adagrad and flsim.optim.Yogi with one "
                                       "param group (main.py:106: Adam(lr)), no amsgrad / maximize")
-        self._optim()                # torch's constructor has validated the hyper-parameters
+        o = self._optim()            # torch's constructor has validated the hyper-parameters
         self.ctx = _context(model)
+        # the accumulator starts where the optimizer's own state would (Adagrad: sum in m; Yogi:
+        # exp_avg_sq in v)
+        if self.ctx.step == 0 and o.kind == "adagrad":
+            self.ctx.m.fill_(o.initial_accumulator_value)
+        if self.ctx.step == 0 and o.kind == "yogi":
+            self.ctx.v.fill_(o.initial_accumulator_value)
         _NEXT_WORKER[0] = 0          # main.py:112-113: the workers built next are 0 .. n-1
 
     def _optim(self):
@@ -520,6 +531,14 @@ class Central:
             return Optim(kind="sgd", lr=g["lr"], weight_decay=g["weight_decay"],
                          momentum=g["momentum"], dampening=g["dampening"],
                          nesterov=bool(g["nesterov"]))
+        if isinstance(self.optim, torch.optim.Adagrad):
+            return Optim(kind="adagrad", lr=g["lr"], lr_decay=g["lr_decay"], eps=g["eps"],
+                         weight_decay=g["weight_decay"],
+                         initial_accumulator_value=g["initial_accumulator_value"])
+        if isinstance(self.optim, Yogi):
+            return Optim(kind="yogi", lr=g["lr"], betas=tuple(g["betas"]), eps=g["eps"],
+                         weight_decay=g["weight_decay"],
+                         initial_accumulator_value=g["initial_accumulator_value"])
         decoupled = isinstance(self.optim, torch.optim.AdamW) or \
             g.get("decoupled_weight_decay", False)
         return Optim(kind="adamw" if decoupled else "adam", lr=g["lr"], betas=tuple(g["betas"]),
@@ -527,9 +546,14 @@ class Central:
 
     def _sync_optimizer_state(self, o):
         """optim.state as torch itself would hold it: step / exp_avg / exp_avg_sq for the Adam
-        family, momentum_buffer for SGD with momentum, nothing for plain SGD (views of the
-        engine's buffers, so optim.state_dict() loads into a stock torch optimizer)."""
+        family and Yogi, step / sum for Adagrad, momentum_buffer for SGD with momentum, nothing
+        for plain SGD (views of the engine's buffers, so optim.state_dict() loads into a stock
+        torch optimizer)."""
         ctx = self.ctx
+        if o.kind == "adagrad":
+            for p, mv in zip(self.model.parameters(), split_views(ctx.m[:ctx.P], ctx.shapes)):
+                self.optim.state[p] = {"step": torch.tensor(float(ctx.step)), "sum": mv}
+            return
         if o.kind == "sgd":
             if o.n_state:
                 for p, mv in zip(self.model.parameters(),

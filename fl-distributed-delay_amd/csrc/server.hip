@@ -11,8 +11,8 @@
 // den = sqrt(v)/sqrt(bc2) + eps, p += (-lr/bc1 * m) / den (correctly rounded sqrt; torch CPU's
 // sqrt is not).  Compiled with -ffp-contract=off: the only fmas are explicit.
 // Central(model, optim) takes other optimizers too: the kernels are instantiated per update rule
-// (OptKind, slabstep.h: Adam, Adam with weight decay / AdamW, SGD with and without momentum; see
-// opt_elem), each streaming only the state arrays its rule owns.
+// (OptKind, slabstep.h: Adam, Adam with weight decay / AdamW, SGD with and without momentum,
+// Adagrad, Yogi; see opt_update), each streaming only the state arrays its rule owns.
 // Agg(rule) takes other rules too: every rule-carrying kernel also has a weighted form (W), the
 // staleness-weighted rule sum_j w_j * entry_j / W with w = 1 for the S_t entries (a stale value is
 // multiplied by its array's fp32 weight where it is loaded, the same cascade sums the products,
@@ -128,6 +128,12 @@ __device__ __forceinline__ void adam_elem(const AdamConst& A, float s, float& p,
 //                         momentum mu != 0: buf = g at step 1, else fma(g, 1 - dampening, buf * mu);
 //                                           g = nesterov ? fma(buf, mu, g) : buf;
 //                         p = fma(g, -lr, p)
+//   Adagrad               g = fma(p, w, g) if w != 0;  sum = fma(g, g, sum);       (_single_tensor_adagrad)
+//                         p = p + (f32(-clr) * g) / (sqrt(sum) + eps)   (sum lives in m)
+//   Yogi (FedYogi form)   g = fma(p, w, g) if w != 0;  m = fma(1 - b1, g - m, m);  g2 = g * g;
+//                         v = fma(f32(-(1 - b2)) * sign(v - g2), g2, v);
+//                         p = p + (f32(-lr) * m) / (sqrt(v) + eps)
+//   (addcmul_(a, b, value=c) is fma(f32(c) * a, b, x); addcdiv_ is x + (f32(c) * a) / b)
 // The flags are launch-uniform (scalar branches).  m is SGD's momentum buffer; a kind never
 // touches an argument it does not own (the callers pass dummies).
 // opt_update: the update for a gradient g (what follows rule()'s division; the clipped step's
@@ -141,6 +147,22 @@ __device__ __forceinline__ void opt_update(const AdamConst& A, const OptConst& X
         if (X.flags & OF_DECOUPLED) p = p * X.wd;
         else g = __fmaf_rn(p, X.wd, g);
         adam_update(A, g, p, m, v);
+    } else if constexpr (OK == OK_ADAGRAD) {
+        if (X.flags & OF_WD) g = __fmaf_rn(p, X.wd, g);
+        const float sum = __fmaf_rn(g, g, m);                   // addcmul_(g, g, value=1)
+        p = p + __fdiv_rn(X.neg_lr * g, sqrt_rn(sum) + A.eps);  // addcdiv_(g, std, value=-clr)
+        m = sum;
+    } else if constexpr (OK == OK_YOGI) {
+        if (X.flags & OF_WD) g = __fmaf_rn(p, X.wd, g);
+        const float mi = __fmaf_rn(A.w1, g - m, m);             // lerp_(g, 1 - beta1)
+        const float g2 = g * g;
+        const float d = v - g2;
+        const float sg = (float)(d > 0.f) - (float)(d < 0.f);   // torch.sign: 0 for a NaN
+        // addcmul_(sign, g2, value=-(1 - beta2)), literally: -+0 * inf is the NaN torch gives
+        const float vi = __fmaf_rn(-A.w2 * sg, g2, v);
+        p = p + __fdiv_rn(X.neg_lr * mi, sqrt_rn(vi) + A.eps);  // addcdiv_(m, std, value=-lr)
+        m = mi;
+        v = vi;
     } else {
         if (X.flags & OF_WD) g = __fmaf_rn(p, X.wd, g);
         if constexpr (OK == OK_SGDM) {
@@ -1296,7 +1318,8 @@ int make_adam_const(double divisor, long step, double lr, double beta1, double b
 int check_optim(const flsim_optim* o) {
     FLSIM_REQUIRE(o, "null optimizer");
     FLSIM_REQUIRE(o->kind == FLSIM_OPT_ADAM || o->kind == FLSIM_OPT_ADAMW ||
-                  o->kind == FLSIM_OPT_SGD, "unknown optimizer kind %d", o->kind);
+                  o->kind == FLSIM_OPT_SGD || o->kind == FLSIM_OPT_ADAGRAD ||
+                  o->kind == FLSIM_OPT_YOGI, "unknown optimizer kind %d", o->kind);
     // negated comparisons: a NaN is refused too
     FLSIM_REQUIRE(o->lr >= 0.0, "Invalid learning rate: %g", o->lr);
     FLSIM_REQUIRE(o->weight_decay >= 0.0, "Invalid weight_decay value: %g", o->weight_decay);
@@ -1304,6 +1327,17 @@ int check_optim(const flsim_optim* o) {
     FLSIM_REQUIRE(o->momentum >= 0.0, "Invalid momentum value: %g", o->momentum);
     FLSIM_REQUIRE(!o->nesterov || (o->momentum > 0.0 && o->dampening == 0.0),
                   "Nesterov momentum requires a momentum and zero dampening");
+    // the two kinds of Adaptive Federated Optimization (lr_decay is read for Adagrad only)
+    if (o->kind == FLSIM_OPT_ADAGRAD)
+        FLSIM_REQUIRE(o->lr_decay >= 0.0, "Invalid lr_decay value: %g", o->lr_decay);
+    if (o->kind == FLSIM_OPT_ADAGRAD || o->kind == FLSIM_OPT_YOGI)
+        FLSIM_REQUIRE(o->eps >= 0.0, "Invalid epsilon value: %g", o->eps);
+    if (o->kind == FLSIM_OPT_YOGI) {
+        FLSIM_REQUIRE(o->beta1 >= 0.0 && o->beta1 < 1.0, "Invalid beta parameter at index 0: %g",
+                      o->beta1);
+        FLSIM_REQUIRE(o->beta2 >= 0.0 && o->beta2 < 1.0, "Invalid beta parameter at index 1: %g",
+                      o->beta2);
+    }
     return 0;
 }
 
@@ -1395,6 +1429,25 @@ int make_opt_launch(const flsim_optim* o, double divisor, long step, OptLaunch* 
                        (step == 1 ? OF_FIRST : 0);
         return 0;
     }
+    if (o->kind == FLSIM_OPT_ADAGRAD || o->kind == FLSIM_OPT_YOGI) {
+        // the constants ride in fields the argument blocks already carry (slabstep.h), each
+        // formed in double and rounded to fp32 once
+        RC(make_divisor(divisor, &ol->ac));
+        FLSIM_REQUIRE(step >= 1, "step must be >= 1");
+        ol->ac.eps = (float)o->eps;
+        ol->oc.wd = (float)o->weight_decay;
+        ol->oc.flags = o->weight_decay != 0.0 ? OF_WD : 0;
+        if (o->kind == FLSIM_OPT_ADAGRAD) {
+            ol->ok = OK_ADAGRAD;
+            ol->oc.neg_lr = (float)(-(o->lr / (1.0 + (double)(step - 1) * o->lr_decay)));
+        } else {
+            ol->ok = OK_YOGI;
+            ol->ac.w1 = (float)(1.0 - o->beta1);
+            ol->ac.w2 = (float)(1.0 - o->beta2);     // the device negates it (exact)
+            ol->oc.neg_lr = (float)(-o->lr);
+        }
+        return 0;
+    }
     RC(make_adam_const(divisor, step, o->lr, o->beta1, o->beta2, o->eps, &ol->ac));
     // no decay: the Adam kernels as they were (AdamW's p * f32(1 - lr * 0) = p exactly)
     ol->ok = o->weight_decay != 0.0 ? OK_ADAMD : OK_ADAM;
@@ -1481,6 +1534,8 @@ static void launch_slab_kind(int ok, bool seq, unsigned nblk, hipStream_t stream
         case OK_ADAM: launch_slab_rule<OK_ADAM, W, C>(seq, nblk, stream, ps, A); break;
         case OK_ADAMD: launch_slab_rule<OK_ADAMD, W, C>(seq, nblk, stream, ps, A); break;
         case OK_SGDM: launch_slab_rule<OK_SGDM, W, C>(seq, nblk, stream, ps, A); break;
+        case OK_ADAGRAD: launch_slab_rule<OK_ADAGRAD, W, C>(seq, nblk, stream, ps, A); break;
+        case OK_YOGI: launch_slab_rule<OK_YOGI, W, C>(seq, nblk, stream, ps, A); break;
         default: launch_slab_rule<OK_SGD, W, C>(seq, nblk, stream, ps, A); break;
     }
 }
@@ -1592,6 +1647,8 @@ static void launch_agg_kind(int ok, bool reg, int G, dim3 grid, hipStream_t stre
         case OK_ADAMD: launch_agg<OK_ADAMD, W, C>(reg, G, grid, stream, ps, A); break;
         case OK_SGDM: launch_agg<OK_SGDM, W, C>(reg, G, grid, stream, ps, A); break;
         case OK_GOUT: launch_agg<OK_GOUT, W, C>(reg, G, grid, stream, ps, A); break;
+        case OK_ADAGRAD: launch_agg<OK_ADAGRAD, W, C>(reg, G, grid, stream, ps, A); break;
+        case OK_YOGI: launch_agg<OK_YOGI, W, C>(reg, G, grid, stream, ps, A); break;
         default: launch_agg<OK_SGD, W, C>(reg, G, grid, stream, ps, A); break;
     }
 }
@@ -1642,6 +1699,14 @@ static int clip_finish_apply(const flsim_clip* clip, long n_part, const OptLaunc
             break;
         case OK_SGDM:
             hipExtLaunchKernelGGL(k_clip_apply<OK_SGDM>, grid, dim3(256), 0, stream, ps.start,
+                                  ps.stop, 0, A);
+            break;
+        case OK_ADAGRAD:
+            hipExtLaunchKernelGGL(k_clip_apply<OK_ADAGRAD>, grid, dim3(256), 0, stream, ps.start,
+                                  ps.stop, 0, A);
+            break;
+        case OK_YOGI:
+            hipExtLaunchKernelGGL(k_clip_apply<OK_YOGI>, grid, dim3(256), 0, stream, ps.start,
                                   ps.stop, 0, A);
             break;
         default:

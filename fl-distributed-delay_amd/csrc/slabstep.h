@@ -153,20 +153,28 @@ struct AdamConst {
 //   OK_SGD    torch.optim.SGD with momentum == 0: p only; m and v untouched
 //   OK_GOUT   no update (the clipped step's first launch, k_agg_stream only): g = rule() is stored
 //             to G and its squares are summed per block; p is read by the C form alone
-enum OptKind { OK_ADAM = 0, OK_ADAMD = 1, OK_SGDM = 2, OK_SGD = 3, OK_GOUT = 4 };
-constexpr int opt_n_state(int ok) { return ok <= OK_ADAMD ? 2 : (ok == OK_SGDM ? 1 : 0); }
+//   OK_ADAGRAD  torch.optim.Adagrad: p and the accumulator `sum` in m; v untouched
+//   OK_YOGI     Yogi in the FedYogi form (no bias correction): p, m, v
+enum OptKind { OK_ADAM = 0, OK_ADAMD = 1, OK_SGDM = 2, OK_SGD = 3, OK_GOUT = 4, OK_ADAGRAD = 5,
+               OK_YOGI = 6 };
+constexpr int opt_n_state(int ok) {
+    return (ok <= OK_ADAMD || ok == OK_YOGI) ? 2 : ((ok == OK_SGDM || ok == OK_ADAGRAD) ? 1 : 0);
+}
 // the same count from a checked flsim_optim (check_optim), before its OptLaunch is made
 inline int optim_n_state(const flsim_optim* o) {
+    if (o->kind == FLSIM_OPT_ADAGRAD) return 1;
     return o->kind == FLSIM_OPT_SGD ? (o->momentum != 0.0 ? 1 : 0) : 2;
 }
 
 // what the kinds other than OK_ADAM need besides AdamConst (whose fk, rk every kind uses)
+// OK_ADAGRAD reads AdamConst.eps and OptConst.wd / neg_lr / flags (OF_WD); OK_YOGI reads
+// AdamConst.w1 / w2 / eps and the same three OptConst fields
 enum { OF_DECOUPLED = 1, OF_WD = 2, OF_NESTEROV = 4, OF_FIRST = 8 };
 struct OptConst {
     float wd;       // weight_decay; OK_ADAMD decoupled: f32(1 - lr * weight_decay)
     float mu;       // momentum
     float omd;      // f32(1 - dampening)
-    float neg_lr;   // f32(-lr)
+    float neg_lr;   // f32(-lr); OK_ADAGRAD: f32(-clr), clr = lr / (1 + (step - 1) * lr_decay)
     int flags;      // OF_*: decoupled decay, weight_decay != 0, nesterov, step 1 (buf = g)
 };
 

@@ -88,7 +88,8 @@ class FlsimClip(ctypes.Structure):
                 ("out", ctypes.c_void_p)]
 
 
-OPT_KINDS = {"adam": 0, "adamw": 1, "sgd": 2}      # FLSIM_OPT_ADAM / _ADAMW / _SGD
+# FLSIM_OPT_ADAM / _ADAMW / _SGD / _ADAGRAD / _YOGI
+OPT_KINDS = {"adam": 0, "adamw": 1, "sgd": 2, "adagrad": 3, "yogi": 4}
 
 
 class FlsimOptim(ctypes.Structure):
@@ -96,7 +97,7 @@ class FlsimOptim(ctypes.Structure):
     _fields_ = [("kind", ctypes.c_int32), ("nesterov", ctypes.c_int32), ("lr", ctypes.c_double),
                 ("beta1", ctypes.c_double), ("beta2", ctypes.c_double), ("eps", ctypes.c_double),
                 ("weight_decay", ctypes.c_double), ("momentum", ctypes.c_double),
-                ("dampening", ctypes.c_double)]
+                ("dampening", ctypes.c_double), ("lr_decay", ctypes.c_double)]
 
 
 class WorkerRec(ctypes.Structure):

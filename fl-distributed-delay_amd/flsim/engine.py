@@ -68,11 +68,34 @@ VGG11_SIZES = [int(np.prod(s)) for _, s in VGG11_SHAPES]
 SAMPLES_PER_WORKER = 128
 
 
+# a kind's conventional defaults where they differ from Optim's own (torch.optim.Adagrad; Yogi as
+# Zaheer et al. 2018 and flsim.optim.Yogi state them)
+OPTIM_DEFAULTS = {
+    "adagrad": dict(lr=1e-2, eps=1e-10, initial_accumulator_value=0.0),
+    "yogi": dict(lr=1e-2, betas=(0.9, 0.99), eps=1e-3, initial_accumulator_value=1e-6),
+}
+
+
+def optim_defaults(kind):
+    """The conventional hyper-parameters of `kind` as a dict of Optim fields (lr, betas, eps,
+    initial_accumulator_value): torch's for "adam", "adamw", "sgd" (lr 1e-3 as main.py:106) and
+    "adagrad", the Yogi paper's for "yogi"."""
+    if kind not in OPT_KINDS:
+        raise ValueError(f"optimizer {kind!r} (supported: {sorted(OPT_KINDS)})")
+    d = dict(lr=1e-3, betas=(0.9, 0.999), eps=1e-8, initial_accumulator_value=0.0)
+    d.update(OPTIM_DEFAULTS.get(kind, {}))
+    return d
+
+
 @dataclasses.dataclass(frozen=True)
 class Optim:
     """flsim_optim (include/flsim.h): the update rule of a server step, torch's hyper-parameter
     names.  kind "adam" = torch.optim.Adam (weight_decay: coupled L2), "adamw" = torch.optim.AdamW
-    (decoupled), "sgd" = torch.optim.SGD (momentum, dampening, weight_decay, nesterov)."""
+    (decoupled), "sgd" = torch.optim.SGD (momentum, dampening, weight_decay, nesterov), "adagrad" =
+    torch.optim.Adagrad (lr_decay, weight_decay, eps; FedAdagrad with beta1 = 0), "yogi" =
+    flsim.optim.Yogi (betas, eps, weight_decay; FedYogi, no bias correction).
+    initial_accumulator_value is what the caller fills the state array with before step 1
+    (Adagrad: m = sum; Yogi: v = exp_avg_sq); the library never initialises state."""
     kind: str = "adam"
     lr: float = 1e-3
     betas: tuple = (0.9, 0.999)
@@ -81,10 +104,15 @@ class Optim:
     momentum: float = 0.0
     dampening: float = 0.0
     nesterov: bool = False
+    lr_decay: float = 0.0
+    initial_accumulator_value: float = 0.0
 
     @property
     def n_state(self):
-        """State arrays the kind owns: 2 (m, v), 1 (the momentum buffer in m) or 0."""
+        """State arrays the kind owns: 2 (m, v), 1 (the momentum buffer or Adagrad's sum in m)
+        or 0."""
+        if self.kind == "adagrad":
+            return 1
         if self.kind != "sgd":
             return 2
         return 1 if self.momentum != 0 else 0
@@ -102,6 +130,18 @@ class Optim:
             raise ValueError(f"Invalid momentum value: {self.momentum}")
         if self.nesterov and (self.momentum <= 0 or self.dampening != 0):
             raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        if self.kind == "adagrad" and not self.lr_decay >= 0:
+            raise ValueError(f"Invalid lr_decay value: {self.lr_decay}")
+        if self.kind in ("adagrad", "yogi"):
+            if not self.initial_accumulator_value >= 0:
+                raise ValueError("Invalid initial_accumulator_value value: "
+                                 f"{self.initial_accumulator_value}")
+            if not self.eps >= 0:
+                raise ValueError(f"Invalid epsilon value: {self.eps}")
+        if self.kind == "yogi":
+            for i, b in enumerate(self.betas):
+                if not 0.0 <= b < 1.0:
+                    raise ValueError(f"Invalid beta parameter at index {i}: {b}")
         return self
 
     def c_struct(self):
@@ -114,6 +154,7 @@ class Optim:
         o.weight_decay = float(self.weight_decay)
         o.momentum = float(self.momentum)
         o.dampening = float(self.dampening)
+        o.lr_decay = float(self.lr_decay)
         return o
 
 
@@ -781,8 +822,8 @@ def aggregate_rule(S, rule, theta, m, v, step, sizes, lr=1e-3, betas=(0.9, 0.999
                    S_out=None, optim=None, theta_out=None, clip=None):
     """rule() + Adam from S_t in a buffer (flsim_aggregate_adam_rule_push; S_out may be None).
     optim (an Optim or a dict of its fields): that update rule instead of Adam(lr, betas, eps)
-    (flsim_aggregate_optim_rule_push); m / v may be None where the kind owns no such array (SGD:
-    v; SGD without momentum: m and v) and are left untouched when given.  clip (a Clip): the
+    (flsim_aggregate_optim_rule_push); m / v may be None where the kind owns no such array (SGD
+    and Adagrad: v; SGD without momentum: m and v) and are left untouched when given.  clip (a Clip): the
     rule's output is clipped to clip.max_norm before the update
     (flsim_aggregate_optim_clip_push); clip.total_norm and clip.coef hold the step's norm and
     factor afterwards."""

@@ -42,8 +42,8 @@ import numpy as np
 import torch
 
 from .data import DevicePool, make_test_pool
-from .engine import (PN1_SIZES, Clip, Optim, ProgramStager, Rule, engine_class, padded,
-                     split_views, staleness_weight)
+from .engine import (PN1_SIZES, Clip, Optim, ProgramStager, Rule, engine_class, optim_defaults,
+                     padded, split_views, staleness_weight)
 from .schedule import Schedule, reference_delays
 
 SEMANTICS = ("reference", "torch1", "independent")
@@ -80,12 +80,13 @@ def load_model_file(path, model="PerformantNet1"):
 class FLSimulation:
     def __init__(self, n_workers, delay=100, delays=None, throttle=False, lr=1e-3, seed=0,
                  semantics="reference", dropout=True, chunk_workers=128, device=None, theta0=None,
-                 group=None, max_throttle=32, pool=None, betas=(0.9, 0.999), eps=1e-8,
+                 group=None, max_throttle=32, pool=None, betas=None, eps=None,
                  engine=None, device_pool=None, test_pool=None, model="PerformantNet1",
                  fused=True, keep_S=False, batch_size=128, distributed=None,
                  collective="torch", optimizer="adam", weight_decay=0.0, momentum=0.0,
                  dampening=0.0, nesterov=False, stale_weight=None, stale_normalize="weights",
-                 delay_comp=None, clip_grad_norm=None):
+                 delay_comp=None, clip_grad_norm=None, lr_decay=0.0,
+                 initial_accumulator_value=None):
         if semantics not in SEMANTICS:
             raise NotImplementedError(f"semantics {semantics!r} (supported: {SEMANTICS})")
         # delay compensation's lambda (None: off); theta is replicated, so at world > 1 every rank
@@ -121,13 +122,24 @@ class FLSimulation:
                                  np.int32)
         self.delay_arg = delay
         self.throttle = bool(throttle)
+        # betas / eps / initial_accumulator_value None: the kind's conventional value (for "adam",
+        # "adamw" and "sgd" (0.9, 0.999), 1e-8 and 0)
+        dflt = optim_defaults(str(optimizer))
+        betas = dflt["betas"] if betas is None else betas
+        eps = dflt["eps"] if eps is None else eps
+        if initial_accumulator_value is None:
+            initial_accumulator_value = dflt["initial_accumulator_value"]
         self.lr, self.betas, self.eps = float(lr), tuple(betas), float(eps)
         # Central(model, optim)'s optimizer (main.py:106 builds Adam(lr)): "adam" (weight_decay:
-        # coupled L2), "adamw" (decoupled) or "sgd" (momentum, dampening, weight_decay, nesterov);
+        # coupled L2), "adamw" (decoupled), "sgd" (momentum, dampening, weight_decay, nesterov),
+        # "adagrad" (lr_decay, weight_decay, initial_accumulator_value; FedAdagrad) or "yogi"
+        # (betas, weight_decay, initial_accumulator_value; FedYogi);
         # refused here, before any device use, where torch's constructor raises ValueError
         self.optim = Optim(kind=str(optimizer), lr=self.lr, betas=self.betas, eps=self.eps,
                            weight_decay=float(weight_decay), momentum=float(momentum),
-                           dampening=float(dampening), nesterov=bool(nesterov)).validate()
+                           dampening=float(dampening), nesterov=bool(nesterov),
+                           lr_decay=float(lr_decay),
+                           initial_accumulator_value=float(initial_accumulator_value)).validate()
         # plain Adam keeps the flsim_aggregate_adam* / flsim_*_server_step entry points
         self._optim_arg = None if (self.optim.kind == "adam" and self.optim.weight_decay == 0) \
             else self.optim
@@ -204,9 +216,15 @@ class FLSimulation:
         th = default_theta(self.seed, model) if theta0 is None else torch.as_tensor(theta0)
         self.theta = th.to(self.device, torch.float32).contiguous().clone()
         # optimizer state: Adam family m = exp_avg, v = exp_avg_sq; SGD with momentum m = the
-        # momentum buffer and no v; SGD without momentum neither
+        # momentum buffer and no v; SGD without momentum neither; Adagrad m = sum and no v, Yogi as
+        # Adam -- their accumulator (Adagrad's sum, Yogi's exp_avg_sq) starts at
+        # initial_accumulator_value
         self.m = torch.zeros_like(self.theta) if self.optim.n_state >= 1 else None
         self.v = torch.zeros_like(self.theta) if self.optim.n_state >= 2 else None
+        if self.optim.kind == "adagrad":
+            self.m.fill_(self.optim.initial_accumulator_value)
+        elif self.optim.kind == "yogi":
+            self.v.fill_(self.optim.initial_accumulator_value)
         self.step = 0
         # [S_t | losses of the computing workers | their per-call BatchNorm statistics (vgg11_bn)]
         # -- one all-reduce per epoch when world > 1 (each rank fills only its workers' rows)
@@ -703,7 +721,8 @@ class FLSimulation:
     def _optim_config(self):
         o = self.optim
         return {"optimizer": o.kind, "weight_decay": o.weight_decay, "momentum": o.momentum,
-                "dampening": o.dampening, "nesterov": o.nesterov}
+                "dampening": o.dampening, "nesterov": o.nesterov, "lr_decay": o.lr_decay,
+                "initial_accumulator_value": o.initial_accumulator_value}
 
     def _stale_config(self):
         """The discount as the checkpoint records it: its spec as a list (None: no discount) and
@@ -737,6 +756,8 @@ class FLSimulation:
         # a checkpoint from before the optimizer was recorded: Adam without weight decay
         for k, v in (("optimizer", "adam"), ("weight_decay", 0.0), ("momentum", 0.0),
                      ("dampening", 0.0), ("nesterov", False),
+                     # ... and from before Adagrad and Yogi: neither hyper-parameter acts
+                     ("lr_decay", 0.0), ("initial_accumulator_value", 0.0),
                      # ... and from before the staleness discount: none
                      ("stale_weight", None), ("stale_normalize", "weights"),
                      # ... and from before delay compensation: off

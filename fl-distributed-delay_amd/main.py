@@ -1,8 +1,10 @@
 """Drop-in for the reference's main.py (main.py:37-212) on MI355X.
 
 Same flags and defaults (main.py:38-53): --n_workers --n_epochs --batch_size --learning_rate
---delay --model_file --throttle.  --optimizer {adam,adamw,sgd} with --momentum --dampening
---nesterov --weight_decay picks the central optimizer (main.py:106 hard-wires Adam(lr)).
+--delay --model_file --throttle.  --optimizer {adam,adamw,sgd,adagrad,yogi} with --momentum
+--dampening --nesterov --weight_decay --lr_decay --initial_accumulator_value --eps --beta1 --beta2
+picks the central optimizer (main.py:106 hard-wires Adam(lr)); adagrad and yogi are FedAdagrad and
+FedYogi (Reddi et al. 2021).
 --stale_weight {none,poly,hinge,const} with --stale_a --stale_b --stale_normalize discounts a stale
 entry by its age before the average (the alternative to --throttle).  --delay_comp LAMBDA
 compensates a stale entry for the distance the model has moved since it was computed (DC-ASGD).
@@ -47,13 +49,24 @@ def parse(argv=None):
     p.add_argument('--model_file', type=str, help='path to model to load (pretrained)')
     p.add_argument('--throttle', action='store_true', help='gradient throttling')
     # build flags
-    p.add_argument('--optimizer', default='adam', choices=['adam', 'adamw', 'sgd'],
+    p.add_argument('--optimizer', default='adam',
+                   choices=['adam', 'adamw', 'sgd', 'adagrad', 'yogi'],
                    help="the central optimizer (main.py:106 builds Adam): torch.optim.Adam "
-                        "(--weight_decay: L2), AdamW (decoupled decay) or SGD")
+                        "(--weight_decay: L2), AdamW (decoupled decay), SGD, Adagrad "
+                        "(FedAdagrad) or Yogi (FedYogi, flsim.optim.Yogi)")
     p.add_argument('--momentum', type=float, default=0.0, help='SGD momentum')
     p.add_argument('--dampening', type=float, default=0.0, help='SGD dampening')
     p.add_argument('--nesterov', action='store_true', help='SGD Nesterov momentum')
     p.add_argument('--weight_decay', type=float, default=0.0, help='weight decay')
+    p.add_argument('--lr_decay', type=float, default=0.0, help='Adagrad learning-rate decay')
+    p.add_argument('--initial_accumulator_value', type=float, default=None,
+                   help="start of Adagrad's sum / Yogi's exp_avg_sq (default: 0 / 1e-6)")
+    p.add_argument('--eps', type=float, default=None,
+                   help="the optimizer's eps (default: the kind's, 1e-8; adagrad 1e-10, yogi 1e-3)")
+    p.add_argument('--beta1', type=float, default=None,
+                   help="Adam family and Yogi: beta1 (default 0.9)")
+    p.add_argument('--beta2', type=float, default=None,
+                   help="Adam family and Yogi: beta2 (default 0.999; yogi 0.99)")
     p.add_argument('--stale_weight', default='none', choices=['none', 'poly', 'hinge', 'const'],
                    help='discount of a stale entry of age tau before the average: poly '
                         '(1+tau)^-a, hinge 1 if tau <= b else 1/(a(tau-b)+1), const a')
@@ -100,6 +113,17 @@ def stale_spec(args):
     return (args.stale_weight, args.stale_a)
 
 
+def optim_kwargs(args):
+    """--lr_decay / --initial_accumulator_value / --eps / --beta1 / --beta2 as FLSimulation's
+    arguments; a flag left out resolves to the kind's default (flsim.engine.optim_defaults)."""
+    from flsim.engine import optim_defaults
+    d = optim_defaults(args.optimizer)
+    betas = (d["betas"][0] if args.beta1 is None else args.beta1,
+             d["betas"][1] if args.beta2 is None else args.beta2)
+    return dict(lr_decay=args.lr_decay, initial_accumulator_value=args.initial_accumulator_value,
+                eps=args.eps, betas=betas)
+
+
 def main(argv=None):
     args = parse(argv)
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -130,7 +154,8 @@ def main(argv=None):
                        weight_decay=args.weight_decay, momentum=args.momentum,
                        dampening=args.dampening, nesterov=args.nesterov,
                        stale_weight=stale_spec(args), stale_normalize=args.stale_normalize,
-                       delay_comp=args.delay_comp, clip_grad_norm=args.clip_grad_norm)
+                       delay_comp=args.delay_comp, clip_grad_norm=args.clip_grad_norm,
+                       **optim_kwargs(args))
     if buffers:
         sim.engine.load_buffers(buffers)
     if args.resume:

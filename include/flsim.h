@@ -368,17 +368,40 @@ int flsim_vgg11_bn_server_step(void* gradstate, float* S_out, const flsim_rule* 
  * weight_decay or momentum, and nesterov with momentum <= 0 or dampening != 0 (where torch
  * raises ValueError) return status 1.  The flsim_aggregate_adam* / flsim_*_server_step entry
  * points above are these with kind = FLSIM_OPT_ADAM and weight_decay = 0.
+ *
+ * FedAdagrad and FedYogi (Reddi et al. 2021, Adaptive Federated Optimization) are two more kinds:
+ *   FLSIM_OPT_ADAGRAD  torch.optim.Adagrad (lr, lr_decay, weight_decay, eps), per element
+ *                        g = fma(p, wd, g) if wd != 0;  sum = fma(g, g, sum);
+ *                        p = p + (f32(-clr) * g) / (sqrt(sum) + eps),
+ *                        clr = lr / (1 + (step - 1) * lr_decay) in double.
+ *                      The accumulator `sum` lives in m; v is neither read nor written and may be
+ *                      NULL.  initial_accumulator_value is what the caller fills m with before
+ *                      step 1 (the library never initialises state).
+ *   FLSIM_OPT_YOGI     Yogi (Zaheer et al. 2018) without bias correction (lr, beta1, beta2, eps,
+ *                      weight_decay: coupled), per element
+ *                        g = fma(p, wd, g) if wd != 0;  m = fma(1 - beta1, g - m, m);
+ *                        g2 = g * g;  v = fma(f32(-(1 - beta2)) * sign(v - g2), g2, v);
+ *                        p = p + (f32(-lr) * m) / (sqrt(v) + eps)
+ *                      with sign(NaN) = 0; m = exp_avg, v = exp_avg_sq (the caller fills v with
+ *                      its initial accumulator value before step 1).
+ * Both take the correctly rounded sqrt, as the Adam kinds do.  Refused with status 1, with
+ * torch's messages: lr_decay < 0 (Adagrad), eps < 0 (both), a beta outside [0, 1) (Yogi), and a
+ * NaN in any of these.
  * ------------------------------------------------------------------------------------------- */
 #define FLSIM_OPT_ADAM 0
 #define FLSIM_OPT_ADAMW 1
 #define FLSIM_OPT_SGD 2
+#define FLSIM_OPT_ADAGRAD 3
+#define FLSIM_OPT_YOGI 4
 typedef struct flsim_optim {
     int32_t kind;     /* FLSIM_OPT_* */
     int32_t nesterov; /* SGD only */
     double lr;
-    double beta1, beta2, eps; /* Adam family */
+    double beta1, beta2, eps; /* Adam family, Yogi; eps: Adagrad too */
     double weight_decay;
     double momentum, dampening; /* SGD only */
+    double lr_decay; /* read only when kind == FLSIM_OPT_ADAGRAD (appended: a caller built against
+                        the struct without it is unaffected for the kinds 0 .. 2) */
 } flsim_optim;
 
 int flsim_aggregate_optim_rule_push(const float* S, float* S_out, const flsim_rule* rule, float* p,

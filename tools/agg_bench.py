@@ -33,6 +33,9 @@ OPTIMS = {      # name -> (the optim= argument, state arrays the kind owns)
     "adamw": (dict(kind="adamw", weight_decay=1e-2), 2),
     "sgdm": (dict(kind="sgd", lr=0.01, momentum=0.9), 1),
     "sgd": (dict(kind="sgd", lr=0.01), 0),
+    # FedAdagrad streams what sgdm streams (p and one state array), FedYogi what adam streams
+    "adagrad": (dict(kind="adagrad", lr=0.01, eps=1e-10), 1),
+    "yogi": (dict(kind="yogi", lr=0.01, betas=(0.9, 0.99), eps=1e-3), 2),
 }
 
 
