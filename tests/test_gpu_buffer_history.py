@@ -77,6 +77,16 @@ class _Ctx:
         self.running = torch.from_numpy(np.concatenate(
             [np.concatenate([rs.normal(0, 0.3, c), rs.uniform(0.5, 2.0, c)])
              for c in MR.VGG_BN_CHANNELS]).astype(np.float32)).to(DEV)
+        self._theta_eval = {}
+
+    def theta_eval(self, model):
+        """The evaluate script's theta: centred for images [3, 303) of the 400-image test pool
+        (vgg11_bn: on the running buffers above, _theta.random_running's)."""
+        import _theta
+        if model not in self._theta_eval:
+            case = _theta.eval_case(model, first=3, n=300, size=400)
+            self._theta_eval[model] = torch.from_numpy(case.theta.copy()).to(DEV)
+        return self._theta_eval[model]
 
 
 class _Script:
@@ -216,10 +226,12 @@ def pn1_input(s):
 
 
 def evaluate(s):
-    """Scenarios 5 and 9.  A ragged evaluation chunk: 300 images from image 3 on."""
+    """Scenarios 5 and 9.  A ragged evaluation chunk: 300 images from image 3 on, at the model's
+    centred theta for those images (tests/_theta.py): the predictions depend on the forward."""
     if s.eng.STATS_PER_WORKER:
         s.eng.running.copy_(s.ctx.running)
-    s.out["pred"] = s.eng.evaluate(s.theta, s.ctx.dtest, first=3, n_images=300)
+    s.out["pred"] = s.eng.evaluate(s.ctx.theta_eval(s.eng.MODEL), s.ctx.dtest, first=3,
+                                   n_images=300)
 
 
 # ---- vgg11 / vgg11_bn (chunk_workers = 3) ---------------------------------------------------

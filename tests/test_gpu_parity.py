@@ -447,26 +447,6 @@ def test_gradient_teacher_forced_decisions(pool, dropout, items):
     _flips.assert_survey(_flips.survey_ratios(g, g_tf32, g_tf, PN1_SHAPES), "pn1_teacher_forced")
 
 
-def test_eval_predictions_match_oracle(pool):
-    """Device evaluation (util.py:31-45, dropout off) vs the oracle's fp32 CPU forward: chunks of
-    256 samples and a ragged last chunk (1000 images), predictions = argmax with first-max ties.
-    Predictions may differ only where two logits are within fp32 noise of each other."""
-    from flsim.data import DevicePool, make_test_pool
-    from flsim.engine import PN1Engine
-    from oracle import model_ref as MR
-    sim = MR.OracleSim(4, delay=2, pool=pool)
-    test = make_test_pool(0, size=1000)
-    eng = PN1Engine(DEV, chunk_workers=2)
-    dtest = DevicePool(DEV, 0, test)
-    theta = torch.from_numpy(sim.theta.copy()).to(DEV)
-    pred = eng.evaluate(theta, dtest).cpu().numpy()
-    ref = MR.predict(sim.theta, test[0])
-    assert pred.shape == (1000,)
-    assert (pred == ref).mean() >= 0.995, (pred != ref).sum()
-    pred2 = eng.evaluate(theta, dtest, first=100, n_images=37).cpu().numpy()
-    assert np.array_equal(pred2, pred[100:137])
-
-
 def test_simulation_evaluate_and_checkpoint_resume(pool, tmp_path):
     """FLSimulation.evaluate returns the reference's accuracy numbers; a run cut in two by
     save_checkpoint / restore continues bit for bit (theta, Adam state, FIFO'd stale gradient)."""

@@ -7,7 +7,9 @@ Tolerances (as tests/test_gpu_parity.py):
     2.5e-4 of |g64| (or 4x the CPU's own fp32 error), or else at most 8 knife-edge decisions
     that fp64 takes the other way, with the teacher-forced gradient exact to TF_TOL;
   * teacher-forced (the GPU's own ReLU / argmax / dropout decisions in an fp64 reference):
-    per-tensor rel-L2 <= TF_TOL, losses to 1e-5;
+    per-tensor rel-L2 <= TF_TOL, losses to 1e-5; at tests/_theta.py's trained_like theta (non-zero
+    conv biases) TF_TOL and the count of 8, both measured at init, are logged, and the bar is
+    SURVEY 8(c) per tensor plus the decisions against the CPU fp32 port's own (tests/_flips.py);
   * losses |dloss| <= 1e-4 on the first step, <= 1e-3 over the first epochs; trace bit-exact.
 """
 import numpy as np
@@ -67,18 +69,11 @@ def _run(theta_np, items, dropout, pool, n_total=4):
     return eng, S.cpu().numpy().astype(np.float64), loss.cpu().numpy()
 
 
-def _teacher_forced(sim, eng, items, dropout, dt=torch.float64):
-    """fp64 VGG-11 forward + backward that takes the GPU's own forward decisions (ReLU signs, max-
-    pool argmax, dropout masks, read back from the workspace).  Returns the per-tensor gradient,
-    the per-worker losses, and the number of GPU decisions that the fp64 pre-activations computed
-    on the way disagree with (a ReLU sign, a pool argmax among live windows, a kept unit whose
-    fp64 pre-activation is <= 0): knife-edge decisions any fp32 order can take either way.
-    dt = torch.float32: the CPU fp32 port given the same decisions (SURVEY 8(c)'s comparison)."""
-    import torch.nn.functional as F
-    import _flips
+def _decisions(eng, items):
+    """The GPU's forward decisions for the chunk the engine ran last, read back from its
+    workspace: the stored activations (a value > 0 = a live ReLU / pooled / kept unit) as NCHW
+    fp32 tensors, the max-pool argmax as NHWC uint8 arrays."""
     from flsim.engine import VGG11Engine
-    from oracle import model_ref as MR
-    from test_gpu_parity import _gather_pool
     NS = 128 * len(items)
     ids = {name: j for j, name in enumerate(VGG11Engine.WORKSPACE)}
 
@@ -86,17 +81,68 @@ def _teacher_forced(sim, eng, items, dropout, dt=torch.float64):
         return eng.workspace_view(ids[name], shp, dt).cpu().numpy()
 
     def nchw(a):
-        return torch.from_numpy(np.ascontiguousarray(a.transpose(0, 3, 1, 2))).to(dt)
+        return torch.from_numpy(np.ascontiguousarray(a.transpose(0, 3, 1, 2)))
 
-    A = dict(d1=nchw(W("d1", (NS, 16, 16, 64))), d2=nchw(W("d2", (NS, 8, 8, 128))),
-             a3=nchw(W("a3", (NS, 8, 8, 256))), d4=nchw(W("d4", (NS, 4, 4, 256))),
-             a5=nchw(W("a5", (NS, 4, 4, 512))), d6=nchw(W("d6", (NS, 2, 2, 512))),
-             a7=nchw(W("a7", (NS, 2, 2, 512))), f0=torch.from_numpy(W("f0", (NS, 512))).to(dt),
-             e1=torch.from_numpy(W("e1", (NS, 512))).to(dt),
-             e2=torch.from_numpy(W("e2", (NS, 512))).to(dt),
-             i1=W("i1", (NS, 16, 16, 64), torch.uint8), i2=W("i2", (NS, 8, 8, 128), torch.uint8),
-             i4=W("i4", (NS, 4, 4, 256), torch.uint8), i6=W("i6", (NS, 2, 2, 512), torch.uint8),
-             i8=W("i8", (NS, 1, 1, 512), torch.uint8))
+    return dict(d1=nchw(W("d1", (NS, 16, 16, 64))), d2=nchw(W("d2", (NS, 8, 8, 128))),
+                a3=nchw(W("a3", (NS, 8, 8, 256))), d4=nchw(W("d4", (NS, 4, 4, 256))),
+                a5=nchw(W("a5", (NS, 4, 4, 512))), d6=nchw(W("d6", (NS, 2, 2, 512))),
+                a7=nchw(W("a7", (NS, 2, 2, 512))), f0=torch.from_numpy(W("f0", (NS, 512))),
+                e1=torch.from_numpy(W("e1", (NS, 512))), e2=torch.from_numpy(W("e2", (NS, 512))),
+                i1=W("i1", (NS, 16, 16, 64), torch.uint8), i2=W("i2", (NS, 8, 8, 128), torch.uint8),
+                i4=W("i4", (NS, 4, 4, 256), torch.uint8), i6=W("i6", (NS, 2, 2, 512), torch.uint8),
+                i8=W("i8", (NS, 1, 1, 512), torch.uint8))
+
+
+def _own_decisions(sim, items, dropout, dt=torch.float32):
+    """The same dict from the CPU port's own forward in dtype dt (models.py:73-77, first-maximum
+    argmax, the build's dropout masks): what _decisions reads from the GPU."""
+    import torch.nn.functional as F
+    import _flips
+    from oracle import model_ref as MR
+    np_dt = np.float64 if dt == torch.float64 else np.float32
+    P = [torch.from_numpy(np.ascontiguousarray(a))
+         for a in MR.split_flat(sim.theta.astype(np_dt), M)]
+    cw, cb = P[0:16:2], P[1:16:2]
+    l1w, l1b, l2w, l2b, l3w, l3b = P[16:]
+    keys = (("i1", "d1"), ("i2", "d2"), (None, "a3"), ("i4", "d4"), (None, "a5"), ("i6", "d6"),
+            (None, "a7"), ("i8", "f0"))
+    out = {}
+    with torch.no_grad():
+        for it in items:
+            h, _ = sim.batch(*it, dtype=dt)
+            noise = MR.dropout_noise(sim.seed, it[0], it[1], 128, dt, M) if dropout else None
+            for j, (ik, ak) in enumerate(keys):
+                z = F.relu(F.conv2d(h, cw[j], cb[j], padding=1))
+                if ik is None:
+                    h = z
+                else:
+                    idx = _flips.pool_idx(z)
+                    h = _flips.gather(z, idx)
+                    out.setdefault(ik, []).append(idx.permute(0, 2, 3, 1).numpy().astype(np.uint8))
+                if ak == "f0":
+                    h = h.reshape(128, 512)
+                    h = h * noise[0] if dropout else h
+                out.setdefault(ak, []).append(h)
+            h = F.relu(F.linear(h, l1w, l1b))
+            h = h * noise[1] if dropout else h
+            out.setdefault("e1", []).append(h)
+            h = F.relu(F.linear(h, l2w, l2b))
+            out.setdefault("e2", []).append(h)
+    return {k: (np.concatenate(v) if k.startswith("i") else torch.cat(v)) for k, v in out.items()}
+
+
+def _forced(sim, A, items, dropout, dt=torch.float64):
+    """fp64 VGG-11 forward + backward at sim.theta that takes the forward decisions A (ReLU
+    signs, max-pool argmax, dropout masks: _decisions' dict).  Returns the per-tensor gradient,
+    the per-worker losses, and the number of decisions that the fp64 pre-activations computed
+    on the way disagree with (a ReLU sign, a pool argmax among live windows, a kept unit whose
+    fp64 pre-activation is <= 0): knife-edge decisions any fp32 order can take either way.
+    dt = torch.float32: the CPU fp32 port given the same decisions (SURVEY 8(c)'s comparison)."""
+    import torch.nn.functional as F
+    import _flips
+    from oracle import model_ref as MR
+    from test_gpu_parity import _gather_pool
+    A = {k: (v.to(dt) if torch.is_tensor(v) else v) for k, v in A.items()}
     np_dt = np.float64 if dt == torch.float64 else np.float32
     P = [torch.tensor(a, requires_grad=True)
          for a in MR.split_flat(sim.theta.astype(np_dt), M)]
@@ -149,6 +195,11 @@ def _teacher_forced(sim, eng, items, dropout, dt=torch.float64):
     return g, lrefs, flips[0]
 
 
+def _teacher_forced(sim, eng, items, dropout, dt=torch.float64):
+    """_forced with the GPU's own forward decisions."""
+    return _forced(sim, _decisions(eng, items), items, dropout, dt)
+
+
 @pytest.mark.parametrize("dropout", [False, True])
 def test_vgg_single_worker_step_gradient(pool, dropout):
     """The GPU gradient of one worker-step against the fp64 oracle with its OWN decisions.  A
@@ -179,18 +230,34 @@ def test_vgg_single_worker_step_gradient(pool, dropout):
         assert _rel_l2(g, g_tf) <= TF_TOL, (e_gpu, flips, _rel_l2(g, g_tf))
 
 
-@pytest.mark.parametrize("dropout,items", [
-    (False, [(0, 1, 2)]), (True, [(0, 1, 2)]), (True, [(1, 0, 3), (1, 2, 0)])])
-def test_vgg_gradient_teacher_forced_decisions(pool, dropout, items):
+@pytest.mark.parametrize("theta,dropout,items", [
+    # (the init cases keep the ids they had before the theta parameter)
+    pytest.param("init", False, [(0, 1, 2)], id="False-items0"),
+    pytest.param("init", True, [(0, 1, 2)], id="True-items1"),
+    pytest.param("init", True, [(1, 0, 3), (1, 2, 0)], id="True-items2"),
+    pytest.param("trained_like", False, [(0, 1, 2)], id="trained_like-False-items0"),
+    pytest.param("trained_like", True, [(1, 0, 3), (1, 2, 0)], id="trained_like-True-items2")])
+def test_vgg_gradient_teacher_forced_decisions(pool, theta, dropout, items):
     """Every backward kernel checked tightly: an fp64 reference that takes the GPU's own forward
     decisions (ReLU signs, max-pool argmax, dropout masks, read back from the workspace) must give
     the GPU's gradient to fp32 accumulation accuracy.  The two-item case is ONE chunk of 256
-    samples whose gradient must be the sum of the per-worker mean-CE gradients (agents.py:35)."""
+    samples whose gradient must be the sum of the per-worker mean-CE gradients (agents.py:35).
+
+    theta = trained_like (tests/_theta.py): every conv bias is non-zero, so a wrong layer offset
+    into the biases or a channel slip in an epilogue changes the forward (losses, decisions) and
+    the bias gradients; at the init theta the biases are all 0.  TF_TOL and the count of 8 were
+    measured at init and are not asserted there: the bar is SURVEY 8(c)'s (relative to the CPU
+    fp32 port under the same decisions), and the GPU's knife-edge decisions against _flips'
+    FLIP_C x the CPU fp32 port's own + FLIP_FLOOR.  The per-tensor rel-L2 is logged."""
+    import _flips
+    import _theta
     from flsim.engine import VGG11_SHAPES
     from oracle import model_ref as MR
-    sim = MR.OracleSim(4, delay=2, pool=pool, dropout=dropout, model=M)
+    theta0 = None if theta == "init" else _theta.trained_like(M)
+    sim = MR.OracleSim(4, delay=2, pool=pool, dropout=dropout, model=M, theta0=theta0)
     eng, g, loss = _run(sim.theta, items, dropout, pool)
-    g_tf, lrefs, flips = _teacher_forced(sim, eng, items, dropout)
+    A = _decisions(eng, items)
+    g_tf, lrefs, flips = _forced(sim, A, items, dropout)
     off = 0
     worst = {}
     for (name, shp) in VGG11_SHAPES:
@@ -199,11 +266,17 @@ def test_vgg_gradient_teacher_forced_decisions(pool, dropout, items):
         off += n
     _tol_log(worst)
     np.testing.assert_allclose(loss, lrefs, atol=1e-5)
-    assert max(worst.values()) <= TF_TOL, worst
-    assert flips <= 8 * len(items), flips
+    if theta == "init":
+        assert max(worst.values()) <= TF_TOL, worst
+        assert flips <= 8 * len(items), flips
+    else:
+        _, _, flips_cpu = _forced(sim, _own_decisions(sim, items, dropout), items, dropout)
+        _flips.log_measured("vgg11_teacher_forced_trained_like", tf_worst=max(worst, key=worst.get),
+                            tf_max=max(worst.values()), tf=worst, flips_gpu=flips,
+                            flips_cpu32=flips_cpu)
+        assert flips <= _flips.FLIP_C * flips_cpu + _flips.FLIP_FLOOR, (flips, flips_cpu)
     # per tensor no farther from fp64 than 2x the CPU fp32 port (same decisions)
-    import _flips
-    g_tf32, _, _ = _teacher_forced(sim, eng, items, dropout, torch.float32)
+    g_tf32, _, _ = _forced(sim, A, items, dropout, torch.float32)
     _flips.assert_survey(_flips.survey_ratios(g, g_tf32, g_tf, VGG11_SHAPES), "vgg11_teacher_forced")
 
 
@@ -233,20 +306,6 @@ def test_vgg_simulation_matches_oracle_trajectory(pool):
         assert [i for (_, i, _) in tr_o["items"]] == list(np.nonzero(plan.computes)[0])
         assert [s for (k, s) in tr_o["appended"] if k == "stale"] == [s for (_, s) in plan.stale]
         assert abs(lg - lo) <= 1e-4, (t, lg, lo)
-
-
-def test_vgg_eval_predictions_match_oracle(pool):
-    """Device evaluation (util.py:31-45, dropout off) of vgg11 vs the oracle's fp32 forward over a
-    ragged 600-image range (chunks of 256); differences only at fp32 near-ties."""
-    from flsim.data import DevicePool, make_test_pool
-    from flsim.engine import VGG11Engine
-    from oracle import model_ref as MR
-    theta = MR.init_params(0, M)
-    test = make_test_pool(0, size=600)
-    eng = VGG11Engine(DEV, chunk_workers=2)
-    pred = eng.evaluate(torch.from_numpy(theta).to(DEV), DevicePool(DEV, 0, test)).cpu().numpy()
-    ref = MR.predict(theta, test[0], model=M)
-    assert (pred == ref).mean() >= 0.99, (pred != ref).sum()
 
 
 def test_vgg_reference_api_facade(pool):

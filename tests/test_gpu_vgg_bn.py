@@ -18,6 +18,8 @@ order.  Tolerances:
     or 10x the CPU's);
   * teacher-forced (the GPU's ReLU / argmax / dropout decisions in an fp64 reference with fp64
     batch statistics): per-tensor rel-L2 <= 7e-6 (conv biases absolute as above), losses 1e-5;
+    at tests/_theta.py's trained_like theta (BatchNorm weights and biases off 1 / 0, conv biases
+    N(0, 1)) the 7e-6, measured at init, is logged and the bar is SURVEY 8(c) per tensor;
   * running buffers: running_var rel 1e-5, running_mean abs 1e-6 after one call (the trajectory
     test: abs 2e-4, see tests/test_oracle_golden._check_running);
   * losses |dloss| <= 1e-4 / 2e-3 / 5e-3 / 1e-2 over epochs 0-3: the near-tie flips above, then
@@ -128,86 +130,129 @@ def test_vgg_bn_single_worker_step_gradient_and_running(pool, dropout):
     np.testing.assert_allclose(got, ref, rtol=1e-5, atol=1e-6)
 
 
-@pytest.mark.parametrize("dropout,items", [
-    (False, [(0, 1, 2)]), (True, [(0, 1, 2)]), (True, [(1, 0, 3), (1, 2, 0)])])
-def test_vgg_bn_gradient_teacher_forced_decisions(pool, dropout, items):
-    """Every backward kernel checked tightly: an fp64 reference that takes the GPU's forward
-    decisions (ReLU signs, max-pool argmax, dropout masks from the workspace) and computes each
-    worker's BatchNorm with fp64 batch statistics must give the GPU's gradient to fp32
-    accumulation accuracy.  Two items = ONE chunk of 256 samples: each worker keeps its own
-    batch statistics, and S is the sum of the per-worker gradients (agents.py:35)."""
-    import torch.nn.functional as F
-    from flsim.engine import VGG11_BN_SHAPES, VGG11BNEngine
-    from oracle import model_ref as MR
-    from test_gpu_parity import _gather_pool
+def _decisions(eng, items):
+    """The GPU's forward decisions for the chunk the engine ran last, read back from its
+    workspace: the stored activations (a value > 0 = a live ReLU / pooled / kept unit) as NCHW
+    fp32 tensors, the max-pool argmax as NHWC uint8 arrays."""
+    from flsim.engine import VGG11BNEngine
     NS = 128 * len(items)
-    sim = MR.OracleSim(4, delay=2, pool=pool, dropout=dropout, model=M)
-    eng, g, loss, stats = _run(sim.theta, items, dropout, pool)
     ids = {name: j for j, name in enumerate(VGG11BNEngine.WORKSPACE)}
 
     def W(name, shp, dt=torch.float32):
         return eng.workspace_view(ids[name], shp, dt).cpu().numpy()
 
     def nchw(a):
-        return torch.from_numpy(np.ascontiguousarray(a.transpose(0, 3, 1, 2))).double()
+        return torch.from_numpy(np.ascontiguousarray(a.transpose(0, 3, 1, 2)))
 
-    A = dict(d1=nchw(W("d1", (NS, 16, 16, 64))), d2=nchw(W("d2", (NS, 8, 8, 128))),
-             a3=nchw(W("a3", (NS, 8, 8, 256))), d4=nchw(W("d4", (NS, 4, 4, 256))),
-             a5=nchw(W("a5", (NS, 4, 4, 512))), d6=nchw(W("d6", (NS, 2, 2, 512))),
-             a7=nchw(W("a7", (NS, 2, 2, 512))), f0=torch.from_numpy(W("f0", (NS, 512))).double(),
-             e1=torch.from_numpy(W("e1", (NS, 512))).double(),
-             e2=torch.from_numpy(W("e2", (NS, 512))).double(),
-             i1=W("i1", (NS, 16, 16, 64), torch.uint8), i2=W("i2", (NS, 8, 8, 128), torch.uint8),
-             i4=W("i4", (NS, 4, 4, 256), torch.uint8), i6=W("i6", (NS, 2, 2, 512), torch.uint8),
-             i8=W("i8", (NS, 1, 1, 512), torch.uint8))
-    def forced(dt):
-        """fp64 (or, for SURVEY 8(c), the CPU fp32 port's) forward + backward with the GPU's
-        decisions and each worker's own batch statistics"""
-        np_dt = np.float64 if dt == torch.float64 else np.float32
-        P = [torch.tensor(a, requires_grad=True)
-             for a in MR.split_flat(sim.theta.astype(np_dt), M)]
-        cw, cb, gw, gb = P[0:32:4], P[1:32:4], P[2:32:4], P[3:32:4]
-        l1w, l1b, l2w, l2b, l3w, l3b = P[32:]
-        Ad = {k: (v.to(dt) if torch.is_tensor(v) else v) for k, v in A.items()}
+    return dict(d1=nchw(W("d1", (NS, 16, 16, 64))), d2=nchw(W("d2", (NS, 8, 8, 128))),
+                a3=nchw(W("a3", (NS, 8, 8, 256))), d4=nchw(W("d4", (NS, 4, 4, 256))),
+                a5=nchw(W("a5", (NS, 4, 4, 512))), d6=nchw(W("d6", (NS, 2, 2, 512))),
+                a7=nchw(W("a7", (NS, 2, 2, 512))), f0=torch.from_numpy(W("f0", (NS, 512))),
+                e1=torch.from_numpy(W("e1", (NS, 512))), e2=torch.from_numpy(W("e2", (NS, 512))),
+                i1=W("i1", (NS, 16, 16, 64), torch.uint8), i2=W("i2", (NS, 8, 8, 128), torch.uint8),
+                i4=W("i4", (NS, 4, 4, 256), torch.uint8), i6=W("i6", (NS, 2, 2, 512), torch.uint8),
+                i8=W("i8", (NS, 1, 1, 512), torch.uint8))
 
-        def m(t):
-            return (t > 0).to(dt)
 
-        def conv(h, j):
-            z = F.conv2d(h, cw[j], cb[j], padding=1)
-            return F.batch_norm(z, None, None, gw[j], gb[j], True, 0.1, 1e-5)
+def _forced(sim, A, items, dropout, dt=torch.float64):
+    """fp64 (or, for SURVEY 8(c), the CPU fp32 port's) forward + backward at sim.theta with the
+    forward decisions A (_decisions' dict) and each worker's own batch statistics.  Returns the
+    parameter tensors, the flat gradient and the per-worker losses."""
+    import torch.nn.functional as F
+    from oracle import model_ref as MR
+    from test_gpu_parity import _gather_pool
+    np_dt = np.float64 if dt == torch.float64 else np.float32
+    P = [torch.tensor(a, requires_grad=True)
+         for a in MR.split_flat(sim.theta.astype(np_dt), M)]
+    cw, cb, gw, gb = P[0:32:4], P[1:32:4], P[2:32:4], P[3:32:4]
+    l1w, l1b, l2w, l2b, l3w, l3b = P[32:]
+    Ad = {k: (v.to(dt) if torch.is_tensor(v) else v) for k, v in A.items()}
 
-        s50 = 2.0 if dropout else 1.0
-        lrefs = []
-        for wi, it in enumerate(items):
-            sl = slice(128 * wi, 128 * (wi + 1))
-            a = {k: v[sl] for k, v in Ad.items()}
-            x, y = sim.batch(*it, dtype=dt)
-            h = _gather_pool(conv(x, 0), a["i1"]) * m(a["d1"])
-            h = _gather_pool(conv(h, 1), a["i2"]) * m(a["d2"])
-            h = conv(h, 2) * m(a["a3"])
-            h = _gather_pool(conv(h, 3), a["i4"]) * m(a["d4"])
-            h = conv(h, 4) * m(a["a5"])
-            h = _gather_pool(conv(h, 5), a["i6"]) * m(a["d6"])
-            h = conv(h, 6) * m(a["a7"])
-            h = _gather_pool(conv(h, 7), a["i8"]).reshape(128, 512) * m(a["f0"]) * s50
-            h = F.linear(h, l1w, l1b) * m(a["e1"]) * s50
-            h = F.linear(h, l2w, l2b) * m(a["e2"])
-            lref = F.cross_entropy(F.linear(h, l3w, l3b), y)
-            lref.backward()
-            lrefs.append(lref.item())
-        return P, torch.cat([p.grad.reshape(-1) for p in P]).double().numpy(), lrefs
+    def m(t):
+        return (t > 0).to(dt)
 
-    P, ref, lrefs = forced(torch.float64)
+    def conv(h, j):
+        z = F.conv2d(h, cw[j], cb[j], padding=1)
+        return F.batch_norm(z, None, None, gw[j], gb[j], True, 0.1, 1e-5)
+
+    s50 = 2.0 if dropout else 1.0
+    lrefs = []
+    for wi, it in enumerate(items):
+        sl = slice(128 * wi, 128 * (wi + 1))
+        a = {k: v[sl] for k, v in Ad.items()}
+        x, y = sim.batch(*it, dtype=dt)
+        h = _gather_pool(conv(x, 0), a["i1"]) * m(a["d1"])
+        h = _gather_pool(conv(h, 1), a["i2"]) * m(a["d2"])
+        h = conv(h, 2) * m(a["a3"])
+        h = _gather_pool(conv(h, 3), a["i4"]) * m(a["d4"])
+        h = conv(h, 4) * m(a["a5"])
+        h = _gather_pool(conv(h, 5), a["i6"]) * m(a["d6"])
+        h = conv(h, 6) * m(a["a7"])
+        h = _gather_pool(conv(h, 7), a["i8"]).reshape(128, 512) * m(a["f0"]) * s50
+        h = F.linear(h, l1w, l1b) * m(a["e1"]) * s50
+        h = F.linear(h, l2w, l2b) * m(a["e2"])
+        lref = F.cross_entropy(F.linear(h, l3w, l3b), y)
+        lref.backward()
+        lrefs.append(lref.item())
+    return P, torch.cat([p.grad.reshape(-1) for p in P]).double().numpy(), lrefs
+
+
+def _tf_errors(g, ref):
+    """What _check_grad bounds, as figures: per-tensor rel-L2, and the conv biases' absolute
+    error against the whole gradient's norm."""
+    from flsim.engine import VGG11_BN_SHAPES
+    off, out, nb = 0, {}, 0.0
+    for (name, shp) in VGG11_BN_SHAPES:
+        n = int(np.prod(shp))
+        if _is_conv_bias(name):
+            nb += float(np.sum((g[off:off + n] - ref[off:off + n]) ** 2))
+        else:
+            out[name] = _rel_l2(g[off:off + n], ref[off:off + n])
+        off += n
+    return out, float(np.sqrt(nb) / np.linalg.norm(ref))
+
+
+@pytest.mark.parametrize("theta,dropout,items", [
+    # (the init cases keep the ids they had before the theta parameter)
+    pytest.param("init", False, [(0, 1, 2)], id="False-items0"),
+    pytest.param("init", True, [(0, 1, 2)], id="True-items1"),
+    pytest.param("init", True, [(1, 0, 3), (1, 2, 0)], id="True-items2"),
+    pytest.param("trained_like", False, [(0, 1, 2)], id="trained_like-False-items0"),
+    pytest.param("trained_like", True, [(1, 0, 3), (1, 2, 0)], id="trained_like-True-items2")])
+def test_vgg_bn_gradient_teacher_forced_decisions(pool, theta, dropout, items):
+    """Every backward kernel checked tightly: an fp64 reference that takes the GPU's forward
+    decisions (ReLU signs, max-pool argmax, dropout masks from the workspace) and computes each
+    worker's BatchNorm with fp64 batch statistics must give the GPU's gradient to fp32
+    accumulation accuracy.  Two items = ONE chunk of 256 samples: each worker keeps its own
+    batch statistics, and S is the sum of the per-worker gradients (agents.py:35).
+
+    theta = trained_like (tests/_theta.py): BatchNorm weights in +-[0.5, 1.5] with channel 0 at
+    exactly 0, BatchNorm biases N(0, 0.5), conv biases N(0, 1): a dropped `* gamma`, a beta that
+    is not added, a wrong layer offset or a channel slip, all invisible at weight 1 / bias 0,
+    change the losses, the statistics and the gradient.  The flat 7e-6 was measured at init and
+    is not asserted there: the bar is SURVEY 8(c)'s, the per-tensor rel-L2 is logged."""
+    import _flips
+    import _theta
+    from flsim.engine import VGG11_BN_SHAPES
+    from oracle import model_ref as MR
+    theta0 = None if theta == "init" else _theta.trained_like(M)
+    sim = MR.OracleSim(4, delay=2, pool=pool, dropout=dropout, model=M, theta0=theta0)
+    eng, g, loss, stats = _run(sim.theta, items, dropout, pool)
+    A = _decisions(eng, items)
+    P, ref, lrefs = _forced(sim, A, items, dropout)
     np.testing.assert_allclose(loss, lrefs, atol=1e-5)
-    # 1.5 x the shipped build's measured worst, 4.57e-6 (features.23.weight, dropout items2;
-    # profiles/r05/tol_r05j.jsonl stores it as 0.0703 of the former 6.5e-5 bound; round 4's build,
-    # data gradients on the split-bf16 MFMA: 4.31e-5)
-    _check_grad(g, ref, rtol=7.0e-6)
+    if theta == "init":
+        # 1.5 x the shipped build's measured worst, 4.57e-6 (features.23.weight, dropout items2;
+        # profiles/r05/tol_r05j.jsonl stores it as 0.0703 of the former 6.5e-5 bound; round 4's
+        # build, data gradients on the split-bf16 MFMA: 4.31e-5)
+        _check_grad(g, ref, rtol=7.0e-6)
+    else:
+        tf, bias_abs = _tf_errors(g, ref)
+        _flips.log_measured("vgg11_bn_teacher_forced_trained_like", tf_worst=max(tf, key=tf.get),
+                            tf_max=max(tf.values()), conv_bias_abs=bias_abs, tf=tf)
     # SURVEY 8(c): per tensor no farther from fp64 than 2x the CPU fp32 port (same decisions);
     # the conv biases ahead of a BatchNorm have an exact gradient of 0 (floor: the whole gradient)
-    import _flips
-    _, ref32, _ = forced(torch.float32)
+    _, ref32, _ = _forced(sim, A, items, dropout, torch.float32)
     _flips.assert_survey(_flips.survey_ratios(
         g, ref32, ref, VGG11_BN_SHAPES,
         whole_floor={n for n, _ in VGG11_BN_SHAPES if _is_conv_bias(n)}), "vgg11_bn_teacher_forced")
@@ -264,22 +309,23 @@ def test_vgg_bn_simulation_matches_oracle_trajectory(pool):
     assert int(mod.features[1].num_batches_tracked) == osim.bn.num_batches_tracked
 
 
-def test_vgg_bn_eval_predictions_match_oracle(pool):
-    """Device evaluation in eval mode (util.py:31-45: BatchNorm with the running buffers, dropout
-    off) vs the oracle's fp32 forward over a ragged 600-image range; near-ties only."""
-    from flsim.data import DevicePool, make_test_pool
-    from flsim.engine import VGG11BNEngine
-    from oracle import model_ref as MR
-    theta = MR.init_params(0, M)
-    rs = np.random.RandomState(3)
-    run = np.concatenate([np.concatenate([rs.normal(0, 0.3, c), rs.uniform(0.5, 2.0, c)])
-                          for c in MR.VGG_BN_CHANNELS]).astype(np.float32)
-    test = make_test_pool(0, size=600)
-    eng = VGG11BNEngine(DEV, chunk_workers=2)
-    eng.running.copy_(torch.from_numpy(run))
-    pred = eng.evaluate(torch.from_numpy(theta).to(DEV), DevicePool(DEV, 0, test)).cpu().numpy()
-    ref = MR.predict(theta, test[0], model=M, bn=run)
-    assert (pred == ref).mean() >= 0.99, (pred != ref).sum()
+def test_vgg_bn_running_update_from_random_buffers(pool):
+    """flsim_vgg11_bn_update_running on a two-worker chunk's statistics, from running buffers that
+    are not the initial (0, 1) -- from those an index slip in the buffers it reads is invisible:
+    r = 0.1 * stat + 0.9 * r folded in worker order in fp64 (nn.BatchNorm2d, momentum 0.1)."""
+    import _theta
+    items = [(1, 0, 3), (1, 2, 0)]
+    run0 = _theta.random_running()
+    eng, _, _, stats = _run(_theta.trained_like(M), items, True, pool)
+    eng.running.copy_(torch.from_numpy(run0))
+    eng.update_running(stats, 2)
+    assert eng.num_batches_tracked == 2
+    st = stats.double().cpu().numpy()
+    assert st.shape == (2, run0.size) and np.abs(st[0] - st[1]).max() > 1e-3
+    ref = run0.astype(np.float64)
+    for w in range(2):
+        ref = 0.1 * st[w] + 0.9 * ref
+    np.testing.assert_allclose(eng.running.double().cpu().numpy(), ref, rtol=1e-5, atol=1e-6)
 
 
 def test_vgg_bn_reference_api_facade(pool):
