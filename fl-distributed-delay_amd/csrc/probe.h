@@ -19,8 +19,9 @@ enum KernelId {
     K_VWG1, K_VWG2, K_VWG3, K_VWG4, K_VWG5, K_VWG6, K_VWG7, K_VWG8,
     K_VL1W, K_VL1D, K_VL2W, K_VL2D,
     // server step (server.hip): general-order aggregation, fused slab step (reference / general
-    // order), slab reduction only; the clipped step's three launches (rule -> G, finish, apply)
-    K_AGG_SEQ, K_STEP, K_STEP_SEQ, K_SLABSUM, K_AGG_GOUT, K_CLIP_FIN, K_CLIP_APPLY, K_COUNT
+    // order), slab reduction only; the clipped step's three launches (rule -> G, finish, apply);
+    // the robust step (median / trimmed mean + update)
+    K_AGG_SEQ, K_STEP, K_STEP_SEQ, K_SLABSUM, K_AGG_GOUT, K_CLIP_FIN, K_CLIP_APPLY, K_ROBUST, K_COUNT
 };
 
 // Event pair for the launch that follows (nullptr events when the probe is off or full).  The

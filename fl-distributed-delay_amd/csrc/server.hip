@@ -39,6 +39,7 @@
 #include "common.h"
 #include "flsim.h"
 #include "probe.h"
+#include "robust.h"
 #include "slabstep.h"
 
 #ifndef FLSIM_SEQ_EARLY_EXIT
@@ -1719,6 +1720,140 @@ static int clip_finish_apply(const flsim_clip* clip, long n_part, const OptLaunc
     return probe_end(ps, K_CLIP_APPLY, 4.0 * (double)P * (3 + 2 * opt_n_state(ol.ok)));
 }
 
+// ================================================================================================
+// k_robust: coordinate-wise median / trimmed mean over k <= 64 bucket means + the update
+// (include/flsim.h: flsim_robust; csrc/robust.h: the network and select / sum, shared with the host)
+// ================================================================================================
+struct RobustArgs {
+    const float* ent[RULE_MAX_ARR];     // bucket / class sums; nullptr = an all-zero entry
+    float cnt[RULE_MAX_ARR];            // (float)count[j] and RN(1 / that): x_j = ent[j][e] / cnt[j]
+    float rcnt[RULE_MAX_ARR];
+    float* g_out;                       // nullable: g is also written here
+    float* G;                           // OK_GOUT, nullable: the clipped step's G
+    double* partials;                   // OK_GOUT, nullable: block b's sum of g * g (fp64)
+    float* p;
+    float* m;
+    float* v;
+    long P;
+    int k, kind, trim;
+    float fn;                           // (float)(k - 2 * trim): the trimmed mean's divisor
+    AdamConst ac;
+    OptConst oc;
+};
+static_assert(sizeof(RobustArgs) <= 4096, "kernel argument block");
+
+// One thread owns one element (a float4 group per thread was measured too, at k = 2 .. 16: it
+// needs four times the registers and is slower at every k, profiles/robust/README.md).  All k loads
+// of a thread are issued before any arithmetic, non-temporally (each byte is read once; a wave's
+// load is one coalesced 256 B row); then p / m / v; then the k divisions, the keys, the network,
+// select / sum and the update of kind OK.  KPAD is the network's size, not k: the runtime k, kind
+// and trim are launch-uniform (scalar branches skip the loads past k).
+// OK_GOUT has no update: g goes to g_out and / or G, and with `partials` every thread of the block
+// stays for the block's fp64 sum of squares (one out of range adds 0).
+template <int KPAD, int OK>
+__global__ void __launch_bounds__(256) k_robust(RobustArgs A) {
+    constexpr bool HAS_M = opt_n_state(OK) >= 1, HAS_V = opt_n_state(OK) == 2;
+    const long e = (long)blockIdx.x * 256 + threadIdx.x;
+    const bool live = e < A.P;
+    if constexpr (OK != OK_GOUT) {
+        if (!live) return;
+    }
+    float x[KPAD];
+#pragma unroll
+    for (int j = 0; j < KPAD; ++j)
+        x[j] = (j < A.k && A.ent[j] && live) ? __builtin_nontemporal_load(A.ent[j] + e) : 0.f;
+    float p = 0.f, m = 0.f, v = 0.f;
+    if constexpr (OK != OK_GOUT) p = __builtin_nontemporal_load(A.p + e);
+    if constexpr (HAS_M) m = __builtin_nontemporal_load(A.m + e);
+    if constexpr (HAS_V) v = __builtin_nontemporal_load(A.v + e);
+    uint32_t key[KPAD];
+#pragma unroll
+    for (int j = 0; j < KPAD; ++j)
+        key[j] = j < A.k ? robust_key(div_const(x[j], A.cnt[j], A.rcnt[j])) : ROBUST_PAD;
+    float g = robust_select<KPAD>(key, A.kind, A.trim, A.k);
+    if (A.kind != FLSIM_ROBUST_MEDIAN) g = __fdiv_rn(g, A.fn);
+    if constexpr (OK == OK_GOUT) {
+        if (live) {
+            if (A.g_out) __builtin_nontemporal_store(g, A.g_out + e);
+            if (A.G) __builtin_nontemporal_store(g, A.G + e);
+        }
+        if (A.partials) {
+            __shared__ double red[4];
+            const double t = block_sum_f64(live ? (double)g * (double)g : 0.0, red);
+            if (threadIdx.x == 0) A.partials[blockIdx.x] = t;
+        }
+    } else {
+        if (A.g_out) __builtin_nontemporal_store(g, A.g_out + e);
+        opt_update<OK>(A.ac, A.oc, g, p, m, v);
+        __builtin_nontemporal_store(p, A.p + e);
+        if constexpr (HAS_M) __builtin_nontemporal_store(m, A.m + e);
+        if constexpr (HAS_V) __builtin_nontemporal_store(v, A.v + e);
+    }
+}
+
+template <int KPAD>
+static void launch_robust(int ok, dim3 grid, hipStream_t stream, const ProbeSlot& ps,
+                          const RobustArgs& A) {
+#define FLSIM_ROBUST_CASE(K)                                                                   \
+    case K:                                                                                    \
+        hipExtLaunchKernelGGL((k_robust<KPAD, K>), grid, dim3(256), 0, stream, ps.start,       \
+                              ps.stop, 0, A);                                                  \
+        break;
+    switch (ok) {
+        FLSIM_ROBUST_CASE(OK_ADAM)
+        FLSIM_ROBUST_CASE(OK_ADAMD)
+        FLSIM_ROBUST_CASE(OK_SGDM)
+        FLSIM_ROBUST_CASE(OK_GOUT)
+        FLSIM_ROBUST_CASE(OK_ADAGRAD)
+        FLSIM_ROBUST_CASE(OK_YOGI)
+        default:
+            hipExtLaunchKernelGGL((k_robust<KPAD, OK_SGD>), grid, dim3(256), 0, stream,
+                                  ps.start, ps.stop, 0, A);
+            break;
+    }
+#undef FLSIM_ROBUST_CASE
+}
+
+// flsim_robust's hyper-parameters; before any pointer check, like check_optim
+static int check_robust(const flsim_robust* r) {
+    FLSIM_REQUIRE(r, "null robust rule");
+    FLSIM_REQUIRE(r->kind == FLSIM_ROBUST_MEDIAN || r->kind == FLSIM_ROBUST_TRIMMED_MEAN,
+                  "unknown robust rule kind %d", r->kind);
+    FLSIM_REQUIRE(r->k >= 1 && r->k <= RULE_MAX_ARR, "robust rule over k = %d entries (1 .. %d)",
+                  r->k, RULE_MAX_ARR);
+    FLSIM_REQUIRE(r->trim >= 0 && r->trim <= RULE_MAX_ARR && 2 * r->trim < r->k,
+                  "Invalid trim %d for k = %d entries: 0 <= 2 * trim < k", r->trim, r->k);
+    FLSIM_REQUIRE(r->kind != FLSIM_ROBUST_MEDIAN || r->trim == 0,
+                  "the median takes no trim (trim = %d)", r->trim);
+    for (int j = 0; j < r->k; ++j)
+        FLSIM_REQUIRE(r->count[j] >= 1, "Invalid count %d of entry %d: it must be >= 1",
+                      r->count[j], j);
+    return 0;
+}
+
+// the host twin's element: the same divisions, keys, network and select / sum as k_robust
+template <int KPAD>
+static void robust_eval_host(const flsim_robust* r, long P, float* g_out) {
+    for (long e = 0; e < P; ++e) {
+        uint32_t key[KPAD];
+        for (int j = 0; j < KPAD; ++j) {
+            if (j >= r->k) {
+                key[j] = ROBUST_PAD;
+                continue;
+            }
+            volatile float x = r->entries[j] ? r->entries[j][e] : 0.f;
+            volatile float c = (float)r->count[j];
+            key[j] = robust_key(x / c);
+        }
+        float g = robust_select<KPAD>(key, r->kind, r->trim, r->k);
+        if (r->kind != FLSIM_ROBUST_MEDIAN) {
+            volatile float s = g, n = (float)(r->k - 2 * r->trim);
+            g = s / n;
+        }
+        g_out[e] = g;
+    }
+}
+
 }  // namespace flsim
 
 using namespace flsim;
@@ -1781,7 +1916,9 @@ int flsim_aggregate_optim_crule_push(const float* S, float* S_out, float* theta_
 // the doubles a clipped step over P elements writes, for any layout of at most 4096 tensors: a
 // launch covers at most MAX_TAILS tensor tails, so at most 513 launches; a launch over n
 // elements has at most n / 1024 + 2 streaming blocks, and each streaming block that is an edge
-// block adds 4 * G <= 8 edge pieces
+// block adds 4 * G <= 8 edge pieces.  The robust step (flsim_robust_optim_step) is one launch
+// without edge pieces, one partial per block of 256 elements: ceil(P / 256) <= 4 * (P / 1024) + 4
+// of them, inside this bound
 long flsim_clip_partials(long P) {
     if (P < 0) return 0;
     return 9 * (P / 1024 + 2 * (4096 / MAX_TAILS + 1));
@@ -2114,6 +2251,121 @@ int flsim_cascade_eval_host_clip(const int32_t* prog, const int32_t* info, const
     for (long e = 0; e < n; ++e) g_out[e] = g_out[e] * coef;
     norm_coef[0] = t;
     norm_coef[1] = coef;
+    return 0;
+}
+
+// ---- robust rules: median / trimmed mean over bucket means + the update (include/flsim.h) --------
+// One launch of k_robust in the optimizer's kind; optim == NULL: OK_GOUT writing g_out alone; clip:
+// OK_GOUT writing clip->G and the per-block partials, then k_clip_finish and k_clip_apply as the
+// clipped entry point above runs them.
+int flsim_robust_optim_step(const flsim_robust* r, const flsim_clip* clip, float* g_out, float* p,
+                            float* m, float* v, long P, long step, const flsim_optim* optim,
+                            hipStream_t stream) {
+    RC(check_robust(r));
+    if (optim) RC(check_optim(optim));
+    RC(check_clip(clip));
+    FLSIM_REQUIRE(optim || (g_out && !clip), "null optimizer (only a step that writes g_out alone, "
+                  "unclipped, takes none)");
+    OptLaunch ol{};
+    ol.ok = OK_GOUT;
+    int nstate = 0;
+    if (optim) {
+        nstate = optim_n_state(optim);
+        RC(make_opt_launch(optim, 1.0, step, &ol));
+        FLSIM_REQUIRE(p && (m || nstate < 1) && (v || nstate < 2), "null pointer");
+    } else {
+        p = nullptr;
+    }
+    if (nstate < 2) v = nullptr;
+    if (nstate < 1) m = nullptr;
+    FLSIM_REQUIRE(P > 0 && P < (1L << 31), "P = %ld out of range", P);
+    FLSIM_REQUIRE((((uintptr_t)p | (uintptr_t)m | (uintptr_t)v | (uintptr_t)g_out) & 15) == 0,
+                  "p/m/v/g_out must be 16-byte aligned");
+    const float* const outs[] = {p, m, v, g_out};
+    for (int a = 0; a < 4; ++a)
+        for (int b = a + 1; b < 4; ++b)
+            FLSIM_REQUIRE(!overlaps(outs[a], outs[b], P), "p/m/v/g_out overlap each other");
+    long n_part = 0;
+    if (clip) {
+        FLSIM_REQUIRE(clip->G && clip->partials && clip->out, "null clip buffer");
+        FLSIM_REQUIRE((((uintptr_t)clip->G | (uintptr_t)clip->partials | (uintptr_t)clip->out) &
+                       15) == 0, "clip G/partials/out must be 16-byte aligned");
+        for (const float* o : outs)
+            FLSIM_REQUIRE(!overlaps(clip->G, o, P), "clip G overlaps p/m/v/g_out");
+    }
+    RobustArgs A{};
+    for (int j = 0; j < r->k; ++j) {
+        const float* e = r->entries[j];
+        FLSIM_REQUIRE(((uintptr_t)e & 3) == 0, "entry %d must be 4-byte aligned", j);
+        for (const float* o : outs)
+            FLSIM_REQUIRE(!overlaps(e, o, P), "entry %d overlaps p/m/v/g_out", j);
+        FLSIM_REQUIRE(!clip || !overlaps(e, clip->G, P), "entry %d overlaps clip G", j);
+        A.ent[j] = e;
+        volatile float one = 1.f, c = (float)r->count[j];    // RN(1 / count) in fp32
+        A.cnt[j] = c;
+        A.rcnt[j] = one / c;
+    }
+    const int kpad = robust_kpad(r->k);
+    const long nblk = (P + 255) / 256;
+    if (clip) {
+        n_part = nblk;
+        FLSIM_REQUIRE(clip->n_partials >= n_part, "clip n_partials = %ld, this step writes %ld",
+                      clip->n_partials, n_part);
+    }
+    A.g_out = g_out;
+    A.G = clip ? clip->G : nullptr;
+    A.partials = clip ? clip->partials : nullptr;
+    A.p = p;
+    A.m = m;
+    A.v = v;
+    A.P = P;
+    A.k = r->k;
+    A.kind = r->kind;
+    A.trim = r->trim;
+    A.fn = (float)(r->k - 2 * r->trim);
+    A.ac = ol.ac;
+    A.oc = ol.oc;
+    const int ok_launch = clip ? (int)OK_GOUT : ol.ok;
+    int distinct = 0;
+    for (int j = 0; j < r->k; ++j) {
+        bool seen = r->entries[j] == nullptr;
+        for (int s = 0; s < j && !seen; ++s) seen = r->entries[s] == r->entries[j];
+        distinct += !seen;
+    }
+    // algorithmic HBM bytes: each distinct entry read once; g_out / G written; p and the kind's
+    // state arrays read + written (not by a launch that only writes g)
+    const int nst_launch = ok_launch == OK_GOUT ? 0 : nstate;
+    const double bytes = 4.0 * (double)P * (distinct + (g_out ? 1 : 0) + (clip ? 1 : 0) +
+                                            (ok_launch == OK_GOUT ? 0 : 2 + 2 * nst_launch));
+    const ProbeSlot ps = probe_begin();
+    const dim3 grid((unsigned)nblk);
+    switch (kpad) {
+        case 2: launch_robust<2>(ok_launch, grid, stream, ps, A); break;
+        case 4: launch_robust<4>(ok_launch, grid, stream, ps, A); break;
+        case 8: launch_robust<8>(ok_launch, grid, stream, ps, A); break;
+        case 16: launch_robust<16>(ok_launch, grid, stream, ps, A); break;
+        case 32: launch_robust<32>(ok_launch, grid, stream, ps, A); break;
+        default: launch_robust<64>(ok_launch, grid, stream, ps, A); break;
+    }
+    FLSIM_LAUNCH_CHECK();
+    if (probe_end(ps, K_ROBUST, bytes)) return 2;
+    if (!clip) return 0;
+    return clip_finish_apply(clip, n_part, ol, p, m, v, P, stream);
+}
+
+// host (testing): g of the rule text for host pointers, through robust.h's network and select / sum
+int flsim_robust_eval_host(const flsim_robust* r, long P, float* g_out) {
+    RC(check_robust(r));
+    FLSIM_REQUIRE(g_out, "null pointer");
+    FLSIM_REQUIRE(P > 0, "P = %ld out of range", P);
+    switch (robust_kpad(r->k)) {
+        case 2: robust_eval_host<2>(r, P, g_out); break;
+        case 4: robust_eval_host<4>(r, P, g_out); break;
+        case 8: robust_eval_host<8>(r, P, g_out); break;
+        case 16: robust_eval_host<16>(r, P, g_out); break;
+        case 32: robust_eval_host<32>(r, P, g_out); break;
+        default: robust_eval_host<64>(r, P, g_out); break;
+    }
     return 0;
 }
 

@@ -50,6 +50,7 @@ EXPORTS = [
     "flsim_vgg11_server_step_crule", "flsim_vgg11_bn_server_step_crule",
     "flsim_cascade_eval_host_c",
     "flsim_clip_partials", "flsim_aggregate_optim_clip_push", "flsim_cascade_eval_host_clip",
+    "flsim_robust_optim_step", "flsim_robust_eval_host",
 ]
 COMM_ID_BYTES = 128      # FLSIM_COMM_ID_BYTES
 
@@ -86,6 +87,16 @@ class FlsimClip(ctypes.Structure):
     _fields_ = [("max_norm", ctypes.c_float), ("G", ctypes.c_void_p),
                 ("partials", ctypes.c_void_p), ("n_partials", ctypes.c_long),
                 ("out", ctypes.c_void_p)]
+
+
+# FLSIM_ROBUST_MEDIAN / _TRIMMED_MEAN
+ROBUST_KINDS = {"median": 0, "trimmed_mean": 1}
+
+
+class FlsimRobust(ctypes.Structure):
+    """flsim_robust (include/flsim.h): a robust rule over k bucket / class sums and their counts."""
+    _fields_ = [("kind", ctypes.c_int32), ("trim", ctypes.c_int32), ("k", ctypes.c_int32),
+                ("entries", ctypes.c_void_p * MAX_ARRAYS), ("count", ctypes.c_int32 * MAX_ARRAYS)]
 
 
 # FLSIM_OPT_ADAM / _ADAMW / _SGD / _ADAGRAD / _YOGI
@@ -211,6 +222,9 @@ def lib():
     L.flsim_cascade_eval_host_clip.argtypes = [
         vp, vp, vp, vp, vp, ctypes.c_int, ctypes.c_double, vp, vp, ctypes.c_double, vp,
         ctypes.c_long, ctypes.c_double, vp, vp]
+    L.flsim_robust_optim_step.argtypes = [vp, vp, vp, vp, vp, vp, ctypes.c_long, ctypes.c_long, vp,
+                                          vp]
+    L.flsim_robust_eval_host.argtypes = [vp, ctypes.c_long, vp]
     L.flsim_cascade_program.argtypes = [ctypes.c_int, vp, vp, ctypes.c_int, vp, ctypes.c_int, vp]
     L.flsim_cascade_eval_host.argtypes = [vp, vp, vp, vp, ctypes.c_int, vp, ctypes.c_long, vp]
     L.flsim_probe_enable.argtypes = [ctypes.c_int]

@@ -20,8 +20,9 @@ import torch
 
 import math
 
-from ._lib import (MAX_ARRAYS, OPT_KINDS, FlsimClip, FlsimOptim, FlsimRule, FlsimRuleComp,
-                   FlsimRuleWeights, WorkerRec, check, lib, ptr, stream_ptr)
+from ._lib import (MAX_ARRAYS, OPT_KINDS, ROBUST_KINDS, FlsimClip, FlsimOptim, FlsimRobust,
+                   FlsimRule, FlsimRuleComp, FlsimRuleWeights, WorkerRec, check, lib, ptr,
+                   stream_ptr)
 
 # named_parameters() order of models.py:PerformantNet1 (models.py:13-25)
 PN1_SHAPES = [
@@ -456,6 +457,13 @@ class NetEngine:
         aggregate_rule(S, rule, theta, m, v, step, self.SIZES, lr, betas, eps, S_out=S_out,
                        optim=optim, theta_out=theta_out, clip=clip)
 
+    def robust_step(self, robust, theta, m, v, step, lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
+                    optim=None, clip=None, g_out=None):
+        """A robust rule (a Robust: median / trimmed mean over bucket sums) + Adam (or the update
+        rule `optim`) over this network's P parameters; clip (a Clip) and g_out as robust_step."""
+        robust_step(robust, theta, m, v, step, self.P, lr, betas, eps, optim=optim, clip=clip,
+                    g_out=g_out)
+
 
 class PN1Engine(NetEngine):
     PREFIX = "pn1"
@@ -866,6 +874,60 @@ def aggregate_rule(S, rule, theta, m, v, step, sizes, lr=1e-3, betas=(0.9, 0.999
         ptr(S), ptr(S_out), ctypes.byref(rule.c_rule), ptr(theta), ptr(m), ptr(v),
         sum(int(n) for n in sizes), csz, len(sizes), int(step), float(lr), float(betas[0]),
         float(betas[1]), float(eps), stream_ptr()))
+
+
+class Robust:
+    """A robust rule over bucket / class sums (flsim_robust, include/flsim.h): kind "median" (the
+    coordinate-wise lower median) or "trimmed_mean" (per coordinate the `trim` lowest and highest
+    values dropped, the rest averaged), over the k = len(entries) values entries[j] / counts[j].
+    entries: flat fp32 device tensors of the same length, or None (an all-zero entry); counts: the
+    number of workers summed into each (>= 1).  flsim/robust.py is the rule's text."""
+
+    def __init__(self, kind, trim, entries, counts):
+        entries, counts = list(entries), [int(c) for c in counts]
+        if len(entries) != len(counts):
+            raise ValueError(f"{len(counts)} counts for {len(entries)} entries")
+        if len(entries) > MAX_ARRAYS:
+            raise ValueError(f"robust rule over k = {len(entries)} entries (1 .. {MAX_ARRAYS})")
+        self.kind, self.trim = kind, int(trim)
+        self.entries, self.counts = entries, counts     # (the rule keeps the tensors alive)
+
+    @property
+    def k(self):
+        return len(self.entries)
+
+    def c_struct(self):
+        r = FlsimRobust()
+        r.kind = ROBUST_KINDS.get(self.kind, -1)
+        r.trim = self.trim
+        r.k = len(self.entries)
+        for j, (e, c) in enumerate(zip(self.entries, self.counts)):
+            r.entries[j] = e.data_ptr() if e is not None else None
+            # (an int32 field: a count it cannot hold is refused as the library refuses one < 1)
+            r.count[j] = c if -2 ** 31 <= c < 2 ** 31 else 0
+        return r
+
+
+def robust_step(robust, theta, m, v, step, P=None, lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
+                optim=None, clip=None, g_out=None):
+    """The robust rule + Adam(lr, betas, eps), or the update rule `optim` (an Optim or a dict of its
+    fields), in one launch (flsim_robust_optim_step); m / v may be None where the kind owns no such
+    array.  clip (a Clip): the rule's output is clipped to clip.max_norm before the update.  g_out
+    (optional): the rule's output is also written there; optim=False with g_out runs the rule
+    alone and touches none of theta / m / v (theta may then be None)."""
+    if optim is False:
+        o = None
+    else:
+        o = ctypes.byref((as_optim(optim) if optim is not None else
+                          Optim(lr=lr, betas=tuple(betas), eps=eps)).c_struct())
+    if P is None:
+        P = int((theta if theta is not None else g_out).numel())
+    r = robust.c_struct()
+    dev = next((t.device for t in (theta, g_out, *robust.entries) if t is not None), None)
+    c = ctypes.byref(clip.c_struct(dev, int(P))) if clip is not None else None
+    check(lib().flsim_robust_optim_step(
+        ctypes.byref(r), c, ptr(g_out), ptr(theta), ptr(m), ptr(v), int(P), int(step), o,
+        stream_ptr()))
 
 
 def worker_table(recs, device):

@@ -44,6 +44,7 @@ import torch
 from .data import DevicePool, make_test_pool
 from .engine import (PN1_SIZES, Clip, Optim, ProgramStager, Rule, engine_class, optim_defaults,
                      padded, split_views, staleness_weight)
+from .robust import parse_rule
 from .schedule import Schedule, reference_delays
 
 SEMANTICS = ("reference", "torch1", "independent")
@@ -86,9 +87,23 @@ class FLSimulation:
                  collective="torch", optimizer="adam", weight_decay=0.0, momentum=0.0,
                  dampening=0.0, nesterov=False, stale_weight=None, stale_normalize="weights",
                  delay_comp=None, clip_grad_norm=None, lr_decay=0.0,
-                 initial_accumulator_value=None):
+                 initial_accumulator_value=None, robust_rule=None, buckets=8,
+                 keep_entries=False):
         if semantics not in SEMANTICS:
             raise NotImplementedError(f"semantics {semantics!r} (supported: {SEMANTICS})")
+        # a robust rule in place of the mean (None: off; today's code paths exactly): (kind, trim)
+        self.robust = parse_rule(robust_rule)
+        self.buckets = int(buckets)
+        self.keep_entries = bool(keep_entries)
+        self.last_entries = None
+        if self.robust is not None:
+            if self.buckets < 1:
+                raise ValueError(f"buckets = {self.buckets}: it must be >= 1")
+            if semantics != "independent":
+                # under the reference's aliasing weight_ups is [S_t] * c + the stale entries: its
+                # median is trivially S_t
+                raise NotImplementedError(f"robust_rule with semantics {semantics!r}: the entries "
+                                          "must be distinct (semantics='independent')")
         # delay compensation's lambda (None: off); theta is replicated, so at world > 1 every rank
         # keeps the same snapshots locally
         self.delay_comp = None if delay_comp is None else float(delay_comp)
@@ -174,6 +189,9 @@ class FLSimulation:
         # streaming server step after it).  Default: on iff world > 1; True at world = 1 runs that
         # path over a one-rank process group (bench.py --force-dist: RCCL on a single GPU)
         self.distributed = self.world > 1 if distributed is None else bool(distributed)
+        if self.robust is not None and (self.distributed or self.world > 1):
+            raise NotImplementedError("robust_rule with distributed runs: the epoch's entries "
+                                      "would need an all-gather")
         if self.distributed and not (dist.is_available() and dist.is_initialized()):
             raise RuntimeError("distributed=True needs an initialised torch.distributed group")
         # the epoch's one all-reduce: "torch" = torch.distributed (RCCL with the nccl backend);
@@ -431,6 +449,8 @@ class FLSimulation:
         plan = self.sched.next_epoch()
         t = plan.t
         ks = self.rs.randint(0, self.n, size=self.n)
+        if self.robust is not None:
+            return self._epoch_robust(plan, ks, sync_loss)
         if self.semantics == "independent":
             return self._epoch_independent(plan, ks, sync_loss)
         active = np.nonzero(plan.computes)[0]
@@ -628,6 +648,95 @@ class FLSimulation:
         self.loss_log.append((losses.detach().clone(), np.arange(len(fast))))
         return None
 
+    def _epoch_robust(self, plan, ks, sync_loss):
+        """A robust rule over bucket means (world = 1, independent entries).  The epoch's fast
+        workers are split into `buckets` contiguous buckets, each one begin_epoch / chunks /
+        end_epoch pass into a slot of its own (the bucket's SUM; its count = the bucket size) --
+        the pattern the delay classes already follow, at no extra GEMM work.  The entries of the
+        rule are the fresh buckets, then the popped delay-class slots in pop order (count = the
+        popped workers sharing the slot); one fused robust step (median / trimmed mean of the
+        entries' means + the update) follows, clipped if configured."""
+        from .engine import Robust
+        from .schedule import DELAY_ZERO
+        t = plan.t
+        eng = self.engine
+        active = np.nonzero(plan.computes)[0]
+        slow_mask = self.delays[active] != 0
+        fast, slow = active[~slow_mask], active[slow_mask]
+
+        def dclass(i):
+            d = int(self.delays[i])
+            return 0 if d == DELAY_ZERO else abs(d)
+        classes = {}
+        for i in slow:
+            classes.setdefault(dclass(i), []).append(int(i))
+        own = sorted(classes.items())
+        losses = self.comm[self.Ppad:self.Ppad + len(fast)]
+        own_workers = np.asarray([i for _, ws in own for i in ws], np.int64)
+        wt = self._worker_table(t, np.concatenate([own_workers, fast]), ks)
+        cw = self.engine.chunk_workers
+        if getattr(self, "_slow_loss", None) is None or self._slow_loss.numel() < cw:
+            self._slow_loss = torch.zeros(cw, device=self.device)
+        off = 0
+        for d, ws in own:                        # one FIFO slot per delay class (its sum)
+            eng.begin_epoch(self.theta)
+            n_ws = len(ws)
+            k = -(-n_ws // cw)
+            for j in range(k):
+                c0, c1 = (j * n_ws) // k, ((j + 1) * n_ws) // k
+                eng.run_chunk(self.theta, self.pool, wt[off + c0:off + c1], c1 - c0, self.n,
+                              self.seed, self.dropout, self._slow_loss[:c1 - c0])
+            slot = self._slot()
+            eng.end_epoch(slot[:self.P])
+            self.stale_store[(d, t)] = slot
+            off += n_ws
+        ns = off
+        entries, counts = [], []
+        B, nf = self.buckets, len(fast)
+        for j in range(B):                       # fresh entries: one pass per non-empty bucket
+            b0, b1 = (j * nf) // B, ((j + 1) * nf) // B
+            if b1 == b0:
+                continue
+            eng.begin_epoch(self.theta)
+            for c0, c1 in self.chunks(b0, b1):
+                eng.run_chunk(self.theta, self.pool, wt[ns + c0:ns + c1], c1 - c0, self.n,
+                              self.seed, self.dropout, losses[c0:c1])
+            slot = self._slot()
+            eng.end_epoch(slot[:self.P])
+            entries.append(slot)
+            counts.append(b1 - b0)
+        popped = {}
+        for (i, src) in plan.stale:              # stale entries: one per (class, src) slot
+            key = (dclass(int(i)), int(src))
+            if key in popped:
+                counts[popped[key]] += 1
+            elif key in self.stale_store:
+                popped[key] = len(entries)
+                entries.append(self.stale_store.pop(key))
+                counts.append(1)
+        self.rank_worker_steps.append(len(fast) + len(own_workers))
+        if not entries:
+            raise IndexError("empty weight_ups (reference: IndexError in rule, main.py:25)")
+        if len(entries) > 64:
+            raise ValueError(f"robust rule over k = {len(entries)} entries (1 .. 64): fewer "
+                             "buckets or delay classes are needed")
+        kind, trim = self.robust
+        if self.keep_entries:
+            self.last_entries = ([e[:self.P].clone() for e in entries], list(counts))
+        self.step += 1
+        eng.robust_step(Robust(kind, trim, [e[:self.P] for e in entries], counts), self.theta,
+                        self.m, self.v, self.step, optim=self.optim, clip=self.clip)
+        self.free_slots.extend(entries)
+        self._log_norm()
+        self.trace.append(plan)
+        if sync_loss:
+            lv = losses.detach().cpu().numpy()
+            val = float(np.mean(lv.astype(np.float32))) if len(lv) else float("nan")
+            self.loss_log.append(val)
+            return val
+        self.loss_log.append((losses.detach().clone(), np.arange(len(fast))))
+        return None
+
     def _log_norm(self):
         """Keep this epoch's norm: a clone of the device scalar, read back only by grad_norms()."""
         if self.clip is not None:
@@ -734,7 +843,9 @@ class FLSimulation:
         spec = None if self.stale_weight is None else \
             [self.stale_weight[0]] + [float(x) for x in self.stale_weight[1:]]
         return {"stale_weight": spec, "stale_normalize": self.stale_normalize,
-                "delay_comp": self.delay_comp, "clip_grad_norm": self.clip_grad_norm}
+                "delay_comp": self.delay_comp, "clip_grad_norm": self.clip_grad_norm,
+                "robust_rule": None if self.robust is None else list(self.robust),
+                "buckets": self.buckets}
 
     def save_checkpoint(self, path):
         torch.save(self.checkpoint(), path)
@@ -763,7 +874,9 @@ class FLSimulation:
                      # ... and from before delay compensation: off
                      ("delay_comp", None),
                      # ... and from before gradient clipping: off
-                     ("clip_grad_norm", None)):
+                     ("clip_grad_norm", None),
+                     # ... and from before the robust rules: off, the default bucket count
+                     ("robust_rule", None), ("buckets", 8)):
             cfg.setdefault(k, v)
         delays = cfg["delays"].numpy().astype(np.int32)
         if fmt == "flsim-checkpoint-1":

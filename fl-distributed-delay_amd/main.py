@@ -10,6 +10,9 @@ entry by its age before the average (the alternative to --throttle).  --delay_co
 compensates a stale entry for the distance the model has moved since it was computed (DC-ASGD).
 --clip_grad_norm MAX_NORM clips the aggregated gradient's global 2-norm before the update
 (torch.nn.utils.clip_grad_norm_) and logs the norm as 'Grad Norm' per epoch.
+--robust_rule {none,median,trimmed_mean} with --trim N and --buckets B replaces the mean by the
+coordinate-wise median or trimmed mean over B bucket means of the fast workers and the popped
+delay-class entries (needs --semantics independent).
 The training loop (main.py:126-188) runs as flsim.sim.FLSimulation: host schedule,
 worker-batched HIP forward/backward, fused rule()+Adam; with
 `torchrun --nproc-per-node N` the computing workers are sharded over N GPUs with one RCCL
@@ -82,6 +85,15 @@ def parse(argv=None):
     p.add_argument('--clip_grad_norm', type=float, default=None, metavar='MAX_NORM',
                    help='clip the aggregated gradient to this global 2-norm before the update, '
                         'as torch.nn.utils.clip_grad_norm_ (default: off; inf only logs the norm)')
+    p.add_argument('--robust_rule', default='none', choices=['none', 'median', 'trimmed_mean'],
+                   help='aggregate with the coordinate-wise median or trimmed mean over bucket '
+                        'means instead of the mean (needs --semantics independent; default: none)')
+    p.add_argument('--trim', type=int, default=1, metavar='N',
+                   help='--robust_rule trimmed_mean: entries dropped at each end, 2N < the '
+                        "epoch's entry count (default 1)")
+    p.add_argument('--buckets', type=int, default=8, metavar='B',
+                   help="--robust_rule: contiguous buckets the epoch's fast workers are averaged "
+                        'in before the rule (default 8)')
     p.add_argument('--seed', type=int, default=0)
     p.add_argument('--semantics', default='reference', choices=['reference', 'torch1', 'independent'],
                    help='stale entry = S_{t-d} (torch>=2 aliasing), zeros (torch 1.x) or the slow '
@@ -111,6 +123,13 @@ def stale_spec(args):
     if args.stale_weight == 'hinge':
         return ('hinge', args.stale_a, args.stale_b)
     return (args.stale_weight, args.stale_a)
+
+
+def robust_spec(args):
+    """--robust_rule / --trim as FLSimulation's robust_rule spec."""
+    if args.robust_rule == 'none':
+        return None
+    return 'median' if args.robust_rule == 'median' else ('trimmed_mean', args.trim)
 
 
 def optim_kwargs(args):
@@ -155,6 +174,7 @@ def main(argv=None):
                        dampening=args.dampening, nesterov=args.nesterov,
                        stale_weight=stale_spec(args), stale_normalize=args.stale_normalize,
                        delay_comp=args.delay_comp, clip_grad_norm=args.clip_grad_norm,
+                       robust_rule=robust_spec(args), buckets=args.buckets,
                        **optim_kwargs(args))
     if buffers:
         sim.engine.load_buffers(buffers)

@@ -584,6 +584,54 @@ int flsim_probe_disable(void);
 int flsim_probe_kernel_count(void);
 const char* flsim_probe_kernel_name(int kid);
 
+/* ---------------------------------------------------------------------------------------------
+ * Robust rules: Agg(rule) (agents.py:43-45) takes any rule; these entry points run the
+ * coordinate-wise median and the trimmed mean (Yin et al. 2018) over bucket means of the workers
+ * (Karimireddy et al. 2022) fused with the update.  The text (flsim/robust.py, plain torch):
+ *
+ *   def _robust(cols, kind, trim):             # cols: [k, numel] fp32, already bucket means
+ *       k = cols.shape[0]
+ *       s = cols.sort(0).values                # ascending; -inf < finite < +inf < NaN
+ *       if kind == "median":
+ *           return s[(k - 1) // 2].clone()     # lower median
+ *       xs = s[trim:k - trim]                  # drop the `trim` lowest and the `trim` highest
+ *       acc = xs[0].clone()
+ *       for r in xs[1:]:                       # sequential fp32 adds, ascending order
+ *           acc += r
+ *       return acc / (k - 2 * trim)            # one IEEE fp32 division
+ *
+ * Per element e: x_j = entries[j][e] / (float)count[j] (one IEEE fp32 division: the mean of bucket
+ * j from its sum), g = _robust over the k values x_j, then the update of `optim` on g -- every kind
+ * of flsim_optim, the same arithmetic and the same correctly rounded sqrt as the entry points above.
+ * The result equals the text as a number: the same 32 bits wherever the text's value is neither
+ * zero nor NaN, a zero (of either sign) where it is a zero, a NaN where it is a NaN (torch's sort
+ * is stable, so the sign of a -0 / +0 tie follows the input order there; the sorting network
+ * orders -0 below +0).  The rule has no tensor structure, hence no tensor_sizes.
+ *   g_out (nullable, 16-byte aligned): g is also written there in the same pass.  optim == NULL
+ *     with g_out != NULL writes g only and touches none of p / m / v (clip must then be NULL).
+ *   clip != NULL: the launch stores g to clip->G and one fp64 sum of squares per block to
+ *     clip->partials (deterministic; at most flsim_clip_partials(P) of them); the finish and apply
+ *     launches of the clipped entry point above follow unchanged.
+ * Checked before any pointer, status 1: an unknown kind; k outside [1, FLSIM_MAX_ARRAYS]; trim < 0
+ * or 2 * trim >= k; trim != 0 with the median; a count < 1; what flsim_optim and flsim_clip are
+ * refused for above.  Then: a NULL or misaligned p (m, v where the kind owns them), a misaligned
+ * g_out or entry, P out of range, the clip buffers as above, and an entry overlapping p, m, v,
+ * g_out or clip->G.
+ * ------------------------------------------------------------------------------------------- */
+#define FLSIM_ROBUST_MEDIAN 0
+#define FLSIM_ROBUST_TRIMMED_MEAN 1
+typedef struct flsim_robust {
+    int32_t kind, trim, k;                      /* 1 <= k <= FLSIM_MAX_ARRAYS; trimmed mean: 2*trim < k */
+    const float* entries[FLSIM_MAX_ARRAYS];     /* bucket / class SUMS; NULL = an all-zero entry */
+    int32_t count[FLSIM_MAX_ARRAYS];            /* >= 1: entry value = entries[j][e] / count[j] */
+} flsim_robust;
+int flsim_robust_optim_step(const flsim_robust* r, const flsim_clip* clip, float* g_out,
+                            float* p, float* m, float* v, long P, long step,
+                            const flsim_optim* optim, flsim_stream_t stream);
+/* host (testing): g of the text above for host pointers, through the same sorting network and
+ * select / sum code the kernel runs; refuses what the entry point refuses about r */
+int flsim_robust_eval_host(const flsim_robust* r, long P, float* g_out);
+
 #ifdef __cplusplus
 }
 #endif
