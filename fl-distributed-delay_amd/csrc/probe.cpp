@@ -17,7 +17,8 @@ static const char* KNAME[K_COUNT] = {
     "vgg_conv4_wgrad", "vgg_conv5_wgrad", "vgg_conv6_wgrad", "vgg_conv7_wgrad", "vgg_conv8_wgrad",
     "vgg_linear1_wgrad", "vgg_linear1_dgrad", "vgg_linear2_wgrad", "vgg_linear2_dgrad",
     "aggregate_adam_seq", "slab_step", "slab_step_seq", "slab_sum",
-    "aggregate_gout", "clip_finish", "clip_apply", "robust_step"};
+    "aggregate_gout", "clip_finish", "clip_apply", "robust_step",
+    "krum_dist", "krum_finish", "krum_apply"};
 
 struct Probe {
     bool on = false;

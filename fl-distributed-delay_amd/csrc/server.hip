@@ -38,6 +38,7 @@
 
 #include "common.h"
 #include "flsim.h"
+#include "krum.h"
 #include "probe.h"
 #include "robust.h"
 #include "slabstep.h"
@@ -1854,6 +1855,353 @@ static void robust_eval_host(const flsim_robust* r, long P, float* g_out) {
     }
 }
 
+// ================================================================================================
+// Krum / Multi-Krum: all-pairs distances, score + selection, apply (include/flsim.h: flsim_krum;
+// csrc/krum.h: the geometry and the score / selection code shared with the host)
+// ================================================================================================
+struct KrumDistArgs {
+    const float* ent[RULE_MAX_ARR];     // bucket / class sums; nullptr = an all-zero entry
+    float cnt[RULE_MAX_ARR];            // x_j = ent[j][e] / cnt[j], as k_robust forms it
+    float rcnt[RULE_MAX_ARR];
+    double* partials;                   // [NPB * 16][grid]
+    long P;
+    int k;
+    int ntiles;
+};
+static_assert(sizeof(KrumDistArgs) <= 4096, "kernel argument block");
+
+template <int KPAD>
+struct KrumGeom {
+    static constexpr int NB = KPAD / 4, NPB = krum_npb(KPAD);
+    static constexpr int E = krum_tile_elems(KPAD), Q = E / 4;      // Q: float4 groups per row
+    // thread groups that split a tile's float4 groups; each holds one thread per 4 x 4 pair block
+    static constexpr int G = KPAD == 64 ? 3 : 256 / NPB;
+    static constexpr int NT = (G * NPB + 63) / 64 * 64;
+    static constexpr int LOADS = (KPAD * Q + NT - 1) / NT;
+    // row r of the tile starts at r * E + 4 * (r / 4) floats: the rows 4t of the 16 pair-block
+    // columns then start in 16 different 16-byte slots of the 256-byte bank row, so the
+    // ds_read_b128 of lanes that differ in their block column is conflict-free
+    static constexpr int LDS_FLOATS = KPAD * E + KPAD;
+    __host__ __device__ static constexpr int row(int r) { return r * E + 4 * (r >> 2); }
+};
+
+// One block stages a tile (E elements of all KPAD rows, the bucket means x = ent / cnt) in LDS:
+// coalesced 16-byte non-temporal loads (scalar loads for an entry that is not 16-byte aligned and
+// at the end of the array), one 16-byte LDS store each; the elements past P and the rows past k
+// are zero, which adds nothing to any sum.  (Issuing the next tile's loads before the current
+// tile is computed was measured and is slower at every k: profiles/krum/README.md.)  Thread (grp, pb) owns the 4 x 4 pairs of block pb and
+// walks the float4 groups grp, grp + G, ...: eight 16-byte LDS reads give four elements of its
+// eight rows, and every pair takes one fp64 subtract and one fp64 fma per element.  A block
+// grid-strides over the tiles; at the end the groups are added by a fixed halving tree through
+// LDS, and group 0 writes the block's NPB * 16 sums.
+template <int KPAD>
+__global__ void __launch_bounds__(KrumGeom<KPAD>::NT) k_krum_dist(KrumDistArgs A) {
+    using Gm = KrumGeom<KPAD>;
+    constexpr int E = Gm::E, Q = Gm::Q, G = Gm::G, NPB = Gm::NPB, NT = Gm::NT;
+    __shared__ __attribute__((aligned(16))) float tile[Gm::LDS_FLOATS];
+    // (a step of the tree has at most G / 2 writing groups)
+    static_assert(sizeof(double) * 16 * (G / 2) * NPB <= sizeof(float) * Gm::LDS_FLOATS,
+                  "the group tree's scratch fits the tile");
+    const int t = threadIdx.x;
+    const int grp = t / NPB, pb = t - grp * NPB;
+    const bool worker = grp < G;
+    int ti = 0, tj = pb;
+    while (tj >= Gm::NB - ti) {
+        tj -= Gm::NB - ti;
+        ++ti;
+    }
+    tj += ti;
+    for (int idx = A.k * Q + t; idx < KPAD * Q; idx += NT) {       // the rows past k: zero, once
+        const int j = idx / Q, q = idx - j * Q;
+        *reinterpret_cast<f32x4*>(&tile[Gm::row(j) + 4 * q]) = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    double acc[4][4];
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int b = 0; b < 4; ++b) acc[a][b] = 0.0;
+    for (int tl = blockIdx.x; tl < A.ntiles; tl += gridDim.x) {
+        const long e0 = (long)tl * E;
+        __syncthreads();                    // the previous tile has been read by every thread
+        f32x4 x[Gm::LOADS];
+#pragma unroll
+        for (int u = 0; u < Gm::LOADS; ++u) {
+            const int idx = u * NT + t;
+            x[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+            if (idx < A.k * Q) {
+                const int j = idx / Q, q = idx - j * Q;
+                const float* src = A.ent[j];
+                const long e = e0 + 4 * q;
+                if (src) {
+                    if ((((uintptr_t)src & 15) == 0) && e + 4 <= A.P) {
+                        x[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(src + e));
+                    } else {
+#pragma unroll
+                        for (int c = 0; c < 4; ++c)
+                            if (e + c < A.P) x[u][c] = __builtin_nontemporal_load(src + e + c);
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < Gm::LOADS; ++u) {
+            const int idx = u * NT + t;
+            if (idx < A.k * Q) {
+                const int j = idx / Q, q = idx - j * Q;
+                const float c = A.cnt[j], rc = A.rcnt[j];
+                f32x4 y;
+#pragma unroll
+                for (int w = 0; w < 4; ++w) y[w] = div_const(x[u][w], c, rc);
+                *reinterpret_cast<f32x4*>(&tile[Gm::row(j) + 4 * q]) = y;
+            }
+        }
+        __syncthreads();
+        if (worker) {
+            for (int q = grp; q < Q; q += G) {
+                f32x4 xi[4], xj[4];
+#pragma unroll
+                for (int a = 0; a < 4; ++a) {
+                    xi[a] = *reinterpret_cast<const f32x4*>(&tile[Gm::row(4 * ti + a) + 4 * q]);
+                    xj[a] = *reinterpret_cast<const f32x4*>(&tile[Gm::row(4 * tj + a) + 4 * q]);
+                }
+#pragma unroll
+                for (int w = 0; w < 4; ++w) {
+                    double di[4], dj[4];
+#pragma unroll
+                    for (int a = 0; a < 4; ++a) {
+                        di[a] = (double)xi[a][w];
+                        dj[a] = (double)xj[a][w];
+                    }
+#pragma unroll
+                    for (int a = 0; a < 4; ++a)
+#pragma unroll
+                        for (int b = 0; b < 4; ++b) {
+                            const double d = di[a] - dj[b];
+                            acc[a][b] = __builtin_fma(d, d, acc[a][b]);
+                        }
+                }
+            }
+        }
+    }
+    // the groups, by a halving tree in a fixed order: group g + s is added into group g
+    double* red = reinterpret_cast<double*>(tile);
+    int top = 1;
+    while (top < G) top <<= 1;
+    for (int s = top >> 1; s > 0; s >>= 1) {
+        __syncthreads();
+        if (worker && grp >= s && grp < 2 * s) {
+            double* dst = red + ((grp - s) * NPB + pb) * 16;
+#pragma unroll
+            for (int a = 0; a < 4; ++a)
+#pragma unroll
+                for (int b = 0; b < 4; ++b) dst[a * 4 + b] = acc[a][b];
+        }
+        __syncthreads();
+        if (worker && grp < s && grp + s < G) {
+            const double* src = red + (grp * NPB + pb) * 16;
+#pragma unroll
+            for (int a = 0; a < 4; ++a)
+#pragma unroll
+                for (int b = 0; b < 4; ++b) acc[a][b] += src[a * 4 + b];
+        }
+    }
+    // slot-major, partials[slot][block]: the finish launch reads a pair's sums as one run
+    if (grp == 0) {
+        double* dst = A.partials + (long)pb * 16 * gridDim.x + blockIdx.x;
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+            for (int b = 0; b < 4; ++b) dst[(long)(a * 4 + b) * gridDim.x] = acc[a][b];
+    }
+}
+
+// One block of KRUM_FIN_THREADS = 16 waves.  Pair (i, j), i < j, belongs to one wave: lane l adds
+// the partials of the blocks l, l + 64, ... in index order (coalesced: the partials are slot-major)
+// and a butterfly adds the 64 lanes, as k_clip_finish and block_sum_f64 do -- a fixed order for a
+// given (P, k).  A wave takes four pairs at a time and issues all their loads before any add.  A NaN
+// sum becomes +inf, the value is mirrored, the diagonal is zero.  Then csrc/krum.h's score /
+// selection code on the matrix in LDS.
+constexpr int KRUM_FIN_THREADS = 1024;
+
+__global__ void __launch_bounds__(KRUM_FIN_THREADS)
+k_krum_finish(const double* partials, int nblocks, int nb, int k, int f, int m, double* dist,
+              double* score, int32_t* sel) {
+    __shared__ double sd[RULE_MAX_ARR * RULE_MAX_ARR];
+    __shared__ double ss[RULE_MAX_ARR];
+    __shared__ int32_t sr[RULE_MAX_ARR];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    constexpr int WAVES = KRUM_FIN_THREADS / 64;
+    // every load of a pair is issued before the first add (the grid's cap bounds them: 12 a lane)
+    constexpr int NLD = 12;
+    static_assert(krum_max_blocks(4) <= 64 * NLD && krum_max_blocks(64) <= 64 * NLD, "NLD");
+    auto lane_sum = [&](int idx) -> double {
+        const int i = idx / k, j = idx - i * k;
+        double a = 0.0;
+        if (idx < k * k && i < j) {
+            const double* src = partials + (long)krum_slot(i, j, nb) * nblocks;
+            double x[NLD];
+#pragma unroll
+            for (int u = 0; u < NLD; ++u) x[u] = lane + 64 * u < nblocks ? src[lane + 64 * u] : 0.0;
+#pragma unroll
+            for (int u = 0; u < NLD; ++u) a = lane + 64 * u < nblocks ? a + x[u] : a;
+        }
+        return a;
+    };
+    auto store = [&](int idx, double a) {
+        const int i = idx / k, j = idx - i * k;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
+        if (lane == 0 && idx < k * k && i <= j) {
+            a = a != a ? (double)__builtin_inff() : a;
+            sd[i * k + j] = a;                  // (the diagonal: no partial was added, 0)
+            sd[j * k + i] = a;
+        }
+    };
+    for (int base = wave; base < k * k; base += 4 * WAVES) {
+        double a[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) a[u] = lane_sum(base + u * WAVES);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) store(base + u * WAVES, a[u]);
+    }
+    __syncthreads();
+    for (int idx = threadIdx.x; idx < k * k; idx += KRUM_FIN_THREADS) dist[idx] = sd[idx];
+    krum_score_select(sd, ss, sr, sel, k, f, m, (int)threadIdx.x, KRUM_FIN_THREADS,
+                      [] { __syncthreads(); });
+    if ((int)threadIdx.x < k) score[threadIdx.x] = ss[threadIdx.x];
+}
+
+struct KrumApplyArgs {
+    const float* ent[RULE_MAX_ARR];
+    float cnt[RULE_MAX_ARR];
+    float rcnt[RULE_MAX_ARR];
+    const int32_t* sel;                 // [m] the selection k_krum_finish wrote (device memory)
+    float* g_out;                       // nullable: g is also written here
+    float* G;                           // OK_GOUT, nullable: the clipped step's G
+    double* partials;                   // OK_GOUT, nullable: block b's sum of g * g (fp64)
+    float* p;
+    float* m;
+    float* v;
+    long P;
+    int nsel;
+    float fm;                           // (float)m: the divisor of the selected entries' sum
+    AdamConst ac;
+    OptConst oc;
+};
+static_assert(sizeof(KrumApplyArgs) <= 4096, "kernel argument block");
+
+// One thread owns one element, as k_robust.  The selection is read from device memory; it is
+// launch-uniform (readfirstlane: the entry pointer, its count and the reciprocal come from the
+// kernel arguments by scalar loads).  Only the m selected entries are loaded, eight loads in flight;
+// g = (x_sel0 + x_sel1 + ...) / (float)m: the divisions, sequential fp32 adds in index order and
+// one IEEE division, as the text.  Then the update of kind OK, or OK_GOUT as k_robust.
+template <int OK>
+__global__ void __launch_bounds__(256) k_krum_apply(KrumApplyArgs A) {
+    constexpr bool HAS_M = opt_n_state(OK) >= 1, HAS_V = opt_n_state(OK) == 2;
+    const long e = (long)blockIdx.x * 256 + threadIdx.x;
+    const bool live = e < A.P;
+    if constexpr (OK != OK_GOUT) {
+        if (!live) return;
+    }
+    float p = 0.f, m = 0.f, v = 0.f;
+    if constexpr (OK != OK_GOUT) p = __builtin_nontemporal_load(A.p + e);
+    if constexpr (HAS_M) m = __builtin_nontemporal_load(A.m + e);
+    if constexpr (HAS_V) v = __builtin_nontemporal_load(A.v + e);
+    float acc = 0.f;
+    for (int t0 = 0; t0 < A.nsel; t0 += 8) {
+        float x[8], c[8], rc[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            x[u] = 0.f;
+            c[u] = 1.f;
+            rc[u] = 1.f;
+            if (t0 + u < A.nsel) {
+                const int j = __builtin_amdgcn_readfirstlane(A.sel[t0 + u]) & (RULE_MAX_ARR - 1);
+                const float* src = A.ent[j];
+                c[u] = A.cnt[j];
+                rc[u] = A.rcnt[j];
+                if (src && live) x[u] = __builtin_nontemporal_load(src + e);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            if (t0 + u < A.nsel) {
+                const float y = div_const(x[u], c[u], rc[u]);
+                acc = (t0 + u == 0) ? y : acc + y;
+            }
+        }
+    }
+    const float g = __fdiv_rn(acc, A.fm);
+    if constexpr (OK == OK_GOUT) {
+        if (live) {
+            if (A.g_out) __builtin_nontemporal_store(g, A.g_out + e);
+            if (A.G) __builtin_nontemporal_store(g, A.G + e);
+        }
+        if (A.partials) {
+            __shared__ double red[4];
+            const double s = block_sum_f64(live ? (double)g * (double)g : 0.0, red);
+            if (threadIdx.x == 0) A.partials[blockIdx.x] = s;
+        }
+    } else {
+        if (A.g_out) __builtin_nontemporal_store(g, A.g_out + e);
+        opt_update<OK>(A.ac, A.oc, g, p, m, v);
+        __builtin_nontemporal_store(p, A.p + e);
+        if constexpr (HAS_M) __builtin_nontemporal_store(m, A.m + e);
+        if constexpr (HAS_V) __builtin_nontemporal_store(v, A.v + e);
+    }
+}
+
+template <int KPAD>
+static void launch_krum_dist(dim3 grid, hipStream_t stream, const ProbeSlot& ps,
+                             const KrumDistArgs& A) {
+    hipExtLaunchKernelGGL((k_krum_dist<KPAD>), grid, dim3(KrumGeom<KPAD>::NT), 0, stream, ps.start,
+                          ps.stop, 0, A);
+}
+
+static void launch_krum_apply(int ok, dim3 grid, hipStream_t stream, const ProbeSlot& ps,
+                              const KrumApplyArgs& A) {
+#define FLSIM_KRUM_CASE(K)                                                                     \
+    case K:                                                                                    \
+        hipExtLaunchKernelGGL((k_krum_apply<K>), grid, dim3(256), 0, stream, ps.start, ps.stop, \
+                              0, A);                                                           \
+        break;
+    switch (ok) {
+        FLSIM_KRUM_CASE(OK_ADAM)
+        FLSIM_KRUM_CASE(OK_ADAMD)
+        FLSIM_KRUM_CASE(OK_SGDM)
+        FLSIM_KRUM_CASE(OK_GOUT)
+        FLSIM_KRUM_CASE(OK_ADAGRAD)
+        FLSIM_KRUM_CASE(OK_YOGI)
+        default:
+            hipExtLaunchKernelGGL((k_krum_apply<OK_SGD>), grid, dim3(256), 0, stream, ps.start,
+                                  ps.stop, 0, A);
+            break;
+    }
+#undef FLSIM_KRUM_CASE
+}
+
+// flsim_krum's hyper-parameters; before any pointer check, like check_optim
+static int check_krum(const flsim_krum* r) {
+    FLSIM_REQUIRE(r, "null Krum rule");
+    FLSIM_REQUIRE(r->k >= 3 && r->k <= RULE_MAX_ARR, "Krum over k = %d entries (3 .. %d)", r->k,
+                  RULE_MAX_ARR);
+    FLSIM_REQUIRE(r->f >= 0 && r->f <= RULE_MAX_ARR && r->k >= 2 * r->f + 3,
+                  "Invalid f = %d for k = %d entries: f >= 0 and k >= 2 * f + 3", r->f, r->k);
+    FLSIM_REQUIRE(r->m >= 1 && r->m <= r->k - r->f,
+                  "Invalid m = %d for k = %d entries and f = %d: 1 <= m <= k - f", r->m, r->k,
+                  r->f);
+    for (int j = 0; j < r->k; ++j)
+        FLSIM_REQUIRE(r->count[j] >= 1, "Invalid count %d of entry %d: it must be >= 1",
+                      r->count[j], j);
+    return 0;
+}
+
+// [a, a + na) and [b, b + nb) bytes share a byte
+static bool overlaps_bytes(const void* a, long na, const void* b, long nb) {
+    return a && b && (uintptr_t)a < (uintptr_t)b + (uintptr_t)nb &&
+           (uintptr_t)b < (uintptr_t)a + (uintptr_t)na;
+}
+
 }  // namespace flsim
 
 using namespace flsim;
@@ -2365,6 +2713,196 @@ int flsim_robust_eval_host(const flsim_robust* r, long P, float* g_out) {
         case 16: robust_eval_host<16>(r, P, g_out); break;
         case 32: robust_eval_host<32>(r, P, g_out); break;
         default: robust_eval_host<64>(r, P, g_out); break;
+    }
+    return 0;
+}
+
+// ---- Krum / Multi-Krum over bucket means + the update (include/flsim.h) --------------------------
+long flsim_krum_partials(long P, int k) {
+    if (k < 1 || k > RULE_MAX_ARR || P < 1 || P >= (1L << 31)) return 0;
+    const int kpad = krum_kpad(k);
+    return krum_blocks(P, kpad) * krum_npb(kpad) * 16;
+}
+
+long flsim_krum_tile_elems(int k) {
+    if (k < 1 || k > RULE_MAX_ARR) return 0;
+    return krum_tile_elems(krum_kpad(k));
+}
+
+// Three launches: k_krum_dist -> s->partials; k_krum_finish -> s->dist, s->score, s->sel;
+// k_krum_apply in the optimizer's kind (optim == NULL: OK_GOUT writing g_out alone; clip: OK_GOUT
+// writing clip->G and the per-block partials, then k_clip_finish and k_clip_apply).
+int flsim_krum_optim_step(const flsim_krum* r, const flsim_krum_scratch* s, const flsim_clip* clip,
+                          float* g_out, float* p, float* m, float* v, long P, long step,
+                          const flsim_optim* optim, hipStream_t stream) {
+    RC(check_krum(r));
+    if (optim) RC(check_optim(optim));
+    RC(check_clip(clip));
+    FLSIM_REQUIRE(optim || (g_out && !clip), "null optimizer (only a step that writes g_out alone, "
+                  "unclipped, takes none)");
+    OptLaunch ol{};
+    ol.ok = OK_GOUT;
+    int nstate = 0;
+    if (optim) {
+        nstate = optim_n_state(optim);
+        RC(make_opt_launch(optim, 1.0, step, &ol));
+        FLSIM_REQUIRE(p && (m || nstate < 1) && (v || nstate < 2), "null pointer");
+    } else {
+        p = nullptr;
+    }
+    if (nstate < 2) v = nullptr;
+    if (nstate < 1) m = nullptr;
+    FLSIM_REQUIRE(P > 0 && P < (1L << 31), "P = %ld out of range", P);
+    FLSIM_REQUIRE((((uintptr_t)p | (uintptr_t)m | (uintptr_t)v | (uintptr_t)g_out) & 15) == 0,
+                  "p/m/v/g_out must be 16-byte aligned");
+    const float* const outs[] = {p, m, v, g_out};
+    for (int a = 0; a < 4; ++a)
+        for (int b = a + 1; b < 4; ++b)
+            FLSIM_REQUIRE(!overlaps(outs[a], outs[b], P), "p/m/v/g_out overlap each other");
+    FLSIM_REQUIRE(s && s->partials && s->dist && s->score && s->sel, "null Krum scratch");
+    FLSIM_REQUIRE((((uintptr_t)s->partials | (uintptr_t)s->dist | (uintptr_t)s->score |
+                    (uintptr_t)s->sel) & 15) == 0, "Krum scratch must be 16-byte aligned");
+    const int kpad = krum_kpad(r->k);
+    const long nblocks = krum_blocks(P, kpad);
+    const long n_dist = nblocks * krum_npb(kpad) * 16;
+    FLSIM_REQUIRE(s->n_partials >= n_dist, "Krum n_partials = %ld, this step writes %ld",
+                  s->n_partials, n_dist);
+    const void* const sb[] = {s->partials, s->dist, s->score, s->sel};
+    const long sn[] = {8 * n_dist, 8L * r->k * r->k, 8L * r->k, 4L * r->m};
+    for (int a = 0; a < 4; ++a) {
+        for (int b = a + 1; b < 4; ++b)
+            FLSIM_REQUIRE(!overlaps_bytes(sb[a], sn[a], sb[b], sn[b]),
+                          "Krum scratch buffers overlap each other");
+        for (const float* o : outs)
+            FLSIM_REQUIRE(!overlaps_bytes(sb[a], sn[a], o, 4 * P),
+                          "Krum scratch overlaps p/m/v/g_out");
+        FLSIM_REQUIRE(!clip || !overlaps_bytes(sb[a], sn[a], clip->G, 4 * P),
+                      "Krum scratch overlaps clip G");
+    }
+    long n_part = 0;
+    if (clip) {
+        FLSIM_REQUIRE(clip->G && clip->partials && clip->out, "null clip buffer");
+        FLSIM_REQUIRE((((uintptr_t)clip->G | (uintptr_t)clip->partials | (uintptr_t)clip->out) &
+                       15) == 0, "clip G/partials/out must be 16-byte aligned");
+        for (const float* o : outs)
+            FLSIM_REQUIRE(!overlaps(clip->G, o, P), "clip G overlaps p/m/v/g_out");
+    }
+    KrumDistArgs D{};
+    KrumApplyArgs A{};
+    int distinct = 0;
+    for (int j = 0; j < r->k; ++j) {
+        const float* e = r->entries[j];
+        FLSIM_REQUIRE(((uintptr_t)e & 3) == 0, "entry %d must be 4-byte aligned", j);
+        for (const float* o : outs)
+            FLSIM_REQUIRE(!overlaps(e, o, P), "entry %d overlaps p/m/v/g_out", j);
+        FLSIM_REQUIRE(!clip || !overlaps(e, clip->G, P), "entry %d overlaps clip G", j);
+        for (int a = 0; a < 4; ++a)
+            FLSIM_REQUIRE(!overlaps_bytes(e, 4 * P, sb[a], sn[a]),
+                          "entry %d overlaps the Krum scratch", j);
+        volatile float one = 1.f, c = (float)r->count[j];    // RN(1 / count) in fp32
+        D.ent[j] = A.ent[j] = e;
+        D.cnt[j] = A.cnt[j] = c;
+        D.rcnt[j] = A.rcnt[j] = one / c;
+        bool seen = e == nullptr;
+        for (int q = 0; q < j && !seen; ++q) seen = r->entries[q] == e;
+        distinct += !seen;
+    }
+    const long nblk = (P + 255) / 256;
+    if (clip) {
+        n_part = nblk;
+        FLSIM_REQUIRE(clip->n_partials >= n_part, "clip n_partials = %ld, this step writes %ld",
+                      clip->n_partials, n_part);
+    }
+    D.partials = s->partials;
+    D.P = P;
+    D.k = r->k;
+    D.ntiles = (int)krum_tiles(P, kpad);
+    {
+        const ProbeSlot ps = probe_begin();
+        const dim3 grid((unsigned)nblocks);
+        switch (kpad) {
+            case 4: launch_krum_dist<4>(grid, stream, ps, D); break;
+            case 8: launch_krum_dist<8>(grid, stream, ps, D); break;
+            case 16: launch_krum_dist<16>(grid, stream, ps, D); break;
+            case 32: launch_krum_dist<32>(grid, stream, ps, D); break;
+            default: launch_krum_dist<64>(grid, stream, ps, D); break;
+        }
+        FLSIM_LAUNCH_CHECK();
+        // algorithmic HBM bytes: each distinct entry read once
+        if (probe_end(ps, K_KRUM_DIST, 4.0 * (double)P * distinct)) return 2;
+    }
+    {
+        const ProbeSlot ps = probe_begin();
+        hipExtLaunchKernelGGL(k_krum_finish, dim3(1), dim3(KRUM_FIN_THREADS), 0, stream, ps.start,
+                              ps.stop, 0, (const double*)s->partials, (int)nblocks, kpad / 4,
+                              (int)r->k, (int)r->f, (int)r->m, s->dist, s->score, s->sel);
+        FLSIM_LAUNCH_CHECK();
+        if (probe_end(ps, K_KRUM_FIN, 8.0 * (double)nblocks * (r->k * (r->k - 1) / 2) +
+                                          8.0 * r->k * (r->k + 1) + 4.0 * r->m))
+            return 2;
+    }
+    A.sel = s->sel;
+    A.g_out = g_out;
+    A.G = clip ? clip->G : nullptr;
+    A.partials = clip ? clip->partials : nullptr;
+    A.p = p;
+    A.m = m;
+    A.v = v;
+    A.P = P;
+    A.nsel = r->m;
+    A.fm = (float)r->m;
+    A.ac = ol.ac;
+    A.oc = ol.oc;
+    const int ok_launch = clip ? (int)OK_GOUT : ol.ok;
+    // algorithmic HBM bytes: the m selected entries read; g_out / G written; p and the kind's
+    // state arrays read + written (not by a launch that only writes g)
+    const int nst_launch = ok_launch == OK_GOUT ? 0 : nstate;
+    const double bytes = 4.0 * (double)P * (r->m + (g_out ? 1 : 0) + (clip ? 1 : 0) +
+                                            (ok_launch == OK_GOUT ? 0 : 2 + 2 * nst_launch));
+    const ProbeSlot ps = probe_begin();
+    launch_krum_apply(ok_launch, dim3((unsigned)nblk), stream, ps, A);
+    FLSIM_LAUNCH_CHECK();
+    if (probe_end(ps, K_KRUM_APPLY, bytes)) return 2;
+    if (!clip) return 0;
+    return clip_finish_apply(clip, n_part, ol, p, m, v, P, stream);
+}
+
+// host (testing): the text for host pointers.  The bucket means by one fp32 division each, every
+// distance as the fp64 sum of the squared fp64 differences in element order (a pair is computed
+// once and mirrored), NaN -> +inf, then csrc/krum.h's score / selection code and g as the text
+// forms it.
+int flsim_krum_eval_host(const flsim_krum* r, long P, double* dist, double* score, int32_t* sel,
+                         float* g_out) {
+    RC(check_krum(r));
+    FLSIM_REQUIRE(dist && score && sel, "null pointer");
+    FLSIM_REQUIRE(P > 0, "P = %ld out of range", P);
+    const int k = r->k;
+    auto mean = [&](int j, long e) -> float {
+        volatile float x = r->entries[j] ? r->entries[j][e] : 0.f;
+        volatile float c = (float)r->count[j];
+        return x / c;
+    };
+    for (int i = 0; i < k; ++i) {
+        dist[(long)i * k + i] = 0.0;
+        for (int j = i + 1; j < k; ++j) {
+            double a = 0.0;
+            for (long e = 0; e < P; ++e) {
+                const double d = (double)mean(i, e) - (double)mean(j, e);
+                a = __builtin_fma(d, d, a);
+            }
+            a = a != a ? (double)__builtin_inff() : a;
+            dist[(long)i * k + j] = a;
+            dist[(long)j * k + i] = a;
+        }
+    }
+    int32_t rank[RULE_MAX_ARR];
+    krum_score_select(dist, score, rank, sel, k, (int)r->f, (int)r->m, 0, 1, [] {});
+    if (!g_out) return 0;
+    for (long e = 0; e < P; ++e) {
+        volatile float acc = mean(sel[0], e);
+        for (int t = 1; t < r->m; ++t) acc = acc + mean(sel[t], e);
+        volatile float fm = (float)r->m;
+        g_out[e] = acc / fm;
     }
     return 0;
 }

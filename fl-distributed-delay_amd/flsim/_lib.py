@@ -51,6 +51,8 @@ EXPORTS = [
     "flsim_cascade_eval_host_c",
     "flsim_clip_partials", "flsim_aggregate_optim_clip_push", "flsim_cascade_eval_host_clip",
     "flsim_robust_optim_step", "flsim_robust_eval_host",
+    "flsim_krum_partials", "flsim_krum_tile_elems", "flsim_krum_optim_step",
+    "flsim_krum_eval_host",
 ]
 COMM_ID_BYTES = 128      # FLSIM_COMM_ID_BYTES
 
@@ -97,6 +99,18 @@ class FlsimRobust(ctypes.Structure):
     """flsim_robust (include/flsim.h): a robust rule over k bucket / class sums and their counts."""
     _fields_ = [("kind", ctypes.c_int32), ("trim", ctypes.c_int32), ("k", ctypes.c_int32),
                 ("entries", ctypes.c_void_p * MAX_ARRAYS), ("count", ctypes.c_int32 * MAX_ARRAYS)]
+
+
+class FlsimKrum(ctypes.Structure):
+    """flsim_krum (include/flsim.h): Krum / Multi-Krum over k bucket / class sums and counts."""
+    _fields_ = [("f", ctypes.c_int32), ("m", ctypes.c_int32), ("k", ctypes.c_int32),
+                ("entries", ctypes.c_void_p * MAX_ARRAYS), ("count", ctypes.c_int32 * MAX_ARRAYS)]
+
+
+class FlsimKrumScratch(ctypes.Structure):
+    """flsim_krum_scratch (include/flsim.h): the caller's scratch and outputs of a Krum step."""
+    _fields_ = [("partials", ctypes.c_void_p), ("n_partials", ctypes.c_long),
+                ("dist", ctypes.c_void_p), ("score", ctypes.c_void_p), ("sel", ctypes.c_void_p)]
 
 
 # FLSIM_OPT_ADAM / _ADAMW / _SGD / _ADAGRAD / _YOGI
@@ -225,6 +239,13 @@ def lib():
     L.flsim_robust_optim_step.argtypes = [vp, vp, vp, vp, vp, vp, ctypes.c_long, ctypes.c_long, vp,
                                           vp]
     L.flsim_robust_eval_host.argtypes = [vp, ctypes.c_long, vp]
+    L.flsim_krum_partials.restype = ctypes.c_long
+    L.flsim_krum_partials.argtypes = [ctypes.c_long, ctypes.c_int]
+    L.flsim_krum_tile_elems.restype = ctypes.c_long
+    L.flsim_krum_tile_elems.argtypes = [ctypes.c_int]
+    L.flsim_krum_optim_step.argtypes = [vp, vp, vp, vp, vp, vp, vp, ctypes.c_long, ctypes.c_long,
+                                        vp, vp]
+    L.flsim_krum_eval_host.argtypes = [vp, ctypes.c_long, vp, vp, vp, vp]
     L.flsim_cascade_program.argtypes = [ctypes.c_int, vp, vp, ctypes.c_int, vp, ctypes.c_int, vp]
     L.flsim_cascade_eval_host.argtypes = [vp, vp, vp, vp, ctypes.c_int, vp, ctypes.c_long, vp]
     L.flsim_probe_enable.argtypes = [ctypes.c_int]

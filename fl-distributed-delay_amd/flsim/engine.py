@@ -20,7 +20,8 @@ import torch
 
 import math
 
-from ._lib import (MAX_ARRAYS, OPT_KINDS, ROBUST_KINDS, FlsimClip, FlsimOptim, FlsimRobust,
+from ._lib import (MAX_ARRAYS, OPT_KINDS, ROBUST_KINDS, FlsimClip, FlsimKrum, FlsimKrumScratch,
+                   FlsimOptim, FlsimRobust,
                    FlsimRule, FlsimRuleComp, FlsimRuleWeights, WorkerRec, check, lib, ptr,
                    stream_ptr)
 
@@ -463,6 +464,13 @@ class NetEngine:
         rule `optim`) over this network's P parameters; clip (a Clip) and g_out as robust_step."""
         robust_step(robust, theta, m, v, step, self.P, lr, betas, eps, optim=optim, clip=clip,
                     g_out=g_out)
+
+    def krum_step(self, krum, theta, m, v, step, lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
+                  optim=None, clip=None, g_out=None):
+        """Krum / Multi-Krum (a Krum over bucket sums) + Adam (or the update rule `optim`) over
+        this network's P parameters; clip (a Clip) and g_out as krum_step."""
+        krum_step(krum, theta, m, v, step, self.P, lr, betas, eps, optim=optim, clip=clip,
+                  g_out=g_out)
 
 
 class PN1Engine(NetEngine):
@@ -928,6 +936,82 @@ def robust_step(robust, theta, m, v, step, P=None, lr=1e-3, betas=(0.9, 0.999), 
     check(lib().flsim_robust_optim_step(
         ctypes.byref(r), c, ptr(g_out), ptr(theta), ptr(m), ptr(v), int(P), int(step), o,
         stream_ptr()))
+
+
+class Krum:
+    """Krum / Multi-Krum over bucket / class sums (flsim_krum, include/flsim.h): of the k =
+    len(entries) values entries[j] / counts[j], the mean of the m whose summed squared distance
+    to their k - f - 2 nearest neighbours is lowest (m = 1: Krum).  entries, counts as for Robust.
+    The object owns its scratch per (device, P, k), allocated at the first step; after a step
+    dist ([k, k] fp64), score ([k] fp64) and sel ([m] int32, ascending) are device tensors, read
+    with no synchronisation beyond the stream's order; the next step overwrites them.
+    flsim/robust.py is the rule's text."""
+    _scratch = {}       # (device, P, k) -> buffers, shared by the objects of a run
+
+    def __init__(self, f, m, entries, counts):
+        entries, counts = list(entries), [int(c) for c in counts]
+        if len(entries) != len(counts):
+            raise ValueError(f"{len(counts)} counts for {len(entries)} entries")
+        if len(entries) > MAX_ARRAYS:
+            raise ValueError(f"Krum over k = {len(entries)} entries (3 .. {MAX_ARRAYS})")
+        self.f, self.m = int(f), int(m)
+        self.entries, self.counts = entries, counts     # (the rule keeps the tensors alive)
+        self.dist = self.score = self.sel = None
+
+    @property
+    def k(self):
+        return len(self.entries)
+
+    def c_struct(self):
+        r = FlsimKrum()
+        r.f, r.m, r.k = self.f, self.m, len(self.entries)
+        for j, (e, c) in enumerate(zip(self.entries, self.counts)):
+            r.entries[j] = e.data_ptr() if e is not None else None
+            r.count[j] = c if -2 ** 31 <= c < 2 ** 31 else 0
+        return r
+
+    def c_scratch(self, device, P):
+        """flsim_krum_scratch over this device's scratch for a step over P elements."""
+        k = len(self.entries)
+        key = (str(device), int(P), k)
+        if key not in Krum._scratch:
+            n = max(int(lib().flsim_krum_partials(int(P), k)), 2)
+            Krum._scratch[key] = (torch.empty(n, dtype=torch.float64, device=device),
+                                  torch.empty(k * k + 2, dtype=torch.float64, device=device),
+                                  torch.empty(k + 2, dtype=torch.float64, device=device),
+                                  torch.empty(MAX_ARRAYS, dtype=torch.int32, device=device))
+        partials, dist, score, sel = Krum._scratch[key]
+        s = FlsimKrumScratch()
+        s.partials = partials.data_ptr()
+        s.n_partials = int(partials.numel())
+        s.dist = dist.data_ptr()
+        s.score = score.data_ptr()
+        s.sel = sel.data_ptr()
+        self.partials = partials
+        self.dist = dist[:k * k].view(k, k)
+        self.score = score[:k]
+        self.sel = sel[:max(min(self.m, MAX_ARRAYS), 0)]
+        return s
+
+
+def krum_step(krum, theta, m, v, step, P=None, lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
+              optim=None, clip=None, g_out=None):
+    """Krum / Multi-Krum + Adam(lr, betas, eps), or the update rule `optim`, in three launches
+    (flsim_krum_optim_step); m / v, clip, g_out and optim=False as robust_step."""
+    if optim is False:
+        o = None
+    else:
+        o = ctypes.byref((as_optim(optim) if optim is not None else
+                          Optim(lr=lr, betas=tuple(betas), eps=eps)).c_struct())
+    if P is None:
+        P = int((theta if theta is not None else g_out).numel())
+    r = krum.c_struct()
+    dev = next((t.device for t in (theta, g_out, *krum.entries) if t is not None), None)
+    s = krum.c_scratch(dev, int(P))
+    c = ctypes.byref(clip.c_struct(dev, int(P))) if clip is not None else None
+    check(lib().flsim_krum_optim_step(
+        ctypes.byref(r), ctypes.byref(s), c, ptr(g_out), ptr(theta), ptr(m), ptr(v), int(P),
+        int(step), o, stream_ptr()))
 
 
 def worker_table(recs, device):

@@ -44,7 +44,7 @@ import torch
 from .data import DevicePool, make_test_pool
 from .engine import (PN1_SIZES, Clip, Optim, ProgramStager, Rule, engine_class, optim_defaults,
                      padded, split_views, staleness_weight)
-from .robust import parse_rule
+from .robust import KRUM_KINDS, check_krum, parse_rule
 from .schedule import Schedule, reference_delays
 
 SEMANTICS = ("reference", "torch1", "independent")
@@ -91,11 +91,14 @@ class FLSimulation:
                  keep_entries=False):
         if semantics not in SEMANTICS:
             raise NotImplementedError(f"semantics {semantics!r} (supported: {SEMANTICS})")
-        # a robust rule in place of the mean (None: off; today's code paths exactly): (kind, trim)
+        # a robust rule in place of the mean (None: off; today's code paths exactly): (kind, trim),
+        # or ("krum" | "multi_krum", f, m)
         self.robust = parse_rule(robust_rule)
         self.buckets = int(buckets)
         self.keep_entries = bool(keep_entries)
         self.last_entries = None
+        self.last_selected = None       # Krum / Multi-Krum with keep_entries: the entries chosen
+        self.sel_log = []               # per epoch: list of ints (read back) or a device tensor
         if self.robust is not None:
             if self.buckets < 1:
                 raise ValueError(f"buckets = {self.buckets}: it must be >= 1")
@@ -655,7 +658,9 @@ class FLSimulation:
         the pattern the delay classes already follow, at no extra GEMM work.  The entries of the
         rule are the fresh buckets, then the popped delay-class slots in pop order (count = the
         popped workers sharing the slot); one fused robust step (median / trimmed mean of the
-        entries' means + the update) follows, clipped if configured."""
+        entries' means, or Krum / Multi-Krum over them: the entry closest to its neighbours, which
+        drops a popped entry that has drifted away from the fresh buckets; then the update)
+        follows, clipped if configured."""
         from .engine import Robust
         from .schedule import DELAY_ZERO
         t = plan.t
@@ -720,12 +725,26 @@ class FLSimulation:
         if len(entries) > 64:
             raise ValueError(f"robust rule over k = {len(entries)} entries (1 .. 64): fewer "
                              "buckets or delay classes are needed")
-        kind, trim = self.robust
         if self.keep_entries:
             self.last_entries = ([e[:self.P].clone() for e in entries], list(counts))
-        self.step += 1
-        eng.robust_step(Robust(kind, trim, [e[:self.P] for e in entries], counts), self.theta,
-                        self.m, self.v, self.step, optim=self.optim, clip=self.clip)
+        if self.robust[0] in KRUM_KINDS:
+            # Krum / Multi-Krum: f and m against this epoch's k, as the trim is refused below
+            from .engine import Krum
+            _, f, m = self.robust
+            check_krum(f, m, len(entries))
+            self.step += 1
+            krum = Krum(f, m, [e[:self.P] for e in entries], counts)
+            eng.krum_step(krum, self.theta, self.m, self.v, self.step, optim=self.optim,
+                          clip=self.clip)
+            self.sel_log.append(krum.sel.detach().clone())      # (a device tensor: no sync)
+            if self.keep_entries:           # (reads the device selection back: synchronises)
+                self.last_selected = [int(j) for j in krum.sel.tolist()]
+        else:
+            kind, trim = self.robust
+            self.step += 1
+            eng.robust_step(Robust(kind, trim, [e[:self.P] for e in entries], counts),
+                            self.theta, self.m, self.v, self.step, optim=self.optim,
+                            clip=self.clip)
         self.free_slots.extend(entries)
         self._log_norm()
         self.trace.append(plan)
@@ -747,6 +766,14 @@ class FLSimulation:
         only; else []), as floats.  Synchronises on the first call after new epochs."""
         self.norm_log = [float(x) for x in self.norm_log]
         return list(self.norm_log)
+
+    def selections(self):
+        """The entries Krum / Multi-Krum selected in every epoch (else []), as lists of ints:
+        indices into the epoch's entries, the fresh buckets first, then the popped slots.
+        Synchronises on the first call after new epochs."""
+        self.sel_log = [x if isinstance(x, list) else [int(j) for j in x.tolist()]
+                        for x in self.sel_log]
+        return [list(x) for x in self.sel_log]
 
     def losses(self):
         out = []

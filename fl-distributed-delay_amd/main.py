@@ -12,7 +12,9 @@ compensates a stale entry for the distance the model has moved since it was comp
 (torch.nn.utils.clip_grad_norm_) and logs the norm as 'Grad Norm' per epoch.
 --robust_rule {none,median,trimmed_mean} with --trim N and --buckets B replaces the mean by the
 coordinate-wise median or trimmed mean over B bucket means of the fast workers and the popped
-delay-class entries (needs --semantics independent).
+delay-class entries (needs --semantics independent).  --robust_rule {krum,multi_krum} with
+--byz_f F (and --krum_m M) picks the entry closest to its k - F - 2 nearest neighbours, or averages
+the M such entries (Blanchard et al. 2017), and logs the chosen entries as 'Krum Selected'.
 The training loop (main.py:126-188) runs as flsim.sim.FLSimulation: host schedule,
 worker-batched HIP forward/backward, fused rule()+Adam; with
 `torchrun --nproc-per-node N` the computing workers are sharded over N GPUs with one RCCL
@@ -85,9 +87,17 @@ def parse(argv=None):
     p.add_argument('--clip_grad_norm', type=float, default=None, metavar='MAX_NORM',
                    help='clip the aggregated gradient to this global 2-norm before the update, '
                         'as torch.nn.utils.clip_grad_norm_ (default: off; inf only logs the norm)')
-    p.add_argument('--robust_rule', default='none', choices=['none', 'median', 'trimmed_mean'],
-                   help='aggregate with the coordinate-wise median or trimmed mean over bucket '
-                        'means instead of the mean (needs --semantics independent; default: none)')
+    p.add_argument('--robust_rule', default='none',
+                   choices=['none', 'median', 'trimmed_mean', 'krum', 'multi_krum'],
+                   help='aggregate with the coordinate-wise median or trimmed mean, or with Krum / '
+                        'Multi-Krum, over bucket means instead of the mean (needs --semantics '
+                        'independent; default: none)')
+    p.add_argument('--byz_f', type=int, default=None, metavar='F',
+                   help="--robust_rule krum / multi_krum: the Byzantine entries tolerated, the "
+                        "epoch's entry count >= 2F + 3 (required: no default)")
+    p.add_argument('--krum_m', type=int, default=1, metavar='M',
+                   help='--robust_rule multi_krum: entries averaged, 1 <= M <= the entry count - F '
+                        '(default 1)')
     p.add_argument('--trim', type=int, default=1, metavar='N',
                    help='--robust_rule trimmed_mean: entries dropped at each end, 2N < the '
                         "epoch's entry count (default 1)")
@@ -129,6 +139,11 @@ def robust_spec(args):
     """--robust_rule / --trim as FLSimulation's robust_rule spec."""
     if args.robust_rule == 'none':
         return None
+    if args.robust_rule in ('krum', 'multi_krum'):
+        if args.byz_f is None:
+            raise SystemExit(f"--robust_rule {args.robust_rule} needs --byz_f F")
+        return ('krum', args.byz_f) if args.robust_rule == 'krum' else \
+            ('multi_krum', args.byz_f, args.krum_m)
     return 'median' if args.robust_rule == 'median' else ('trimmed_mean', args.trim)
 
 
@@ -197,6 +212,8 @@ def main(argv=None):
         emit("Avg. Loss", loss, t)                                     # main.py:185
         if args.clip_grad_norm is not None:
             emit("Grad Norm", sim.grad_norms()[-1], t)
+        if args.robust_rule in ('krum', 'multi_krum'):
+            emit("Krum Selected", sim.selections()[-1], t)
         if rank == 0 and (t % 10 == 0 or t == args.n_epochs - 1):
             print(f"epoch {t} Avg. Loss {loss:.5f}", flush=True)
         if args.save_model and t % 100 == 0 and t > 0 and rank == 0:   # main.py:192-194

@@ -632,6 +632,78 @@ int flsim_robust_optim_step(const flsim_robust* r, const flsim_clip* clip, float
  * select / sum code the kernel runs; refuses what the entry point refuses about r */
 int flsim_robust_eval_host(const flsim_robust* r, long P, float* g_out);
 
+/* ---------------------------------------------------------------------------------------------
+ * Krum and Multi-Krum (Blanchard et al. 2017) over bucket means, fused with the update: the
+ * entry closest to its neighbours (Krum, m = 1) or the mean of the m such entries (Multi-Krum).
+ * Unlike the rules above it is not coordinate-wise: the distances are over all P elements.  The
+ * text (flsim/robust.py, plain torch):
+ *
+ *   def krum_select(cols, f, m):                 # cols: [k, numel] fp32, already bucket means
+ *       k = cols.shape[0]
+ *       x = cols.double()
+ *       d = torch.stack([((x[i] - x) ** 2).sum(1) for i in range(k)])      # fp64
+ *       d = torch.where(torch.isnan(d), torch.full_like(d, float("inf")), d)
+ *       score = []
+ *       for i in range(k):
+ *           row = torch.cat([d[i, :i], d[i, i + 1:]]).sort().values[:k - f - 2]
+ *           acc = row[0].clone()
+ *           for r in row[1:]:                    # ascending, sequential fp64 adds
+ *               acc += r
+ *           score.append(acc)
+ *       order = sorted(range(k), key=lambda i: (score[i].item(), i))       # ties: lowest index
+ *       return d, torch.stack(score), sorted(order[:m])                    # selection in index order
+ *   def _krum(cols, f, m):
+ *       _, _, sel = krum_select(cols, f, m)
+ *       acc = cols[sel[0]].clone()
+ *       for j in sel[1:]:                        # sequential fp32 adds, ascending entry index
+ *           acc += cols[j]
+ *       return acc / m                           # one IEEE fp32 division
+ *
+ * Per element x_j = entries[j][e] / (float)count[j] as for flsim_robust; a NULL entry is all zero.
+ * Three launches on `stream`, no host synchronisation: the distance launch reads the entries once
+ * and writes, per block, one fp64 sum of ((double)x_i - (double)x_j)^2 for every pair i < j (the
+ * direct difference, never the Gram form) to s->partials; a one-block launch adds the partials in
+ * block order, writes s->dist (symmetric: a pair is computed once and mirrored; zero diagonal; a
+ * NaN distance becomes +inf, so a poisoned entry is never preferred), s->score and s->sel; the
+ * apply launch reads sel on the device, loads the m selected entries only, forms g as the text
+ * does and runs the update of `optim` (every kind).  No atomics: the grid and the element-to-block
+ * map depend on (P, k) alone, so the same shape gives the same bits on every run.
+ *   dist, score: each within 2 (P + 2) 2^-53 (dist) and twice that (score) of the text, relative;
+ *   sel equal to the text's wherever the text's scores are further apart than that; g then equal
+ *   bit for bit.
+ * g_out, optim == NULL and clip as for flsim_robust_optim_step (clip: the apply launch stores g to
+ * clip->G with one fp64 sum of squares per 256 elements; the finish and apply launches of the
+ * clipped entry point follow unchanged).  The library never allocates: the caller provides the
+ * scratch, and nothing depends on what it held before.
+ * Checked before any pointer, status 1: k outside [3, FLSIM_MAX_ARRAYS]; f < 0 or k < 2f + 3;
+ * m outside [1, k - f]; a count < 1; what flsim_optim and flsim_clip are refused for.  Then: what
+ * flsim_robust_optim_step refuses about p / m / v / g_out / P / clip and the entries; a NULL or
+ * misaligned (16 bytes) scratch pointer; n_partials too small; an entry overlapping the scratch.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct flsim_krum {
+    int32_t f, m, k;                            /* k >= 2f+3, 1 <= m <= k-f, k <= FLSIM_MAX_ARRAYS */
+    const float* entries[FLSIM_MAX_ARRAYS];     /* bucket / class SUMS; NULL = all zero */
+    int32_t count[FLSIM_MAX_ARRAYS];            /* >= 1 */
+} flsim_krum;
+typedef struct flsim_krum_scratch {             /* caller-provided; the library never allocates */
+    double* partials; long n_partials;          /* >= flsim_krum_partials(P, k) */
+    double* dist;                               /* [k*k] out: the distance matrix */
+    double* score;                              /* [k]   out */
+    int32_t* sel;                               /* [m]   out: selected entries, ascending */
+} flsim_krum_scratch;
+/* the doubles the distance launch writes for P elements and k entries (0: k or P out of range) */
+long flsim_krum_partials(long P, int k);
+/* (tests) the distance launch's tile: the elements of every entry a block stages at a time */
+long flsim_krum_tile_elems(int k);
+int flsim_krum_optim_step(const flsim_krum* r, const flsim_krum_scratch* s, const flsim_clip* clip,
+                          float* g_out, float* p, float* m, float* v, long P, long step,
+                          const flsim_optim* optim, flsim_stream_t stream);
+/* host (testing): dist [k*k], score [k], sel [m] and g (g_out nullable) of the text for host
+ * pointers: the distances summed in element order, then the score / selection code the finish
+ * kernel runs; refuses what the entry point refuses about r */
+int flsim_krum_eval_host(const flsim_krum* r, long P, double* dist, double* score, int32_t* sel,
+                         float* g_out);
+
 #ifdef __cplusplus
 }
 #endif

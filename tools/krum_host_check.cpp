@@ -1,0 +1,359 @@
+// Stand-alone host check of Krum / Multi-Krum's host code (csrc/server.hip: check_krum, the pointer
+// checks of flsim_krum_optim_step, flsim_krum_partials, flsim_krum_eval_host; csrc/krum.h: the score /
+// selection code the finish kernel shares with the twin), meant to be built with the host
+// sanitizers and run on a CPU-only machine, as tools/robust_host_check.cpp is for the coordinate-wise
+// rules.  Nothing here launches a kernel: the entry point is only driven into its refusals, which
+// come before any launch.
+//
+//   cd fl-distributed-delay_amd && hipcc -O1 -g -std=c++17 --offload-arch=gfx950 \
+//       -ffp-contract=off -Xarch_host -fsanitize=address,undefined \
+//       -Xarch_host -fno-sanitize-recover=undefined -I../include -Icsrc -x hip \
+//       csrc/server.hip csrc/probe.cpp ../tools/krum_host_check.cpp \
+//       -fsanitize=address,undefined -o /tmp/krum_host_check && /tmp/krum_host_check
+//
+// The twin runs on exactly-sized heap buffers (ASan sees any over-read or over-write) for every k
+// in 3 .. 64 and is compared with the text restated here in plain C: one fp32 division per value,
+// fp64 sums of squared fp64 differences, NaN -> +inf, a stable sort of each row's off-diagonal
+// distances and sequential fp64 adds of the first k - f - 2, the m lowest (score, index), sequential
+// fp32 adds of the selected means in index order and one division.
+#include <math.h>
+#include <stdarg.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "flsim.h"
+
+// the library's error slot lives with the network engines (csrc/pn1_net.hip), which this program
+// does not link: the same few lines
+namespace flsim {
+static thread_local char g_err[512];
+void set_error(const char* fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_err, sizeof(g_err), fmt, ap);
+    va_end(ap);
+}
+const char* last_error() { return g_err; }
+}  // namespace flsim
+extern "C" const char* flsim_last_error(void) { return flsim::last_error(); }
+
+static uint32_t bits(float x) {
+    uint32_t u;
+    memcpy(&u, &x, 4);
+    return u;
+}
+
+static int fails = 0;
+#define EXPECT(cond)                                                       \
+    do {                                                                   \
+        if (!(cond)) {                                                     \
+            printf("FAIL %s:%d %s [%s]\n", __FILE__, __LINE__, #cond, flsim_last_error()); \
+            ++fails;                                                       \
+        }                                                                  \
+    } while (0)
+
+// |got - ref| <= rel * ref, or both +inf
+static bool close_to(double got, double ref, double rel) {
+    if (isinf(ref)) return got == ref;
+    return fabs(got - ref) <= rel * ref;
+}
+
+int main() {
+    // ---- the host twin, every k in 3 .. 64 ----------------------------------------------------------
+    uint32_t seed = 2025;
+    auto rnd = [&]() {
+        seed = seed * 1664525u + 1013904223u;
+        return (float)((int)(seed >> 8) - (1 << 23)) * 0x1p-20f;
+    };
+    long checked = 0;
+    for (int k = 3; k <= FLSIM_MAX_ARRAYS; ++k) {
+        const long P = 1 + (k * 7) % 37;
+        const double bound = 2.0 * (double)(P + 2) * 0x1p-53;
+        auto* r = new flsim_krum();
+        std::vector<float*> ent(k, nullptr);
+        for (int j = 0; j < k; ++j) {
+            r->count[j] = 1 + (j + k) % 4;
+            if (k > 4 && j == k / 2) continue;              // one NULL entry: all zeros
+            ent[j] = new float[P];
+            for (long e = 0; e < P; ++e) ent[j][e] = rnd() * (float)r->count[j];
+            if (k % 5 == 0 && j == 1) ent[j][P / 2] = NAN;  // a poisoned entry
+            if (k % 7 == 0 && j == 0) ent[j][0] = INFINITY;
+            r->entries[j] = ent[j];
+        }
+        if (k % 6 == 0) r->entries[k - 1] = r->entries[0];  // a duplicate pointer
+        r->k = k;
+        double* dist = new double[(size_t)k * k];
+        double* score = new double[k];
+        float* g = new float[P];
+        for (int f = 0; k >= 2 * f + 3; f += (f < 2 ? 1 : 7))
+            for (int m : {1, 2, (k - f + 1) / 2, k - f}) {
+                if (m < 1 || m > k - f) continue;
+                r->f = f;
+                r->m = m;
+                int32_t* sel = new int32_t[m];
+                EXPECT(flsim_krum_eval_host(r, P, dist, score, sel, g) == 0);
+                // the text
+                std::vector<std::vector<float>> x(k, std::vector<float>(P));
+                for (int j = 0; j < k; ++j)
+                    for (long e = 0; e < P; ++e) {
+                        volatile float s = r->entries[j] ? r->entries[j][e] : 0.f;
+                        volatile float c = (float)r->count[j];
+                        x[j][e] = s / c;
+                    }
+                std::vector<double> d((size_t)k * k), sc(k);
+                for (int i = 0; i < k; ++i)
+                    for (int j = 0; j < k; ++j) {
+                        volatile double a = 0.0;
+                        for (long e = 0; e < P; ++e) {
+                            volatile double t = (double)x[i][e] - (double)x[j][e];
+                            volatile double q = t * t;
+                            a = a + q;
+                        }
+                        d[(size_t)i * k + j] = a != a ? (double)INFINITY : (double)a;
+                    }
+                bool near_tie = false;
+                for (int i = 0; i < k; ++i) {
+                    std::vector<double> row;
+                    for (int j = 0; j < k; ++j)
+                        if (j != i) row.push_back(d[(size_t)i * k + j]);
+                    std::stable_sort(row.begin(), row.end());
+                    volatile double a = row[0];
+                    for (int t = 1; t < k - f - 2; ++t) a = a + row[t];
+                    sc[i] = a;
+                }
+                std::vector<int> order(k);
+                for (int i = 0; i < k; ++i) order[i] = i;
+                std::stable_sort(order.begin(), order.end(),
+                                 [&](int a, int b) { return sc[a] < sc[b]; });
+                if (m < k && isfinite(sc[order[m - 1]]) &&
+                    sc[order[m]] - sc[order[m - 1]] <= 1000 * bound * sc[order[m - 1]] &&
+                    sc[order[m]] != sc[order[m - 1]])
+                    near_tie = true;                        // (the selection may then differ)
+                std::vector<int> want(order.begin(), order.begin() + m);
+                std::sort(want.begin(), want.end());
+                for (int i = 0; i < k; ++i) {
+                    for (int j = 0; j < k; ++j) {
+                        if (i == j) {
+                            EXPECT(dist[(size_t)i * k + j] == 0.0);
+                            continue;
+                        }
+                        EXPECT(close_to(dist[(size_t)i * k + j], d[(size_t)i * k + j], bound));
+                        EXPECT(memcmp(&dist[(size_t)i * k + j], &dist[(size_t)j * k + i], 8) == 0);
+                    }
+                    EXPECT(close_to(score[i], sc[i], 2 * bound));
+                    ++checked;
+                }
+                if (!near_tie) {
+                    for (int t = 0; t < m; ++t) EXPECT(sel[t] == want[t]);
+                    for (long e = 0; e < P; ++e) {
+                        volatile float a = x[want[0]][e];
+                        for (int t = 1; t < m; ++t) a = a + x[want[t]][e];
+                        volatile float fm = (float)m;
+                        const float ref = a / fm;
+                        EXPECT(ref != ref ? g[e] != g[e] : bits(g[e]) == bits(ref));
+                    }
+                }
+                delete[] sel;
+            }
+        delete[] dist;
+        delete[] score;
+        delete[] g;
+        for (float* p : ent) delete[] p;
+        delete r;
+    }
+    printf("host twin: %ld rows checked against the text for k = 3 .. %d\n", checked,
+           FLSIM_MAX_ARRAYS);
+
+    // ---- the entry point's checks: heap structs, every refusal before a launch (made-up device
+    // addresses are never read on the host) --------------------------------------------------------
+    auto* r = new flsim_krum();
+    auto* s = new flsim_krum_scratch();
+    auto* clip = new flsim_clip();
+    flsim_optim o{};
+    const long P = 64;
+    float* fP = reinterpret_cast<float*>(0x200000);
+    float* fM = reinterpret_cast<float*>(0x300000);
+    float* fV = reinterpret_cast<float*>(0x400000);
+    float* fG = reinterpret_cast<float*>(0x500000);
+    double* fD = reinterpret_cast<double*>(0x600000);
+    float* fO = reinterpret_cast<float*>(0x700000);
+    float* fE = reinterpret_cast<float*>(0x800000);
+    float* fX = reinterpret_cast<float*>(0x900000);
+    double* sP = reinterpret_cast<double*>(0xA00000);
+    double* sD = reinterpret_cast<double*>(0xB00000);
+    double* sS = reinterpret_cast<double*>(0xC00000);
+    int32_t* sL = reinterpret_cast<int32_t*>(0xD00000);
+    auto reset = [&]() {
+        memset(r, 0, sizeof(*r));
+        r->f = 1;
+        r->m = 2;
+        r->k = 5;
+        for (int j = 0; j < 5; ++j) {
+            r->entries[j] = fE + 0x1000 * j;
+            r->count[j] = 1 + j;
+        }
+        s->partials = sP;
+        s->n_partials = 1 << 20;
+        s->dist = sD;
+        s->score = sS;
+        s->sel = sL;
+        clip->max_norm = 1.f;
+        clip->G = fG;
+        clip->partials = fD;
+        clip->n_partials = 1 << 20;
+        clip->out = fO;
+        o = flsim_optim{};
+        o.kind = FLSIM_OPT_SGD;
+        o.lr = 0.1;
+    };
+    auto call = [&](const flsim_clip* c, float* g_out, float* p, float* m, float* v, long n,
+                    long step, const flsim_optim* op) {
+        return flsim_krum_optim_step(r, s, c, g_out, p, m, v, n, step, op, nullptr);
+    };
+    auto refused = [&](int rc, const char* what) {
+        EXPECT(rc == 1);
+        EXPECT(strstr(flsim_last_error(), what) != nullptr);
+    };
+    reset();
+    refused(flsim_krum_optim_step(nullptr, s, nullptr, nullptr, fP, nullptr, nullptr, P, 1, &o,
+                                  nullptr), "null Krum rule");
+    // hyper-parameters first: every pointer is NULL in these calls
+    for (int k : {0, -3, 2, FLSIM_MAX_ARRAYS + 1, 1 << 30}) {
+        reset();
+        r->k = k;
+        r->f = 0;
+        refused(call(nullptr, nullptr, nullptr, nullptr, nullptr, P, 1, &o), "entries (3 .. 64)");
+    }
+    for (int f : {-1, 2, 40, 0x7FFFFFFF}) {
+        reset();
+        r->f = f;
+        refused(call(nullptr, nullptr, nullptr, nullptr, nullptr, P, 1, &o), "Invalid f");
+    }
+    for (int m : {0, -1, 5, 0x7FFFFFFF}) {
+        reset();
+        r->m = m;
+        refused(call(nullptr, nullptr, nullptr, nullptr, nullptr, P, 1, &o), "Invalid m");
+    }
+    for (int c : {0, -1, (int)0x80000000}) {
+        reset();
+        r->count[2] = c;
+        refused(call(nullptr, nullptr, nullptr, nullptr, nullptr, P, 1, &o), "Invalid count");
+    }
+    reset();
+    o.lr = -1.0;
+    refused(call(nullptr, nullptr, nullptr, nullptr, nullptr, P, 1, &o), "Invalid learning rate");
+    reset();
+    o.kind = 9;
+    refused(call(nullptr, nullptr, nullptr, nullptr, nullptr, P, 1, &o), "unknown optimizer kind");
+    for (float bad : {0.f, -1.f, NAN, -INFINITY}) {
+        reset();
+        clip->max_norm = bad;
+        refused(call(clip, nullptr, nullptr, nullptr, nullptr, P, 1, &o), "max_norm");
+    }
+    reset();
+    refused(call(nullptr, nullptr, fP, nullptr, nullptr, P, 1, nullptr), "null optimizer");
+    refused(call(clip, fX, fP, nullptr, nullptr, P, 1, nullptr), "null optimizer");
+    // then the pointers
+    refused(call(nullptr, nullptr, nullptr, nullptr, nullptr, P, 1, &o), "null pointer");
+    o.momentum = 0.9;
+    refused(call(nullptr, nullptr, fP, nullptr, nullptr, P, 1, &o), "null pointer");
+    o.kind = FLSIM_OPT_ADAM;
+    refused(call(nullptr, nullptr, fP, fM, nullptr, P, 1, &o), "null pointer");
+    refused(call(nullptr, nullptr, fP, fM, fV, P, 0, &o), "step must be >= 1");
+    refused(call(nullptr, nullptr, fP + 1, fM, fV, P, 1, &o), "16-byte aligned");
+    refused(call(nullptr, fX + 1, fP, fM, fV, P, 1, &o), "16-byte aligned");
+    for (long n : {0L, -5L, 1L << 31})
+        refused(call(nullptr, nullptr, fP, fM, fV, n, 1, &o), "out of range");
+    refused(call(nullptr, fP + 32, fP, fM, fV, P, 1, &o), "overlap each other");
+    // the scratch
+    reset();
+    {
+        const flsim_krum_scratch* keep = s;
+        EXPECT(flsim_krum_optim_step(r, nullptr, nullptr, nullptr, fP, nullptr, nullptr, P, 1, &o,
+                                     nullptr) == 1);
+        EXPECT(strstr(flsim_last_error(), "null Krum scratch") != nullptr);
+        (void)keep;
+    }
+    reset();
+    s->dist = nullptr;
+    refused(call(nullptr, nullptr, fP, nullptr, nullptr, P, 1, &o), "null Krum scratch");
+    reset();
+    s->sel = nullptr;
+    refused(call(nullptr, nullptr, fP, nullptr, nullptr, P, 1, &o), "null Krum scratch");
+    reset();
+    s->partials = sP + 1;
+    refused(call(nullptr, nullptr, fP, nullptr, nullptr, P, 1, &o), "Krum scratch must be 16-byte");
+    reset();
+    s->sel = sL + 1;
+    refused(call(nullptr, nullptr, fP, nullptr, nullptr, P, 1, &o), "Krum scratch must be 16-byte");
+    reset();
+    s->n_partials = flsim_krum_partials(P, 5) - 1;
+    refused(call(nullptr, nullptr, fP, nullptr, nullptr, P, 1, &o), "Krum n_partials");
+    reset();
+    s->score = sD + 2;
+    refused(call(nullptr, nullptr, fP, nullptr, nullptr, P, 1, &o), "scratch buffers overlap");
+    reset();
+    s->dist = reinterpret_cast<double*>(fP + 32);
+    refused(call(nullptr, nullptr, fP, nullptr, nullptr, P, 1, &o), "scratch overlaps p/m/v/g_out");
+    reset();
+    s->sel = reinterpret_cast<int32_t*>(fG + 16);
+    refused(call(clip, nullptr, fP, nullptr, nullptr, P, 1, &o), "scratch overlaps clip G");
+    // the entries
+    reset();
+    r->entries[1] = reinterpret_cast<const float*>(0x801002);
+    refused(call(nullptr, nullptr, fP, nullptr, nullptr, P, 1, &o), "4-byte aligned");
+    for (const float* over : {(const float*)fP, (const float*)(fP + 63), (const float*)(fP - 63),
+                              (const float*)fX}) {
+        reset();
+        r->entries[2] = over;
+        refused(call(nullptr, fX, fP, nullptr, nullptr, P, 1, &o), "entry 2 overlaps");
+    }
+    reset();
+    r->entries[0] = fG + 60;
+    refused(call(clip, nullptr, fP, nullptr, nullptr, P, 1, &o), "entry 0 overlaps clip G");
+    for (const void* over : {(const void*)sP, (const void*)(sD + 3), (const void*)sS,
+                             (const void*)sL, (const void*)((const float*)sL - 63)}) {
+        reset();
+        r->entries[4] = reinterpret_cast<const float*>(over);
+        refused(call(nullptr, nullptr, fP, nullptr, nullptr, P, 1, &o),
+                "entry 4 overlaps the Krum scratch");
+    }
+    reset();
+    clip->G = nullptr;
+    refused(call(clip, nullptr, fP, nullptr, nullptr, P, 1, &o), "null clip buffer");
+    reset();
+    clip->n_partials = 0;
+    refused(call(clip, nullptr, fP, nullptr, nullptr, P, 1, &o), "clip n_partials");
+    // the twin's own refusals
+    reset();
+    double d25[25], s5[5];
+    int32_t l2[2];
+    float g1[1];
+    r->k = 2;
+    EXPECT(flsim_krum_eval_host(r, 1, d25, s5, l2, g1) == 1);
+    reset();
+    EXPECT(flsim_krum_eval_host(r, 0, d25, s5, l2, g1) == 1);
+    EXPECT(flsim_krum_eval_host(r, 1, nullptr, s5, l2, g1) == 1);
+    EXPECT(flsim_krum_eval_host(r, 1, d25, nullptr, l2, g1) == 1);
+    EXPECT(flsim_krum_eval_host(r, 1, d25, s5, nullptr, g1) == 1);
+    EXPECT(flsim_krum_eval_host(nullptr, 1, d25, s5, l2, g1) == 1);
+    // the partials: positive and a whole number of 4 x 4 pair blocks for every valid shape
+    for (int k = 1; k <= FLSIM_MAX_ARRAYS; ++k)
+        for (long n : {1L, 255L, 257L, 5596090L, (1L << 31) - 1}) {
+            const long need = flsim_krum_partials(n, k);
+            EXPECT(need >= (long)k * (k - 1) / 2 && need > 0 && need % 16 == 0);
+            EXPECT(flsim_krum_tile_elems(k) >= 4);
+        }
+    EXPECT(flsim_krum_partials(0, 8) == 0 && flsim_krum_partials(64, 0) == 0 &&
+           flsim_krum_partials(64, 65) == 0 && flsim_krum_tile_elems(65) == 0);
+    delete r;
+    delete s;
+    delete clip;
+    printf(fails ? "%d checks FAILED\n" : "all checks passed\n", fails);
+    return fails != 0;
+}
