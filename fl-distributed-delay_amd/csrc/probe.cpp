@@ -18,7 +18,8 @@ static const char* KNAME[K_COUNT] = {
     "vgg_linear1_wgrad", "vgg_linear1_dgrad", "vgg_linear2_wgrad", "vgg_linear2_dgrad",
     "aggregate_adam_seq", "slab_step", "slab_step_seq", "slab_sum",
     "aggregate_gout", "clip_finish", "clip_apply", "robust_step",
-    "krum_dist", "krum_finish", "krum_apply"};
+    "krum_dist", "krum_finish", "krum_apply",
+    "geomed_dist", "geomed_finish", "geomed_apply"};
 
 struct Probe {
     bool on = false;

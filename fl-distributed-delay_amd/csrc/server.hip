@@ -38,6 +38,7 @@
 
 #include "common.h"
 #include "flsim.h"
+#include "geomed.h"
 #include "krum.h"
 #include "probe.h"
 #include "robust.h"
@@ -2202,6 +2203,441 @@ static bool overlaps_bytes(const void* a, long na, const void* b, long nb) {
            (uintptr_t)b < (uintptr_t)a + (uintptr_t)na;
 }
 
+// ================================================================================================
+// Geometric median (RFA, smoothed Weiszfeld): distances to the iterate, the scalar step, apply
+// (include/flsim.h: flsim_geomed; csrc/geomed.h: the geometry and the scalar code shared with the
+// host)
+// ================================================================================================
+struct GeomedDistArgs {
+    const float* ent[RULE_MAX_ARR];     // bucket / class sums; nullptr = an all-zero entry
+    float cnt[RULE_MAX_ARR];            // x_j = ent[j][e] / cnt[j], as k_robust forms it
+    float rcnt[RULE_MAX_ARR];
+    double w0[RULE_MAX_ARR];            // pair 0: w^(0) of "every entry alive" (the host's, fp64)
+    const double* w;                    // later pairs: s->w, written by the finish launches
+    const int32_t* state;               // later pairs: the dead flags [k], then the control words
+    double* partials;                   // [k + 1][grid]
+    long P;
+    int k, ntiles, pair, iters;
+};
+static_assert(sizeof(GeomedDistArgs) <= 4096, "kernel argument block");
+
+// Values an earlier launch wrote and this launch only reads, at launch-uniform addresses: through
+// the constant address space they are scalar loads, like the kernel arguments (k_geomed_apply).
+typedef const double __attribute__((address_space(4)))* GeomedConstF64;
+
+// One streaming pass over the k entries for the iterate z of weights w: thread t of the block's
+// 256 owns the elements u * 256 + t, u < U, of a tile (a wave's load is one coalesced 256-byte row;
+// an entry need only be 4-byte aligned) and a block grid-strides over the tiles.  All k * U loads
+// of a thread are issued before any arithmetic, non-temporally: each byte is read once.  Per
+// element the bucket means x_j = ent / cnt (one fp32 division each, where it is loaded), then
+// z = sum_j w_j * x_j: fp64, index order, one multiply and one add per term with contraction off,
+// and ((double)x_j - z)^2 into the thread's k fp64 sums by one fma each.  z starts from +0.0 and
+// a term of weight 0 (a dead entry: not loaded, x = 0) adds +-0: that differs from _wsum, which
+// skips such a term and starts from the first one kept, in the sign of a zero z at most, which
+// (x - z)^2 does not see.  The sums stay in registers over all the block's tiles; at the end each
+// is added over the wave by a butterfly and over the four waves as (w0 + w1) + (w2 + w3), a fixed
+// order, and written slot-major.
+// The per-entry table (pointer, count, its reciprocal, weight: 384 words at KPAD = 64, more than
+// the scalar registers hold) lives in LDS and is read by broadcast (all lanes one address), GRP
+// entries at a time; a group wholly past k is skipped by a scalar branch, and inside a group
+// nothing branches: an entry that is not loaded (NULL, dead, past k) reads the block's first loaded
+// entry instead and an element past P reads element 0, and both are replaced by 0.
+// PAIR0: the weights are the kernel arguments; every entry is loaded, and each thread notes in a
+// 64-bit mask which entries held a NaN or an inf (OR-ed over the block into slot k): the finish
+// launch finds the dead entries there.  (A second fp64 sum per entry for that would double the
+// accumulators: 256 VGPRs at KPAD = 64.)
+// Later pairs: iteration it = pair - redo; it == iters: one word is read and the block is out.  A
+// dead entry is not loaded (its sum is ignored by the finish launch).
+typedef const float __attribute__((address_space(1)))* GeomedGlobalF32;
+
+template <int KPAD, bool PAIR0>
+__global__ void __launch_bounds__(256) k_geomed_dist(GeomedDistArgs A) {
+#pragma clang fp contract(off)
+    constexpr int U = geomed_unroll(KPAD), E = geomed_tile_elems(KPAD);
+    constexpr int GRP = KPAD < 8 ? KPAD : 8;
+    __shared__ unsigned long long s_ent[KPAD];  // the address loaded for entry j
+    __shared__ double s_w[KPAD];
+    __shared__ float s_cnt[KPAD], s_rcnt[KPAD];
+    __shared__ unsigned long long s_mask;       // bit j: entry j is loaded
+    {
+        int it = 0;
+        if constexpr (!PAIR0) {
+            it = A.pair - A.state[A.k + GEOMED_ST_REDO];
+            if (it >= A.iters) return;
+        }
+        const int j = threadIdx.x;
+        if (j < 64) {                           // (wave 0: lane j is entry j)
+            const float* src = nullptr;
+            double w = 0.0;
+            float c = 1.f, rc = 1.f;
+            if (j < A.k) {
+                src = A.ent[j];
+                c = A.cnt[j];
+                rc = A.rcnt[j];
+                if constexpr (PAIR0) {
+                    w = A.w0[j];
+                } else {
+                    w = A.w[(long)it * A.k + j];
+                    if (A.state[j]) src = nullptr;
+                }
+            }
+            const unsigned long long ml = __ballot(src != nullptr);
+            const int first = ml ? __builtin_ctzll(ml) : 0;
+            const unsigned long long any = __shfl((unsigned long long)(uintptr_t)src, first, 64);
+            if (j < KPAD) {
+                s_ent[j] = src ? (unsigned long long)(uintptr_t)src : any;
+                s_w[j] = w;
+                s_cnt[j] = c;
+                s_rcnt[j] = rc;
+            }
+            if (j == 0) s_mask = ml;
+        }
+        __syncthreads();
+    }
+    // launch-uniform: a scalar register pair, tested by scalar bit compares
+    const uint64_t ld_mask =
+        ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(s_mask >> 32)) << 32) |
+        (uint32_t)__builtin_amdgcn_readfirstlane((int)s_mask);
+    double acc[KPAD];
+#pragma unroll
+    for (int j = 0; j < KPAD; ++j) acc[j] = 0.0;
+    uint32_t bad_lo = 0, bad_hi = 0;
+    for (int tl = blockIdx.x; tl < A.ntiles; tl += gridDim.x) {
+        // the table is read, and the mask and k tested, again in every tile: hoisted out of the
+        // loop they would take some 400 registers
+        asm volatile("" ::: "memory");
+        int m_lo = (int)ld_mask, m_hi = (int)(ld_mask >> 32), k = A.k;
+        asm volatile("" : "+v"(m_lo), "+v"(m_hi), "+v"(k));
+        k = __builtin_amdgcn_readfirstlane(k);
+        const uint64_t ldm = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane(m_hi) << 32) |
+                             (uint32_t)__builtin_amdgcn_readfirstlane(m_lo);
+        const long e0 = (long)tl * E + threadIdx.x;
+        bool inb[U];
+        long off[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            inb[u] = e0 + u * 256 < A.P;
+            off[u] = inb[u] ? e0 + u * 256 : 0;
+        }
+        float x[U][KPAD];
+#pragma unroll
+        for (int j0 = 0; j0 < KPAD; j0 += GRP) {
+            if (j0 < k && ldm != 0) {
+#pragma unroll
+                for (int j = j0; j < j0 + GRP; ++j) {
+                    const GeomedGlobalF32 src = (GeomedGlobalF32)s_ent[j];
+#pragma unroll
+                    for (int u = 0; u < U; ++u)
+                        x[u][j] = __builtin_nontemporal_load(src + off[u]);
+                }
+            } else {
+#pragma unroll
+                for (int j = j0; j < j0 + GRP; ++j)
+#pragma unroll
+                    for (int u = 0; u < U; ++u) x[u][j] = 0.f;
+            }
+        }
+        double z[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) z[u] = 0.0;
+#pragma unroll
+        for (int j0 = 0; j0 < KPAD; j0 += GRP) {
+            if (j0 < k) {
+#pragma unroll
+                for (int j = j0; j < j0 + GRP; ++j) {
+                    const float c = s_cnt[j], rc = s_rcnt[j];
+                    const double w = s_w[j];
+                    const bool ld = (ldm >> j) & 1;
+#pragma unroll
+                    for (int u = 0; u < U; ++u) {
+                        const float y = div_const((ld && inb[u]) ? x[u][j] : 0.f, c, rc);
+                        x[u][j] = y;
+                        if constexpr (PAIR0) {
+                            const uint32_t nf =
+                                !(fabsf(y) < __builtin_inff()) ? 1u << (j & 31) : 0u;
+                            if (j < 32) bad_lo |= nf;
+                            else bad_hi |= nf;
+                        }
+                        const double t = (double)y * w;
+                        z[u] = z[u] + t;
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) z[u] = inb[u] ? z[u] : 0.0;    // (past P: the sums gain 0)
+#pragma unroll
+        for (int j0 = 0; j0 < KPAD; j0 += GRP) {
+            if (j0 < k) {
+#pragma unroll
+                for (int j = j0; j < j0 + GRP; ++j)
+#pragma unroll
+                    for (int u = 0; u < U; ++u) {
+                        const double d = (double)x[u][j] - z[u];
+                        acc[j] = __builtin_fma(d, d, acc[j]);
+                    }
+            }
+        }
+    }
+    __shared__ double red[4][KPAD + 1];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int j = 0; j < KPAD; ++j) {
+        if (j < A.k) {
+            double a = acc[j];
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
+            if (lane == 0) red[wave][j] = a;
+        }
+    }
+    if constexpr (PAIR0) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            bad_lo |= (uint32_t)__shfl_xor((int)bad_lo, o, 64);
+            bad_hi |= (uint32_t)__shfl_xor((int)bad_hi, o, 64);
+        }
+        if (lane == 0)
+            red[wave][KPAD] = __builtin_bit_cast(double, ((uint64_t)bad_hi << 32) | bad_lo);
+    }
+    __syncthreads();
+    const int t = threadIdx.x;
+    if (t < A.k)
+        A.partials[(long)t * gridDim.x + blockIdx.x] =
+            (red[0][t] + red[1][t]) + (red[2][t] + red[3][t]);
+    if constexpr (PAIR0) {
+        if (t == 64) {
+            uint64_t mk = 0;
+#pragma unroll
+            for (int w = 0; w < 4; ++w) mk |= __builtin_bit_cast(uint64_t, red[w][KPAD]);
+            reinterpret_cast<uint64_t*>(A.partials)[(long)A.k * gridDim.x + blockIdx.x] = mk;
+        }
+    }
+}
+
+struct GeomedFinArgs {
+    int32_t count[RULE_MAX_ARR];
+    const double* partials;             // [k + 1][nblocks]
+    double* w;                          // s->w
+    double* d2;                         // s->d2
+    double* obj;                        // s->obj
+    int32_t* state;                     // s->state
+    double nu;
+    int nblocks, k, pair, iters, weighted;
+};
+
+// One block of 16 waves.  Entry j's sum belongs to one wave: lane l adds the partials of the
+// blocks l, l + 64, ... in index order (coalesced: the partials are slot-major) and a butterfly
+// adds the 64 lanes, as k_krum_finish does -- a fixed order for a given (P, k).  Pair 0 also ORs
+// the blocks' masks, writes the dead flags and the control words, and w^(0) over the live entries
+// (the host's, bit for bit, when none is dead); with a dead entry its distances are worthless (z was
+// a NaN) and it stops there: "redo".  Then csrc/geomed.h's scalar code of one iteration on the
+// sums in LDS, and d2, obj and the next w.
+constexpr int GEOMED_FIN_THREADS = 1024;
+
+__global__ void __launch_bounds__(GEOMED_FIN_THREADS) k_geomed_finish(GeomedFinArgs A) {
+    __shared__ double sd[RULE_MAX_ARR], sa[RULE_MAX_ARR], sw[RULE_MAX_ARR], sterm[RULE_MAX_ARR];
+    __shared__ double ssum[2];
+    __shared__ int32_t sdead[RULE_MAX_ARR];
+    __shared__ unsigned long long smask[GEOMED_FIN_THREADS / 64];
+    __shared__ int32_t sgo;
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, k = A.k;
+    int it = 0;
+    if (A.pair > 0) {
+        it = A.pair - A.state[k + GEOMED_ST_REDO];
+        if (it >= A.iters) return;
+    }
+    for (int j = wave; j < k; j += GEOMED_FIN_THREADS / 64) {
+        const double* src = A.partials + (long)j * A.nblocks;
+        double a = 0.0;
+#pragma unroll 8
+        for (int b = lane; b < A.nblocks; b += 64) a += src[b];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
+        if (lane == 0) sd[j] = a;
+    }
+    if (A.pair == 0) {
+        const unsigned long long* src =
+            reinterpret_cast<const unsigned long long*>(A.partials) + (long)k * A.nblocks;
+        unsigned long long mk = 0;
+        for (int b = t; b < A.nblocks; b += GEOMED_FIN_THREADS) mk |= src[b];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) mk |= __shfl_xor(mk, o, 64);
+        if (lane == 0) smask[wave] = mk;
+        __syncthreads();
+        if (t < k) {
+            unsigned long long all = 0;
+            for (int w = 0; w < GEOMED_FIN_THREADS / 64; ++w) all |= smask[w];
+            const int32_t dead = (int32_t)((all >> t) & 1);
+            sdead[t] = dead;
+            A.state[t] = dead;
+            sa[t] = geomed_alpha(A.weighted, A.count[t], dead);
+        }
+        __syncthreads();
+        if (t == 0) {
+            int nd = 0;
+            for (int j = 0; j < k; ++j) nd += sdead[j];
+            A.state[k + GEOMED_ST_REDO] = nd > 0;
+            A.state[k + GEOMED_ST_NDEAD] = nd;
+            for (int c = 2; c < GEOMED_ST_WORDS; ++c) A.state[k + c] = 0;
+            ssum[0] = geomed_seqsum(sa, k);
+            sgo = nd == 0 && A.iters > 0;
+        }
+        __syncthreads();
+        if (t < k) A.w[t] = sa[t] / ssum[0];
+        if (!sgo) return;
+        __syncthreads();                // (ssum is rewritten below)
+    } else {
+        if (t < k) {
+            const int32_t dead = A.state[t];
+            sdead[t] = dead;
+            sa[t] = geomed_alpha(A.weighted, A.count[t], dead);
+        }
+        __syncthreads();
+    }
+    geomed_iterate(sd, sa, sdead, k, A.nu, sterm, ssum, sw, t, GEOMED_FIN_THREADS,
+                   [] { __syncthreads(); });
+    if (t < k) {
+        A.d2[(long)it * k + t] = sd[t];
+        A.w[(long)(it + 1) * k + t] = sw[t];
+    }
+    if (t == 0) A.obj[it] = ssum[0];
+}
+
+struct GeomedApplyArgs {
+    const float* ent[RULE_MAX_ARR];
+    float cnt[RULE_MAX_ARR];
+    float rcnt[RULE_MAX_ARR];
+    const double* w;                    // w^(iters) (device memory, written by a finish launch)
+    float* g_out;                       // nullable: g is also written here
+    float* G;                           // OK_GOUT, nullable: the clipped step's G
+    double* partials;                   // OK_GOUT, nullable: block b's sum of g * g (fp64)
+    float* p;
+    float* m;
+    float* v;
+    long P;
+    int k;
+    AdamConst ac;
+    OptConst oc;
+};
+static_assert(sizeof(GeomedApplyArgs) <= 4096, "kernel argument block");
+
+// One thread owns one element, as k_krum_apply.  The weights are launch-uniform scalar loads;
+// an entry of weight 0 (a dead one) is not loaded, eight loads in flight.  z as _wsum forms it
+// (k_geomed_dist), g = (float)z: one fp64 -> fp32 rounding.  Then the update of kind OK, or
+// OK_GOUT as k_robust.
+template <int OK>
+__global__ void __launch_bounds__(256) k_geomed_apply(GeomedApplyArgs A) {
+#pragma clang fp contract(off)
+    constexpr bool HAS_M = opt_n_state(OK) >= 1, HAS_V = opt_n_state(OK) == 2;
+    const long e = (long)blockIdx.x * 256 + threadIdx.x;
+    const bool live = e < A.P;
+    if constexpr (OK != OK_GOUT) {
+        if (!live) return;
+    }
+    float p = 0.f, m = 0.f, v = 0.f;
+    if constexpr (OK != OK_GOUT) p = __builtin_nontemporal_load(A.p + e);
+    if constexpr (HAS_M) m = __builtin_nontemporal_load(A.m + e);
+    if constexpr (HAS_V) v = __builtin_nontemporal_load(A.v + e);
+    GeomedConstF64 wdev = (GeomedConstF64)(uintptr_t)A.w;
+    double z = 0.0;
+    bool have = false;
+    for (int j0 = 0; j0 < A.k; j0 += 8) {
+        float x[8], c[8], rc[8];
+        double w[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            x[u] = 0.f;
+            c[u] = 1.f;
+            rc[u] = 1.f;
+            w[u] = 0.0;
+            if (j0 + u < A.k) {
+                const int j = j0 + u;
+                const float* src = A.ent[j];
+                w[u] = wdev[j];
+                c[u] = A.cnt[j];
+                rc[u] = A.rcnt[j];
+                if (geomed_nonzero(w[u]) && src && live) x[u] = __builtin_nontemporal_load(src + e);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            if (j0 + u < A.k && geomed_nonzero(w[u])) {
+                const double t = (double)div_const(x[u], c[u], rc[u]) * w[u];
+                z = have ? z + t : t;
+                have = true;
+            }
+        }
+    }
+    const float g = (float)z;
+    if constexpr (OK == OK_GOUT) {
+        if (live) {
+            if (A.g_out) __builtin_nontemporal_store(g, A.g_out + e);
+            if (A.G) __builtin_nontemporal_store(g, A.G + e);
+        }
+        if (A.partials) {
+            __shared__ double red[4];
+            const double s = block_sum_f64(live ? (double)g * (double)g : 0.0, red);
+            if (threadIdx.x == 0) A.partials[blockIdx.x] = s;
+        }
+    } else {
+        if (A.g_out) __builtin_nontemporal_store(g, A.g_out + e);
+        opt_update<OK>(A.ac, A.oc, g, p, m, v);
+        __builtin_nontemporal_store(p, A.p + e);
+        if constexpr (HAS_M) __builtin_nontemporal_store(m, A.m + e);
+        if constexpr (HAS_V) __builtin_nontemporal_store(v, A.v + e);
+    }
+}
+
+template <int KPAD>
+static void launch_geomed_dist(bool pair0, dim3 grid, hipStream_t stream, const ProbeSlot& ps,
+                               const GeomedDistArgs& A) {
+    if (pair0)
+        hipExtLaunchKernelGGL((k_geomed_dist<KPAD, true>), grid, dim3(256), 0, stream, ps.start,
+                              ps.stop, 0, A);
+    else
+        hipExtLaunchKernelGGL((k_geomed_dist<KPAD, false>), grid, dim3(256), 0, stream, ps.start,
+                              ps.stop, 0, A);
+}
+
+static void launch_geomed_apply(int ok, dim3 grid, hipStream_t stream, const ProbeSlot& ps,
+                                const GeomedApplyArgs& A) {
+#define FLSIM_GEOMED_CASE(K)                                                                     \
+    case K:                                                                                      \
+        hipExtLaunchKernelGGL((k_geomed_apply<K>), grid, dim3(256), 0, stream, ps.start, ps.stop, \
+                              0, A);                                                             \
+        break;
+    switch (ok) {
+        FLSIM_GEOMED_CASE(OK_ADAM)
+        FLSIM_GEOMED_CASE(OK_ADAMD)
+        FLSIM_GEOMED_CASE(OK_SGDM)
+        FLSIM_GEOMED_CASE(OK_GOUT)
+        FLSIM_GEOMED_CASE(OK_ADAGRAD)
+        FLSIM_GEOMED_CASE(OK_YOGI)
+        default:
+            hipExtLaunchKernelGGL((k_geomed_apply<OK_SGD>), grid, dim3(256), 0, stream, ps.start,
+                                  ps.stop, 0, A);
+            break;
+    }
+#undef FLSIM_GEOMED_CASE
+}
+
+// flsim_geomed's hyper-parameters; before any pointer check, like check_optim
+static int check_geomed(const flsim_geomed* r) {
+    FLSIM_REQUIRE(r, "null geometric-median rule");
+    FLSIM_REQUIRE(r->k >= 1 && r->k <= RULE_MAX_ARR,
+                  "geometric median over k = %d entries (1 .. %d)", r->k, RULE_MAX_ARR);
+    FLSIM_REQUIRE(r->iters >= 0 && r->iters <= FLSIM_GEOMED_MAX_ITERS,
+                  "Invalid iters = %d: 0 <= iters <= %d", r->iters, FLSIM_GEOMED_MAX_ITERS);
+    FLSIM_REQUIRE(r->nu > 0.0 && r->nu < (double)__builtin_inff(),
+                  "Invalid nu = %g: it must be finite and > 0", r->nu);
+    FLSIM_REQUIRE(r->weighted == 0 || r->weighted == 1,
+                  "Invalid weighted = %d: 0 (uniform) or 1 (count)", r->weighted);
+    for (int j = 0; j < r->k; ++j)
+        FLSIM_REQUIRE(r->count[j] >= 1, "Invalid count %d of entry %d: it must be >= 1",
+                      r->count[j], j);
+    return 0;
+}
+
 }  // namespace flsim
 
 using namespace flsim;
@@ -2904,6 +3340,233 @@ int flsim_krum_eval_host(const flsim_krum* r, long P, double* dist, double* scor
         volatile float fm = (float)r->m;
         g_out[e] = acc / fm;
     }
+    return 0;
+}
+
+// ---- geometric median (RFA) over bucket means + the update (include/flsim.h) ---------------------
+long flsim_geomed_partials(long P, int k) {
+    if (k < 1 || k > RULE_MAX_ARR || P < 1 || P >= (1L << 31)) return 0;
+    return geomed_blocks(P, geomed_kpad(k)) * (k + 1);
+}
+
+long flsim_geomed_tile_elems(int k) {
+    if (k < 1 || k > RULE_MAX_ARR) return 0;
+    return geomed_tile_elems(geomed_kpad(k));
+}
+
+// iters + 1 pairs (k_geomed_dist -> s->partials; k_geomed_finish -> s->d2, s->obj, s->w,
+// s->state), then k_geomed_apply in the optimizer's kind (optim == NULL: OK_GOUT writing g_out
+// alone; clip: OK_GOUT writing clip->G and the per-block partials, then k_clip_finish and
+// k_clip_apply).
+int flsim_geomed_optim_step(const flsim_geomed* r, const flsim_geomed_scratch* s,
+                            const flsim_clip* clip, float* g_out, float* p, float* m, float* v,
+                            long P, long step, const flsim_optim* optim, hipStream_t stream) {
+    RC(check_geomed(r));
+    if (optim) RC(check_optim(optim));
+    RC(check_clip(clip));
+    FLSIM_REQUIRE(optim || (g_out && !clip), "null optimizer (only a step that writes g_out alone, "
+                  "unclipped, takes none)");
+    OptLaunch ol{};
+    ol.ok = OK_GOUT;
+    int nstate = 0;
+    if (optim) {
+        nstate = optim_n_state(optim);
+        RC(make_opt_launch(optim, 1.0, step, &ol));
+        FLSIM_REQUIRE(p && (m || nstate < 1) && (v || nstate < 2), "null pointer");
+    } else {
+        p = nullptr;
+    }
+    if (nstate < 2) v = nullptr;
+    if (nstate < 1) m = nullptr;
+    FLSIM_REQUIRE(P > 0 && P < (1L << 31), "P = %ld out of range", P);
+    FLSIM_REQUIRE((((uintptr_t)p | (uintptr_t)m | (uintptr_t)v | (uintptr_t)g_out) & 15) == 0,
+                  "p/m/v/g_out must be 16-byte aligned");
+    const float* const outs[] = {p, m, v, g_out};
+    for (int a = 0; a < 4; ++a)
+        for (int b = a + 1; b < 4; ++b)
+            FLSIM_REQUIRE(!overlaps(outs[a], outs[b], P), "p/m/v/g_out overlap each other");
+    FLSIM_REQUIRE(s && s->partials && s->w && s->d2 && s->obj && s->state,
+                  "null geometric-median scratch");
+    FLSIM_REQUIRE((((uintptr_t)s->partials | (uintptr_t)s->w | (uintptr_t)s->d2 |
+                    (uintptr_t)s->obj | (uintptr_t)s->state) & 15) == 0,
+                  "geometric-median scratch must be 16-byte aligned");
+    const int k = r->k, iters = r->iters;
+    const int kpad = geomed_kpad(k);
+    const long nblocks = geomed_blocks(P, kpad);
+    const long n_dist = nblocks * (k + 1);
+    FLSIM_REQUIRE(s->n_partials >= n_dist,
+                  "geometric-median n_partials = %ld, this step writes %ld", s->n_partials, n_dist);
+    // (a buffer of no bytes -- d2 and obj at iters = 0 -- overlaps nothing)
+    const void* const sb[] = {s->partials, s->w, s->d2, s->obj, s->state};
+    const long sn[] = {8 * n_dist, 8L * (iters + 1) * k, 8L * iters * k, 8L * iters,
+                       4L * (k + GEOMED_ST_WORDS)};
+    for (int a = 0; a < 5; ++a) {
+        if (!sn[a]) continue;
+        for (int b = a + 1; b < 5; ++b)
+            FLSIM_REQUIRE(!sn[b] || !overlaps_bytes(sb[a], sn[a], sb[b], sn[b]),
+                          "geometric-median scratch buffers overlap each other");
+        for (const float* o : outs)
+            FLSIM_REQUIRE(!overlaps_bytes(sb[a], sn[a], o, 4 * P),
+                          "geometric-median scratch overlaps p/m/v/g_out");
+        FLSIM_REQUIRE(!clip || !overlaps_bytes(sb[a], sn[a], clip->G, 4 * P),
+                      "geometric-median scratch overlaps clip G");
+    }
+    long n_part = 0;
+    if (clip) {
+        FLSIM_REQUIRE(clip->G && clip->partials && clip->out, "null clip buffer");
+        FLSIM_REQUIRE((((uintptr_t)clip->G | (uintptr_t)clip->partials | (uintptr_t)clip->out) &
+                       15) == 0, "clip G/partials/out must be 16-byte aligned");
+        for (const float* o : outs)
+            FLSIM_REQUIRE(!overlaps(clip->G, o, P), "clip G overlaps p/m/v/g_out");
+    }
+    GeomedDistArgs D{};
+    GeomedFinArgs F{};
+    GeomedApplyArgs A{};
+    int distinct = 0;
+    double alpha[RULE_MAX_ARR];
+    for (int j = 0; j < k; ++j) {
+        const float* e = r->entries[j];
+        FLSIM_REQUIRE(((uintptr_t)e & 3) == 0, "entry %d must be 4-byte aligned", j);
+        for (const float* o : outs)
+            FLSIM_REQUIRE(!overlaps(e, o, P), "entry %d overlaps p/m/v/g_out", j);
+        FLSIM_REQUIRE(!clip || !overlaps(e, clip->G, P), "entry %d overlaps clip G", j);
+        for (int a = 0; a < 5; ++a)
+            FLSIM_REQUIRE(!sn[a] || !overlaps_bytes(e, 4 * P, sb[a], sn[a]),
+                          "entry %d overlaps the geometric-median scratch", j);
+        volatile float one = 1.f, c = (float)r->count[j];    // RN(1 / count) in fp32
+        D.ent[j] = A.ent[j] = e;
+        D.cnt[j] = A.cnt[j] = c;
+        D.rcnt[j] = A.rcnt[j] = one / c;
+        F.count[j] = r->count[j];
+        alpha[j] = geomed_alpha(r->weighted, r->count[j], 0);
+        bool seen = e == nullptr;
+        for (int q = 0; q < j && !seen; ++q) seen = r->entries[q] == e;
+        distinct += !seen;
+    }
+    geomed_w0(alpha, k, D.w0);
+    const long nblk = (P + 255) / 256;
+    if (clip) {
+        n_part = nblk;
+        FLSIM_REQUIRE(clip->n_partials >= n_part, "clip n_partials = %ld, this step writes %ld",
+                      clip->n_partials, n_part);
+    }
+    D.w = s->w;
+    D.state = s->state;
+    D.partials = s->partials;
+    D.P = P;
+    D.k = k;
+    D.ntiles = (int)geomed_tiles(P, kpad);
+    D.iters = iters;
+    F.partials = s->partials;
+    F.w = s->w;
+    F.d2 = s->d2;
+    F.obj = s->obj;
+    F.state = s->state;
+    F.nu = r->nu;
+    F.nblocks = (int)nblocks;
+    F.k = k;
+    F.iters = iters;
+    F.weighted = r->weighted;
+    for (int pair = 0; pair <= iters; ++pair) {
+        D.pair = F.pair = pair;
+        {
+            const ProbeSlot ps = probe_begin();
+            const dim3 grid((unsigned)nblocks);
+            switch (kpad) {
+                case 4: launch_geomed_dist<4>(pair == 0, grid, stream, ps, D); break;
+                case 8: launch_geomed_dist<8>(pair == 0, grid, stream, ps, D); break;
+                case 16: launch_geomed_dist<16>(pair == 0, grid, stream, ps, D); break;
+                case 32: launch_geomed_dist<32>(pair == 0, grid, stream, ps, D); break;
+                default: launch_geomed_dist<64>(pair == 0, grid, stream, ps, D); break;
+            }
+            FLSIM_LAUNCH_CHECK();
+            // algorithmic HBM bytes: each distinct entry read once
+            if (probe_end(ps, K_GEOMED_DIST, 4.0 * (double)P * distinct)) return 2;
+        }
+        const ProbeSlot ps = probe_begin();
+        hipExtLaunchKernelGGL(k_geomed_finish, dim3(1), dim3(GEOMED_FIN_THREADS), 0, stream,
+                              ps.start, ps.stop, 0, F);
+        FLSIM_LAUNCH_CHECK();
+        if (probe_end(ps, K_GEOMED_FIN, 8.0 * (double)nblocks * (k + (pair == 0)) + 8.0 * (3 * k + 1)))
+            return 2;
+    }
+    A.w = s->w + (long)iters * k;
+    A.g_out = g_out;
+    A.G = clip ? clip->G : nullptr;
+    A.partials = clip ? clip->partials : nullptr;
+    A.p = p;
+    A.m = m;
+    A.v = v;
+    A.P = P;
+    A.k = k;
+    A.ac = ol.ac;
+    A.oc = ol.oc;
+    const int ok_launch = clip ? (int)OK_GOUT : ol.ok;
+    // algorithmic HBM bytes: the distinct entries read; g_out / G written; p and the kind's state
+    // arrays read + written (not by a launch that only writes g)
+    const int nst_launch = ok_launch == OK_GOUT ? 0 : nstate;
+    const double bytes = 4.0 * (double)P * (distinct + (g_out ? 1 : 0) + (clip ? 1 : 0) +
+                                            (ok_launch == OK_GOUT ? 0 : 2 + 2 * nst_launch));
+    const ProbeSlot ps = probe_begin();
+    launch_geomed_apply(ok_launch, dim3((unsigned)nblk), stream, ps, A);
+    FLSIM_LAUNCH_CHECK();
+    if (probe_end(ps, K_GEOMED_APPLY, bytes)) return 2;
+    if (!clip) return 0;
+    return clip_finish_apply(clip, n_part, ol, p, m, v, P, stream);
+}
+
+// host (testing): the text for host pointers.  The bucket means by one fp32 division each; z as
+// _wsum forms it; every distance as the fp64 sum of ((double)x_j - z)^2 in element order (one fma
+// each, as the kernel's); then csrc/geomed.h's scalar code, and g = (float)z at w^(iters).
+int flsim_geomed_eval_host(const flsim_geomed* r, long P, double* w, double* d2, double* obj,
+                           float* g_out) {
+    RC(check_geomed(r));
+    const int k = r->k, iters = r->iters;
+    FLSIM_REQUIRE(w && (iters == 0 || (d2 && obj)), "null pointer");
+    FLSIM_REQUIRE(P > 0, "P = %ld out of range", P);
+    auto mean = [&](int j, long e) -> float {
+        volatile float x = r->entries[j] ? r->entries[j][e] : 0.f;
+        volatile float c = (float)r->count[j];
+        return x / c;
+    };
+    auto wsum = [&](const double* wt, long e) -> double {
+        double z = 0.0;
+        bool have = false;
+        for (int j = 0; j < k; ++j) {
+            if (!geomed_nonzero(wt[j])) continue;
+            volatile double t = (double)mean(j, e) * wt[j];
+            z = have ? z + t : (double)t;
+            have = true;
+        }
+        return z;
+    };
+    int32_t dead[RULE_MAX_ARR];
+    double a[RULE_MAX_ARR], term[RULE_MAX_ARR], sums[2];
+    for (int j = 0; j < k; ++j) {
+        dead[j] = 0;
+        for (long e = 0; e < P && !dead[j]; ++e) {
+            const float y = mean(j, e);
+            dead[j] = !(__builtin_fabsf(y) < __builtin_inff());
+        }
+        a[j] = geomed_alpha(r->weighted, r->count[j], dead[j]);
+    }
+    geomed_w0(a, k, w);
+    for (int it = 0; it < iters; ++it) {
+        double* d = d2 + (long)it * k;
+        for (int j = 0; j < k; ++j) d[j] = 0.0;
+        for (long e = 0; e < P; ++e) {
+            const double z = wsum(w + (long)it * k, e);
+            for (int j = 0; j < k; ++j) {
+                if (dead[j]) continue;
+                const double df = (double)mean(j, e) - z;
+                d[j] = __builtin_fma(df, df, d[j]);
+            }
+        }
+        geomed_iterate(d, a, dead, k, r->nu, term, sums, w + (long)(it + 1) * k, 0, 1, [] {});
+        obj[it] = sums[0];
+    }
+    if (!g_out) return 0;
+    for (long e = 0; e < P; ++e) g_out[e] = (float)wsum(w + (long)iters * k, e);
     return 0;
 }
 

@@ -53,6 +53,8 @@ EXPORTS = [
     "flsim_robust_optim_step", "flsim_robust_eval_host",
     "flsim_krum_partials", "flsim_krum_tile_elems", "flsim_krum_optim_step",
     "flsim_krum_eval_host",
+    "flsim_geomed_partials", "flsim_geomed_tile_elems", "flsim_geomed_optim_step",
+    "flsim_geomed_eval_host",
 ]
 COMM_ID_BYTES = 128      # FLSIM_COMM_ID_BYTES
 
@@ -111,6 +113,20 @@ class FlsimKrumScratch(ctypes.Structure):
     """flsim_krum_scratch (include/flsim.h): the caller's scratch and outputs of a Krum step."""
     _fields_ = [("partials", ctypes.c_void_p), ("n_partials", ctypes.c_long),
                 ("dist", ctypes.c_void_p), ("score", ctypes.c_void_p), ("sel", ctypes.c_void_p)]
+
+
+class FlsimGeomed(ctypes.Structure):
+    """flsim_geomed (include/flsim.h): the geometric median (RFA) over k bucket / class sums."""
+    _fields_ = [("iters", ctypes.c_int32), ("weighted", ctypes.c_int32), ("k", ctypes.c_int32),
+                ("nu", ctypes.c_double),
+                ("entries", ctypes.c_void_p * MAX_ARRAYS), ("count", ctypes.c_int32 * MAX_ARRAYS)]
+
+
+class FlsimGeomedScratch(ctypes.Structure):
+    """flsim_geomed_scratch (include/flsim.h): the caller's scratch and outputs of a step."""
+    _fields_ = [("partials", ctypes.c_void_p), ("n_partials", ctypes.c_long),
+                ("w", ctypes.c_void_p), ("d2", ctypes.c_void_p), ("obj", ctypes.c_void_p),
+                ("state", ctypes.c_void_p)]
 
 
 # FLSIM_OPT_ADAM / _ADAMW / _SGD / _ADAGRAD / _YOGI
@@ -246,6 +262,13 @@ def lib():
     L.flsim_krum_optim_step.argtypes = [vp, vp, vp, vp, vp, vp, vp, ctypes.c_long, ctypes.c_long,
                                         vp, vp]
     L.flsim_krum_eval_host.argtypes = [vp, ctypes.c_long, vp, vp, vp, vp]
+    L.flsim_geomed_partials.restype = ctypes.c_long
+    L.flsim_geomed_partials.argtypes = [ctypes.c_long, ctypes.c_int]
+    L.flsim_geomed_tile_elems.restype = ctypes.c_long
+    L.flsim_geomed_tile_elems.argtypes = [ctypes.c_int]
+    L.flsim_geomed_optim_step.argtypes = [vp, vp, vp, vp, vp, vp, vp, ctypes.c_long, ctypes.c_long,
+                                          vp, vp]
+    L.flsim_geomed_eval_host.argtypes = [vp, ctypes.c_long, vp, vp, vp, vp]
     L.flsim_cascade_program.argtypes = [ctypes.c_int, vp, vp, ctypes.c_int, vp, ctypes.c_int, vp]
     L.flsim_cascade_eval_host.argtypes = [vp, vp, vp, vp, ctypes.c_int, vp, ctypes.c_long, vp]
     L.flsim_probe_enable.argtypes = [ctypes.c_int]

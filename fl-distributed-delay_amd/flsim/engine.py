@@ -20,8 +20,8 @@ import torch
 
 import math
 
-from ._lib import (MAX_ARRAYS, OPT_KINDS, ROBUST_KINDS, FlsimClip, FlsimKrum, FlsimKrumScratch,
-                   FlsimOptim, FlsimRobust,
+from ._lib import (MAX_ARRAYS, OPT_KINDS, ROBUST_KINDS, FlsimClip, FlsimGeomed,
+                   FlsimGeomedScratch, FlsimKrum, FlsimKrumScratch, FlsimOptim, FlsimRobust,
                    FlsimRule, FlsimRuleComp, FlsimRuleWeights, WorkerRec, check, lib, ptr,
                    stream_ptr)
 
@@ -471,6 +471,13 @@ class NetEngine:
         this network's P parameters; clip (a Clip) and g_out as krum_step."""
         krum_step(krum, theta, m, v, step, self.P, lr, betas, eps, optim=optim, clip=clip,
                   g_out=g_out)
+
+    def geomed_step(self, geomed, theta, m, v, step, lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
+                    optim=None, clip=None, g_out=None):
+        """The geometric median (a GeoMed over bucket sums) + Adam (or the update rule `optim`)
+        over this network's P parameters; clip (a Clip) and g_out as geomed_step."""
+        geomed_step(geomed, theta, m, v, step, self.P, lr, betas, eps, optim=optim, clip=clip,
+                    g_out=g_out)
 
 
 class PN1Engine(NetEngine):
@@ -1010,6 +1017,90 @@ def krum_step(krum, theta, m, v, step, P=None, lr=1e-3, betas=(0.9, 0.999), eps=
     s = krum.c_scratch(dev, int(P))
     c = ctypes.byref(clip.c_struct(dev, int(P))) if clip is not None else None
     check(lib().flsim_krum_optim_step(
+        ctypes.byref(r), ctypes.byref(s), c, ptr(g_out), ptr(theta), ptr(m), ptr(v), int(P),
+        int(step), o, stream_ptr()))
+
+
+class GeoMed:
+    """The geometric median over bucket / class sums by smoothed Weiszfeld iterations
+    (flsim_geomed, include/flsim.h; "RFA"): of the k = len(entries) values entries[j] /
+    counts[j], `iters` iterations from their alpha-weighted mean, alpha = 1 or (weighted) the
+    counts.  entries, counts as for Robust.  The object owns its scratch per (device, P, k,
+    iters), allocated at the first step; after a step w ([iters + 1, k] fp64), d2 ([iters, k]
+    fp64), obj ([iters] fp64) and dead ([k] int32) are device tensors, read with no
+    synchronisation beyond the stream's order; the next step overwrites them.
+    flsim/robust.py is the rule's text."""
+    _scratch = {}       # (device, P, k, iters) -> buffers, shared by the objects of a run
+
+    def __init__(self, iters, nu, weighted, entries, counts):
+        entries, counts = list(entries), [int(c) for c in counts]
+        if len(entries) != len(counts):
+            raise ValueError(f"{len(counts)} counts for {len(entries)} entries")
+        if len(entries) > MAX_ARRAYS:
+            raise ValueError(f"geometric median over k = {len(entries)} entries "
+                             f"(1 .. {MAX_ARRAYS})")
+        self.iters, self.nu, self.weighted = int(iters), float(nu), bool(weighted)
+        self.entries, self.counts = entries, counts     # (the rule keeps the tensors alive)
+        self.w = self.d2 = self.obj = self.dead = None
+
+    @property
+    def k(self):
+        return len(self.entries)
+
+    def c_struct(self):
+        r = FlsimGeomed()
+        r.iters, r.weighted, r.k = self.iters, int(self.weighted), len(self.entries)
+        r.nu = self.nu
+        for j, (e, c) in enumerate(zip(self.entries, self.counts)):
+            r.entries[j] = e.data_ptr() if e is not None else None
+            r.count[j] = c if -2 ** 31 <= c < 2 ** 31 else 0
+        return r
+
+    def c_scratch(self, device, P):
+        """flsim_geomed_scratch over this device's scratch for a step over P elements."""
+        k = len(self.entries)
+        it = max(min(self.iters, 32), 0)
+        key = (str(device), int(P), k, it)
+        if key not in GeoMed._scratch:
+            n = max(int(lib().flsim_geomed_partials(int(P), k)), 2)
+            GeoMed._scratch[key] = (torch.empty(n, dtype=torch.float64, device=device),
+                                    torch.empty((it + 1) * k + 2, dtype=torch.float64, device=device),
+                                    torch.empty(it * k + 2, dtype=torch.float64, device=device),
+                                    torch.empty(it + 2, dtype=torch.float64, device=device),
+                                    torch.empty(k + 4 + 4, dtype=torch.int32, device=device))
+        partials, w, d2, obj, state = GeoMed._scratch[key]
+        s = FlsimGeomedScratch()
+        s.partials = partials.data_ptr()
+        s.n_partials = int(partials.numel())
+        s.w = w.data_ptr()
+        s.d2 = d2.data_ptr()
+        s.obj = obj.data_ptr()
+        s.state = state.data_ptr()
+        self.partials = partials
+        self.w = w[:(it + 1) * k].view(it + 1, k)
+        self.d2 = d2[:it * k].view(it, k)
+        self.obj = obj[:it]
+        self.dead = state[:k]
+        return s
+
+
+def geomed_step(geomed, theta, m, v, step, P=None, lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
+                optim=None, clip=None, g_out=None):
+    """The geometric median (RFA) + Adam(lr, betas, eps), or the update rule `optim`, in
+    2 * (iters + 1) + 1 launches (flsim_geomed_optim_step); m / v, clip, g_out and optim=False
+    as robust_step."""
+    if optim is False:
+        o = None
+    else:
+        o = ctypes.byref((as_optim(optim) if optim is not None else
+                          Optim(lr=lr, betas=tuple(betas), eps=eps)).c_struct())
+    if P is None:
+        P = int((theta if theta is not None else g_out).numel())
+    r = geomed.c_struct()
+    dev = next((t.device for t in (theta, g_out, *geomed.entries) if t is not None), None)
+    s = geomed.c_scratch(dev, int(P))
+    c = ctypes.byref(clip.c_struct(dev, int(P))) if clip is not None else None
+    check(lib().flsim_geomed_optim_step(
         ctypes.byref(r), ctypes.byref(s), c, ptr(g_out), ptr(theta), ptr(m), ptr(v), int(P),
         int(step), o, stream_ptr()))
 

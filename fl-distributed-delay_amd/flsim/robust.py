@@ -153,16 +153,155 @@ def krum_flat(entries, counts, f, m=1):
     return _krum(cols, f, m), d, score, sel
 
 
+# ---- the geometric median by smoothed Weiszfeld iterations ("RFA", Pillutla, Kakade and Harchaoui
+# 2022): breakdown point 1/2, no Byzantine count from the user; the entries are re-weighted
+# continuously by 1 / distance to the iterate.  The yardstick of flsim_geomed_optim_step
+# (include/flsim.h) and of its host twin, stage by stage at the device's own inputs: d2[r] within
+# 2 (P + 2) 2^-53 relative of the distances at w[r]; w[r + 1], obj[r] (geomed_scalar on d2[r]) and
+# g (_wsum at w[iters]) bit for bit.
+GEOMED_KIND = "geomed"
+GEOMED_WEIGHTS = ("uniform", "count")
+GEOMED_MAX_ITERS = 32
+
+
+def _seqsum(v):                              # sequential fp64 adds, index order
+    acc = v[0].clone()
+    for t in v[1:]:
+        acc = acc + t
+    return acc
+
+
+def _wsum(x, w):
+    """z = sum_j w[j] * x[j]: fp64, index order, one multiply and one add per term (two roundings,
+    never an fma); terms with w[j] == 0 are skipped (not read); the first term kept initialises
+    the sum."""
+    z = None
+    for j in range(x.shape[0]):
+        if w[j] == 0:
+            continue
+        t = x[j] * w[j]
+        z = t if z is None else z + t
+    return torch.zeros_like(x[0]) if z is None else z
+
+
+def _sqrt_rn(v):
+    """The correctly rounded fp64 square root of a small 1-d tensor, element by element
+    (math.sqrt: torch's vectorised CPU sqrt is 1 ulp off for some inputs on some machines)."""
+    import math
+    return torch.tensor([math.sqrt(t) for t in v.tolist()], dtype=torch.float64, device=v.device)
+
+
+def geomed_scalar(d2_r, a, alive, nu):
+    """One iteration's scalar code from the squared distances (dead: +inf) -> (obj, next w)."""
+    d = _sqrt_rn(d2_r)
+    live = [j for j in range(len(a)) if alive[j]]
+    obj = _seqsum((a * d)[live]) if live else torch.tensor(float("nan"), dtype=torch.float64)
+    beta = a / torch.maximum(d, torch.tensor(nu, dtype=torch.float64))  # dead: 0 / inf = 0
+    return obj, beta / _seqsum(beta)
+
+
+def geomed_dist2(x, w_r, alive):
+    """The squared distances of the entries x [k, numel] fp64 to z = _wsum(x, w_r); dead: +inf."""
+    z = _wsum(x, w_r)
+    d2_r = ((x - z) ** 2).sum(1)
+    d2_r[~alive] = float("inf")
+    return d2_r
+
+
+def geomed_steps(cols, alpha, iters, nu):    # cols [k, numel] fp32 (bucket means), alpha [k] fp64 > 0
+    x = cols.double()
+    alive = torch.isfinite(x).all(1)         # an entry with any NaN / inf element is dead
+    a = torch.where(alive, alpha, torch.zeros_like(alpha))
+    # (not alive.any(): a / 0 below is NaN throughout, and so is g)
+    w = [a / _seqsum(a)]                     # w^(0): z_0 is the alpha-weighted mean of the live entries
+    d2, obj = [], []
+    for r in range(iters):
+        d2_r = geomed_dist2(x, w[r], alive)
+        o, w_next = geomed_scalar(d2_r, a, alive, nu)
+        obj.append(o)                        # sum_j alpha_j ||x_j - z_r||
+        w.append(w_next)                     # the smoothed Weiszfeld weights, normalised
+        d2.append(d2_r)
+    g = _wsum(x, w[iters]).float()           # one fp64 -> fp32 rounding
+    return g, w, d2, obj
+
+
+def check_geomed(iters, nu, weights, k):
+    """The cases the library refuses (ValueError), and rule()'s IndexError on an empty list.
+    Returns (iters, nu, weights) with weights None -> "uniform"."""
+    import math
+    if k == 0:
+        raise IndexError("empty weight_ups (reference: IndexError in rule, main.py:25)")
+    iters, nu = int(iters), float(nu)
+    weights = "uniform" if weights is None else weights
+    if iters < 0 or iters > GEOMED_MAX_ITERS:
+        raise ValueError(f"Invalid iters = {iters}: 0 <= iters <= {GEOMED_MAX_ITERS}")
+    if not (math.isfinite(nu) and nu > 0):
+        raise ValueError(f"Invalid nu = {nu}: it must be finite and > 0")
+    if weights not in GEOMED_WEIGHTS:
+        raise ValueError(f"Invalid weights {weights!r} (supported: {GEOMED_WEIGHTS})")
+    return iters, nu, weights
+
+
+def geomed_rule(ups_list, iters=3, nu=1e-6, weights=None):
+    """rule() with the geometric median of the updates (`iters` smoothed Weiszfeld iterations from
+    their mean), over all tensors flattened together.  weights: None (uniform) or a sequence of
+    positive per-update weights (RFA's sample counts)."""
+    alpha = None
+    if weights is not None and not isinstance(weights, str):
+        alpha = torch.as_tensor(list(weights), dtype=torch.float64)
+        if alpha.numel() != len(ups_list) or not bool((alpha > 0).all()):
+            raise ValueError("weights: one positive weight per update")
+        weights = "count"
+    iters, nu, _ = check_geomed(iters, nu, weights, len(ups_list))
+    if alpha is None:
+        alpha = torch.ones(len(ups_list), dtype=torch.float64)
+    cols = torch.stack([torch.cat([u.reshape(-1) for u in ups]) for ups in ups_list])
+    g = geomed_steps(cols, alpha, iters, nu)[0]
+    out, off = [], 0
+    for u in ups_list[0]:
+        out.append(g[off:off + u.numel()].view(u.shape))
+        off += u.numel()
+    return out
+
+
+def geomed_alpha(counts, weighted):
+    return torch.tensor([float(c) if weighted else 1.0 for c in counts], dtype=torch.float64)
+
+
+def geomed_flat(entries, counts, iters=3, nu=1e-6, weighted=False):
+    """The text over flat bucket SUMS (None = an all-zero entry) with their counts: what
+    flsim_geomed_optim_step computes.  Returns (g, w, d2, obj): w iters + 1 tensors [k], d2 iters
+    tensors [k], obj iters scalars."""
+    iters, nu, _ = check_geomed(iters, nu, "count" if weighted else "uniform", len(entries))
+    ref = next(e for e in entries if e is not None)
+    sums = [torch.zeros_like(ref) if e is None else e for e in entries]
+    cols = torch.stack(bucket_means(sums, counts))
+    return geomed_steps(cols, geomed_alpha(counts, weighted), iters, nu)
+
+
 def parse_rule(spec):
     """FLSimulation's robust_rule argument -> (kind, trim): None, "median", "trimmed_mean" (trim
     0), or ("trimmed_mean", trim); or ("krum", f) -> ("krum", f, 1) and ("multi_krum", f, m) as
-    it stands (f has no default: the bare strings are refused)."""
+    it stands (f has no default: the bare strings are refused); or "geomed", ("geomed", iters),
+    ("geomed", iters, nu), ("geomed", iters, nu, "uniform" | "count") -> ("geomed", iters, nu,
+    weights), defaults 3, 1e-6, "uniform"."""
     if spec is None or spec == "none":
         return None
     if isinstance(spec, str):
         spec = (spec,)
     spec = tuple(spec)
     kind = spec[0]
+    if kind == GEOMED_KIND:
+        if len(spec) > 4:
+            raise ValueError(f"robust_rule {spec!r} (supported: 'geomed', ('geomed', iters), "
+                             "('geomed', iters, nu), ('geomed', iters, nu, 'uniform' | 'count'))")
+        try:
+            iters, nu, weights = check_geomed(spec[1] if len(spec) > 1 else 3,
+                                              spec[2] if len(spec) > 2 else 1e-6,
+                                              spec[3] if len(spec) > 3 else None, 1)
+        except (TypeError, ValueError) as e:
+            raise ValueError(f"robust_rule {spec!r}: {e}") from None
+        return kind, iters, nu, weights
     if kind in KRUM_KINDS:
         if len(spec) != (2 if kind == "krum" else 3):
             raise ValueError(f"robust_rule {spec!r} (supported: ('krum', f), ('multi_krum', f, m))")

@@ -44,7 +44,7 @@ import torch
 from .data import DevicePool, make_test_pool
 from .engine import (PN1_SIZES, Clip, Optim, ProgramStager, Rule, engine_class, optim_defaults,
                      padded, split_views, staleness_weight)
-from .robust import KRUM_KINDS, check_krum, parse_rule
+from .robust import GEOMED_KIND, KRUM_KINDS, check_krum, parse_rule
 from .schedule import Schedule, reference_delays
 
 SEMANTICS = ("reference", "torch1", "independent")
@@ -92,13 +92,15 @@ class FLSimulation:
         if semantics not in SEMANTICS:
             raise NotImplementedError(f"semantics {semantics!r} (supported: {SEMANTICS})")
         # a robust rule in place of the mean (None: off; today's code paths exactly): (kind, trim),
-        # or ("krum" | "multi_krum", f, m)
+        # ("krum" | "multi_krum", f, m), or ("geomed", iters, nu, weights)
         self.robust = parse_rule(robust_rule)
         self.buckets = int(buckets)
         self.keep_entries = bool(keep_entries)
         self.last_entries = None
         self.last_selected = None       # Krum / Multi-Krum with keep_entries: the entries chosen
         self.sel_log = []               # per epoch: list of ints (read back) or a device tensor
+        self.last_geomed = None         # the geometric median with keep_entries: the epoch's GeoMed
+        self.geomed_entries = []        # per epoch: (obj, final w), device tensors or read back
         if self.robust is not None:
             if self.buckets < 1:
                 raise ValueError(f"buckets = {self.buckets}: it must be >= 1")
@@ -739,6 +741,18 @@ class FLSimulation:
             self.sel_log.append(krum.sel.detach().clone())      # (a device tensor: no sync)
             if self.keep_entries:           # (reads the device selection back: synchronises)
                 self.last_selected = [int(j) for j in krum.sel.tolist()]
+        elif self.robust[0] == GEOMED_KIND:
+            # the geometric median (RFA): alpha = 1, or the entries' counts
+            from .engine import GeoMed
+            _, iters, nu, weights = self.robust
+            self.step += 1
+            gm = GeoMed(iters, nu, weights == "count", [e[:self.P] for e in entries], counts)
+            eng.geomed_step(gm, self.theta, self.m, self.v, self.step, optim=self.optim,
+                            clip=self.clip)
+            # (device tensors, cloned: no sync; the scratch is the next epoch's too)
+            self.geomed_entries.append((gm.obj.detach().clone(), gm.w[-1].detach().clone()))
+            if self.keep_entries:
+                self.last_geomed = gm
         else:
             kind, trim = self.robust
             self.step += 1
@@ -774,6 +788,16 @@ class FLSimulation:
         self.sel_log = [x if isinstance(x, list) else [int(j) for j in x.tolist()]
                         for x in self.sel_log]
         return [list(x) for x in self.sel_log]
+
+    def geomed_log(self):
+        """Per epoch of a geometric-median run (else []) the pair (obj, w): the objective
+        sum_j alpha_j ||x_j - z_r|| at every iterate z_r, r < iters, as a list of floats, and the
+        final weights w^(iters) over the epoch's entries (the fresh buckets first, then the
+        popped slots).  Synchronises on the first call after new epochs."""
+        self.geomed_entries = [(o if isinstance(o, list) else [float(x) for x in o.tolist()],
+                                w if isinstance(w, list) else [float(x) for x in w.tolist()])
+                               for o, w in self.geomed_entries]
+        return [(list(o), list(w)) for o, w in self.geomed_entries]
 
     def losses(self):
         out = []

@@ -15,6 +15,9 @@ coordinate-wise median or trimmed mean over B bucket means of the fast workers a
 delay-class entries (needs --semantics independent).  --robust_rule {krum,multi_krum} with
 --byz_f F (and --krum_m M) picks the entry closest to its k - F - 2 nearest neighbours, or averages
 the M such entries (Blanchard et al. 2017), and logs the chosen entries as 'Krum Selected'.
+--robust_rule geomed with --geomed_iters R, --geomed_nu NU and --geomed_weights {uniform,count}
+takes the geometric median of the entries by R smoothed Weiszfeld iterations (RFA, Pillutla et
+al. 2022; no Byzantine count needed) and logs the objective at every iterate as 'GeoMed Objective'.
 The training loop (main.py:126-188) runs as flsim.sim.FLSimulation: host schedule,
 worker-batched HIP forward/backward, fused rule()+Adam; with
 `torchrun --nproc-per-node N` the computing workers are sharded over N GPUs with one RCCL
@@ -88,10 +91,18 @@ def parse(argv=None):
                    help='clip the aggregated gradient to this global 2-norm before the update, '
                         'as torch.nn.utils.clip_grad_norm_ (default: off; inf only logs the norm)')
     p.add_argument('--robust_rule', default='none',
-                   choices=['none', 'median', 'trimmed_mean', 'krum', 'multi_krum'],
-                   help='aggregate with the coordinate-wise median or trimmed mean, or with Krum / '
-                        'Multi-Krum, over bucket means instead of the mean (needs --semantics '
-                        'independent; default: none)')
+                   choices=['none', 'median', 'trimmed_mean', 'krum', 'multi_krum', 'geomed'],
+                   help='aggregate with the coordinate-wise median or trimmed mean, with Krum / '
+                        'Multi-Krum, or with the geometric median (RFA), over bucket means instead '
+                        'of the mean (needs --semantics independent; default: none)')
+    p.add_argument('--geomed_iters', type=int, default=3, metavar='R',
+                   help='--robust_rule geomed: smoothed Weiszfeld iterations, 0 .. 32 (default 3)')
+    p.add_argument('--geomed_nu', type=float, default=1e-6, metavar='NU',
+                   help='--robust_rule geomed: the floor of a distance in the weights 1 / '
+                        'max(distance, NU), finite and > 0 (default 1e-6)')
+    p.add_argument('--geomed_weights', default='uniform', choices=['uniform', 'count'],
+                   help="--robust_rule geomed: weigh every entry alike, or by its workers' count "
+                        '(default uniform)')
     p.add_argument('--byz_f', type=int, default=None, metavar='F',
                    help="--robust_rule krum / multi_krum: the Byzantine entries tolerated, the "
                         "epoch's entry count >= 2F + 3 (required: no default)")
@@ -144,6 +155,8 @@ def robust_spec(args):
             raise SystemExit(f"--robust_rule {args.robust_rule} needs --byz_f F")
         return ('krum', args.byz_f) if args.robust_rule == 'krum' else \
             ('multi_krum', args.byz_f, args.krum_m)
+    if args.robust_rule == 'geomed':
+        return ('geomed', args.geomed_iters, args.geomed_nu, args.geomed_weights)
     return 'median' if args.robust_rule == 'median' else ('trimmed_mean', args.trim)
 
 
@@ -207,6 +220,7 @@ def main(argv=None):
             log.flush()
 
     t = len(sim.trace) - 1
+    first = len(sim.trace)
     for t in range(len(sim.trace), args.n_epochs):
         loss = sim.epoch()
         emit("Avg. Loss", loss, t)                                     # main.py:185
@@ -228,6 +242,9 @@ def main(argv=None):
         if args.checkpoint and args.checkpoint_every and (t + 1) % args.checkpoint_every == 0 \
                 and rank == 0:
             sim.save_checkpoint(args.checkpoint)
+    # (read back once, here: the epochs themselves never wait for the device)
+    for i, (obj, _) in enumerate(sim.geomed_log()):
+        emit("GeoMed Objective", obj, first + i)
     acc, per = sim.evaluate()                                           # main.py:205-210
     emit("Avg. Test Accuracy", acc, t)
     emit("Class 9 Test Accuracy", per[-1], t)

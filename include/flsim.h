@@ -704,6 +704,89 @@ int flsim_krum_optim_step(const flsim_krum* r, const flsim_krum_scratch* s, cons
 int flsim_krum_eval_host(const flsim_krum* r, long P, double* dist, double* score, int32_t* sel,
                          float* g_out);
 
+/* ---------------------------------------------------------------------------------------------
+ * Geometric median over bucket means by smoothed Weiszfeld iterations ("RFA", Pillutla, Kakade and
+ * Harchaoui 2022), fused with the update.  Breakdown point 1/2, no Byzantine count from the user;
+ * where Krum selects, it re-weights the entries continuously by 1 / distance to the iterate.  The
+ * text (flsim/robust.py, plain torch):
+ *
+ *   def _seqsum(v):                    # sequential fp64 adds, index order
+ *   def _wsum(x, w):                   # z = sum_j w[j] * x[j]: fp64, index order, one multiply and one add
+ *                                      # per term (two roundings, never an fma); terms with w[j] == 0 are
+ *                                      # skipped (not read); the first term kept initialises the sum
+ *   def geomed_steps(cols, alpha, iters, nu):     # cols [k, numel] fp32 (bucket means), alpha [k] fp64 > 0
+ *       x = cols.double()
+ *       alive = torch.isfinite(x).all(1)          # an entry with any NaN / inf element is dead
+ *       a = torch.where(alive, alpha, 0.0)
+ *       if not alive.any(): return all-NaN g, ...
+ *       w = [a / _seqsum(a)]                      # w^(0): z_0 is the alpha-weighted mean of the live entries
+ *       d2, obj = [], []
+ *       for r in range(iters):
+ *           z = _wsum(x, w[r])
+ *           d2_r = ((x - z) ** 2).sum(1); d2_r[~alive] = inf
+ *           d = d2_r.sqrt()
+ *           obj.append(_seqsum(a * d over the live entries))      # sum_j alpha_j ||x_j - z_r||
+ *           beta = a / torch.maximum(d, nu)       # smoothed Weiszfeld weight; dead: 0
+ *           w.append(beta / _seqsum(beta))
+ *           d2.append(d2_r)
+ *       g = _wsum(x, w[iters]).float()            # one fp64 -> fp32 rounding
+ *       return g, w, d2, obj
+ *
+ * alpha_j = 1 (weighted = 0) or count[j] (weighted = 1: RFA's sample-count weights).  No early
+ * stopping: that would need a host synchronisation.  Per element x_j = entries[j][e] /
+ * (float)count[j] as for flsim_robust; a NULL entry is all zero.
+ * iters + 1 pairs of (distance launch, one-block finish launch), then one apply launch, all on
+ * `stream`, no host synchronisation, no atomics: the grid and the element-to-block map depend on
+ * (P, k) alone, so the same shape gives the same bits on every run.  A distance launch reads the
+ * live entries once as coalesced rows, forms z[e] exactly as _wsum does (zero-weight entries are
+ * not loaded) and adds ((double)x_j - z)^2 into k fp64 sums a thread, reduced once per block into
+ * s->partials.  Pair 0 takes w^(0) of "every entry alive" from the host and also notes which
+ * entries hold a NaN or an inf.  A finish launch adds the partials in a fixed order and writes
+ * d2, obj and the next w with the scalar fp64 code of the text (correctly rounded sqrt, max,
+ * divide, sequential sums).  A dead entry makes pair 0's z a NaN: its finish then marks the dead
+ * entries in s->state, rewrites w^(0) from the live ones and sets a "redo" word, and every later
+ * pair acts as iteration (its index - 1); a pair whose iteration number equals iters returns at
+ * once (with no dead entry: the last pair).  Every entry dead: g is all NaN.  The apply launch forms
+ * z with w^(iters), g = (float)z, and runs the update of `optim` (every kind).
+ *   d2[r]: within 2 (P + 2) 2^-53 relative of the text's distances at the device's own w[r]
+ *   (z is then bit-identical; the summation order differs); w[r + 1] and obj[r] equal, bit for bit,
+ *   the text's scalar code applied to d2[r]; g equals _wsum(x, w[iters]).float() bit for bit.
+ * g_out, optim == NULL and clip as for flsim_krum_optim_step (clip: the apply launch stores g to
+ * clip->G with one fp64 sum of squares per 256 elements; the finish and apply launches of the
+ * clipped entry point follow unchanged).  The library never allocates: the caller provides the
+ * scratch, and nothing depends on what it held before.
+ * Checked before any pointer, status 1: k outside [1, FLSIM_MAX_ARRAYS]; iters outside
+ * [0, FLSIM_GEOMED_MAX_ITERS]; nu NaN, inf or <= 0; weighted not 0 or 1; a count < 1; what
+ * flsim_optim and flsim_clip are refused for.  Then: what flsim_krum_optim_step refuses about
+ * p / m / v / g_out / P / clip and the entries; a NULL or misaligned (16 bytes) scratch pointer;
+ * n_partials too small; an entry overlapping the scratch.
+ * ------------------------------------------------------------------------------------------- */
+#define FLSIM_GEOMED_MAX_ITERS 32
+typedef struct flsim_geomed {
+    int32_t iters, weighted, k;               /* 0..32; 0: alpha = 1, 1: alpha = count; 1..FLSIM_MAX_ARRAYS */
+    double nu;                                /* finite, > 0 */
+    const float* entries[FLSIM_MAX_ARRAYS];   /* bucket / class SUMS; NULL = all zero */
+    int32_t count[FLSIM_MAX_ARRAYS];          /* >= 1: x_j[e] = entries[j][e] / (float)count[j] */
+} flsim_geomed;
+typedef struct flsim_geomed_scratch {         /* caller-provided, 16-byte aligned, never pre-initialised */
+    double* partials; long n_partials;        /* >= flsim_geomed_partials(P, k) */
+    double* w;                                /* [(iters + 1) * k] out: w^(0) .. w^(iters) */
+    double* d2;                               /* [iters * k]       out: squared distances; +inf for a dead entry */
+    double* obj;                              /* [iters]           out */
+    int32_t* state;                           /* [k + 4] out: dead flags, then the control words the launches share */
+} flsim_geomed_scratch;
+/* the doubles a distance launch writes for P elements and k entries (0: k or P out of range) */
+long flsim_geomed_partials(long P, int k);
+/* (tests) the distance launch's tile: the elements of every entry a block takes at a time */
+long flsim_geomed_tile_elems(int k);
+int flsim_geomed_optim_step(const flsim_geomed* r, const flsim_geomed_scratch* s, const flsim_clip* clip,
+                            float* g_out, float* p, float* m, float* v, long P, long step,
+                            const flsim_optim* optim, flsim_stream_t stream);
+/* host (testing): w [(iters + 1) * k], d2 [iters * k], obj [iters] and g (g_out nullable) of the
+ * text for host pointers: the distances summed in element order, then the scalar code the finish
+ * kernel runs; refuses what the entry point refuses about r */
+int flsim_geomed_eval_host(const flsim_geomed* r, long P, double* w, double* d2, double* obj, float* g_out);
+
 #ifdef __cplusplus
 }
 #endif
