@@ -19,7 +19,8 @@ static const char* KNAME[K_COUNT] = {
     "aggregate_adam_seq", "slab_step", "slab_step_seq", "slab_sum",
     "aggregate_gout", "clip_finish", "clip_apply", "robust_step",
     "krum_dist", "krum_finish", "krum_apply",
-    "geomed_dist", "geomed_finish", "geomed_apply"};
+    "geomed_dist", "geomed_finish", "geomed_apply",
+    "attack_entries"};
 
 struct Probe {
     bool on = false;

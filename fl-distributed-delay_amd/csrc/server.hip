@@ -36,6 +36,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include "attack.h"
 #include "common.h"
 #include "flsim.h"
 #include "geomed.h"
@@ -2638,6 +2639,218 @@ static int check_geomed(const flsim_geomed* r) {
     return 0;
 }
 
+// ================================================================================================
+// Simulated Byzantine workers: IPM and ALIE mixed into the bucket sums (include/flsim.h:
+// flsim_attack; csrc/attack.h: the geometry and the element code shared with the host)
+// ================================================================================================
+struct AttackArgs {
+    float* ent[RULE_MAX_ARR];           // bucket sums, updated in place
+    int32_t honest[RULE_MAX_ARR];       // > 0: the entry is read
+    int32_t byz[RULE_MAX_ARR];          // > 0: the entry is written
+    float* b_out;                       // nullable
+    double strength;
+    long P;
+    int k, kh, ntiles;
+};
+static_assert(sizeof(AttackArgs) <= 4096, "kernel argument block");
+
+// One streaming pass, the shape of k_geomed_dist: thread t of the block's 256 owns the elements
+// u * 256 + t, u < U, of a tile (a wave's load or store is one coalesced 256-byte row) and a block
+// grid-strides over the tiles.  All loads of the honest entries for a thread's elements are issued
+// before any arithmetic; then attack_craft (csrc/attack.h) per element: y_j, mu, var and b in fp64
+// registers, in the text's order, contraction off; b rounded to fp32 once, stored to b_out, and
+// H_j + b * (float)byz[j] (attack_mix: a separate fp32 multiply and add) to the entries with
+// byz[j] >= 1 alone.  Nothing is summed across elements: the bits do not depend on the geometry.
+// The per-entry table (the addresses loaded and stored to, (double)honest, (float)byz: 448 words at
+// KPAD = 64; kept in the kernel arguments the pointers alone spilled 217 scalar registers) is
+// built in LDS by wave 0 and read by broadcast, eight entries at a time, as in k_geomed_dist; a
+// group wholly past k is skipped by a scalar branch, and the honest / Byzantine masks are
+// launch-uniform scalar pairs.  An entry that is not read (honest == 0, padding) loads the first
+// honest entry's address instead, and an element past P loads element 0: both values are dropped,
+// so every load is in bounds and no byte of a write-only entry is ever read.
+typedef float __attribute__((address_space(1)))* AttackGlobalF32;
+
+template <int KPAD, int KIND>
+__global__ void __launch_bounds__(256) k_attack(AttackArgs A) {
+#pragma clang fp contract(off)
+    constexpr int U = attack_unroll(KPAD), E = attack_tile_elems(KPAD);
+    constexpr int GRP = KPAD < 8 ? KPAD : 8;
+    __shared__ unsigned long long s_ent[KPAD];  // the address loaded for entry j
+    __shared__ unsigned long long s_dst[KPAD];  // entry j itself: the address stored to
+    __shared__ double s_hon[KPAD];
+    __shared__ float s_byz[KPAD];
+    __shared__ unsigned long long s_mask[2];    // bit j: entry j is read / is written
+    {
+        const int j = threadIdx.x;
+        if (j < 64) {                           // (wave 0: lane j is entry j)
+            float* src = nullptr;
+            int h = 0, b = 0;
+            if (j < A.k) {
+                src = A.ent[j];
+                h = A.honest[j];
+                b = A.byz[j];
+            }
+            const unsigned long long mh = __ballot(h > 0), mb = __ballot(b > 0);
+            const int first = mh ? __builtin_ctzll(mh) : 0;
+            const unsigned long long any = __shfl((unsigned long long)(uintptr_t)src, first, 64);
+            if (j < KPAD) {
+                s_ent[j] = h > 0 ? (unsigned long long)(uintptr_t)src : any;
+                s_dst[j] = (unsigned long long)(uintptr_t)src;
+                s_hon[j] = h > 0 ? (double)h : 1.0;
+                s_byz[j] = (float)b;
+            }
+            if (j == 0) {
+                s_mask[0] = mh;
+                s_mask[1] = mb;
+            }
+        }
+        __syncthreads();
+    }
+    const unsigned long long mh0 = s_mask[0], mb0 = s_mask[1];
+    for (int tl = blockIdx.x; tl < A.ntiles; tl += gridDim.x) {
+        // the table is read, and the masks and k made scalar, again in every tile: hoisted out of
+        // the loop they would hold their registers over all of it (k_geomed_dist)
+        asm volatile("" ::: "memory");
+        int h_lo = (int)mh0, h_hi = (int)(mh0 >> 32), b_lo = (int)mb0, b_hi = (int)(mb0 >> 32);
+        int k = A.k;
+        asm volatile("" : "+v"(h_lo), "+v"(h_hi), "+v"(b_lo), "+v"(b_hi), "+v"(k));
+        k = __builtin_amdgcn_readfirstlane(k);
+        const uint64_t hm = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane(h_hi) << 32) |
+                            (uint32_t)__builtin_amdgcn_readfirstlane(h_lo);
+        const uint64_t bm = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane(b_hi) << 32) |
+                            (uint32_t)__builtin_amdgcn_readfirstlane(b_lo);
+        const long e0 = (long)tl * E + threadIdx.x;
+        bool inb[U];
+        long off[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            inb[u] = e0 + u * 256 < A.P;
+            off[u] = inb[u] ? e0 + u * 256 : 0;
+        }
+        float x[U][KPAD];
+#pragma unroll
+        for (int j0 = 0; j0 < KPAD; j0 += GRP) {
+            if (j0 < k) {
+#pragma unroll
+                for (int j = j0; j < j0 + GRP; ++j) {
+                    const GeomedGlobalF32 src = (GeomedGlobalF32)s_ent[j];
+#pragma unroll
+                    for (int u = 0; u < U; ++u)
+                        x[u][j] = __builtin_nontemporal_load(src + off[u]);
+                }
+            } else {
+#pragma unroll
+                for (int j = j0; j < j0 + GRP; ++j)
+#pragma unroll
+                    for (int u = 0; u < U; ++u) x[u][j] = 0.f;
+            }
+        }
+        float b[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+            b[u] = attack_craft<KPAD, KIND>(x[u], s_hon, hm, k, (double)A.kh, A.strength);
+        if (A.b_out) {
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+                if (inb[u]) A.b_out[off[u]] = b[u];
+        }
+#pragma unroll
+        for (int j0 = 0; j0 < KPAD; j0 += GRP) {
+            if (j0 < k) {
+#pragma unroll
+                for (int j = j0; j < j0 + GRP; ++j) {
+                    if ((bm >> j) & 1) {
+                        const AttackGlobalF32 dst = (AttackGlobalF32)s_dst[j];
+                        const float nb = s_byz[j];
+                        const bool hh = (hm >> j) & 1;
+#pragma unroll
+                        for (int u = 0; u < U; ++u)
+                            if (inb[u]) dst[off[u]] = attack_mix(x[u][j], hh, b[u], nb);
+                    }
+                }
+            }
+        }
+    }
+}
+
+template <int KPAD>
+static void launch_attack(int kind, dim3 grid, hipStream_t stream, const ProbeSlot& ps,
+                          const AttackArgs& A) {
+    if (kind == FLSIM_ATTACK_IPM)
+        hipExtLaunchKernelGGL((k_attack<KPAD, FLSIM_ATTACK_IPM>), grid, dim3(256), 0, stream,
+                              ps.start, ps.stop, 0, A);
+    else
+        hipExtLaunchKernelGGL((k_attack<KPAD, FLSIM_ATTACK_ALIE>), grid, dim3(256), 0, stream,
+                              ps.start, ps.stop, 0, A);
+}
+
+// flsim_attack's fields, before any pointer is looked at; *kh: the entries with honest >= 1
+static int check_attack(const flsim_attack* a, int* kh) {
+    FLSIM_REQUIRE(a, "null attack");
+    FLSIM_REQUIRE(a->kind == FLSIM_ATTACK_IPM || a->kind == FLSIM_ATTACK_ALIE,
+                  "Invalid attack kind %d (0: ipm, 1: alie)", a->kind);
+    FLSIM_REQUIRE(a->k >= 1 && a->k <= RULE_MAX_ARR, "attack over k = %d entries (1 .. %d)", a->k,
+                  RULE_MAX_ARR);
+    FLSIM_REQUIRE(a->strength >= 0.0 && a->strength < (double)__builtin_inff(),
+                  "Invalid attack strength = %g: it must be finite and >= 0", a->strength);
+    int nh = 0, nb = 0;
+    for (int j = 0; j < a->k; ++j) {
+        FLSIM_REQUIRE(a->honest[j] >= 0, "Invalid honest count %d of entry %d: it must be >= 0",
+                      a->honest[j], j);
+        FLSIM_REQUIRE(a->byz[j] >= 0, "Invalid Byzantine count %d of entry %d: it must be >= 0",
+                      a->byz[j], j);
+        FLSIM_REQUIRE(a->honest[j] > 0 || a->byz[j] > 0, "entry %d holds no worker: honest + byz "
+                      "must be >= 1", j);
+        nh += a->honest[j] > 0;
+        nb += a->byz[j] > 0;
+    }
+    FLSIM_REQUIRE(nh >= 1, "ValueError: no entry holds an honest worker: the attacker has nothing "
+                  "to observe");
+    FLSIM_REQUIRE(nb >= 1, "no entry holds a Byzantine worker: nothing to attack");
+    *kh = nh;
+    return 0;
+}
+
+// ... and the pointers: every entry is read or written
+static int check_attack_pointers(const flsim_attack* a, const float* b_out, long P) {
+    for (int j = 0; j < a->k; ++j) {
+        FLSIM_REQUIRE(a->entries[j], "null entry %d", j);
+        FLSIM_REQUIRE(((uintptr_t)a->entries[j] & 15) == 0, "entry %d must be 16-byte aligned", j);
+    }
+    FLSIM_REQUIRE(((uintptr_t)b_out & 15) == 0, "b_out must be 16-byte aligned");
+    FLSIM_REQUIRE(P > 0 && P < (1L << 31), "P = %ld out of range", P);
+    for (int j = 0; j < a->k; ++j) {
+        for (int q = 0; q < j; ++q)
+            FLSIM_REQUIRE(!overlaps(a->entries[q], a->entries[j], P), "entries %d and %d overlap",
+                          q, j);
+        FLSIM_REQUIRE(!overlaps(a->entries[j], b_out, P), "entry %d overlaps b_out", j);
+    }
+    return 0;
+}
+
+template <int KIND>
+static void attack_eval_host(const flsim_attack* a, int kh, float* b_out, long P) {
+    uint64_t hm = 0;
+    double hon[RULE_MAX_ARR];
+    for (int j = 0; j < RULE_MAX_ARR; ++j) {
+        hon[j] = 1.0;
+        if (j < a->k && a->honest[j] > 0) {
+            hm |= 1ull << j;
+            hon[j] = (double)a->honest[j];
+        }
+    }
+    for (long e = 0; e < P; ++e) {
+        float x[RULE_MAX_ARR];
+        for (int j = 0; j < RULE_MAX_ARR; ++j) x[j] = ((hm >> j) & 1) ? a->entries[j][e] : 0.f;
+        const float b = attack_craft<RULE_MAX_ARR, KIND>(x, hon, hm, a->k, (double)kh,
+                                                         a->strength);
+        if (b_out) b_out[e] = b;
+        for (int j = 0; j < a->k; ++j)
+            if (a->byz[j] > 0)
+                a->entries[j][e] = attack_mix(x[j], (hm >> j) & 1, b, (float)a->byz[j]);
+    }
+}
+
 }  // namespace flsim
 
 using namespace flsim;
@@ -3567,6 +3780,60 @@ int flsim_geomed_eval_host(const flsim_geomed* r, long P, double* w, double* d2,
     }
     if (!g_out) return 0;
     for (long e = 0; e < P; ++e) g_out[e] = (float)wsum(w + (long)iters * k, e);
+    return 0;
+}
+
+// ---- simulated Byzantine workers: IPM / ALIE mixed into the bucket sums (include/flsim.h) --------
+long flsim_attack_tile_elems(int k) {
+    if (k < 1 || k > RULE_MAX_ARR) return 0;
+    return attack_tile_elems(attack_kpad(k));
+}
+
+// one launch of k_attack on `stream`
+int flsim_attack_entries(const flsim_attack* a, float* b_out, long P, hipStream_t stream) {
+    int kh = 0;
+    RC(check_attack(a, &kh));
+    RC(check_attack_pointers(a, b_out, P));
+    AttackArgs A{};
+    int nread = 0, nwritten = 0;
+    for (int j = 0; j < a->k; ++j) {
+        A.ent[j] = a->entries[j];
+        A.honest[j] = a->honest[j];
+        A.byz[j] = a->byz[j];
+        nread += a->honest[j] > 0;
+        nwritten += a->byz[j] > 0;
+    }
+    A.b_out = b_out;
+    A.strength = a->strength;
+    A.P = P;
+    A.k = a->k;
+    A.kh = kh;
+    const int kpad = attack_kpad(a->k);
+    A.ntiles = (int)attack_tiles(P, kpad);
+    const dim3 grid((unsigned)attack_blocks(P, kpad));
+    const ProbeSlot ps = probe_begin();
+    switch (kpad) {
+        case 4: launch_attack<4>(a->kind, grid, stream, ps, A); break;
+        case 8: launch_attack<8>(a->kind, grid, stream, ps, A); break;
+        case 16: launch_attack<16>(a->kind, grid, stream, ps, A); break;
+        case 32: launch_attack<32>(a->kind, grid, stream, ps, A); break;
+        default: launch_attack<64>(a->kind, grid, stream, ps, A); break;
+    }
+    FLSIM_LAUNCH_CHECK();
+    // algorithmic HBM bytes: the honest entries read, the Byzantine-holding ones and b_out written
+    if (probe_end(ps, K_ATTACK, 4.0 * (double)P * (nread + nwritten + (b_out ? 1 : 0)))) return 2;
+    return 0;
+}
+
+// host (testing): the same checks, then csrc/attack.h's element code over host pointers
+int flsim_attack_eval_host(const flsim_attack* a, float* b_out, long P) {
+    int kh = 0;
+    RC(check_attack(a, &kh));
+    RC(check_attack_pointers(a, b_out, P));
+    if (a->kind == FLSIM_ATTACK_IPM)
+        attack_eval_host<FLSIM_ATTACK_IPM>(a, kh, b_out, P);
+    else
+        attack_eval_host<FLSIM_ATTACK_ALIE>(a, kh, b_out, P);
     return 0;
 }
 

@@ -55,6 +55,7 @@ EXPORTS = [
     "flsim_krum_eval_host",
     "flsim_geomed_partials", "flsim_geomed_tile_elems", "flsim_geomed_optim_step",
     "flsim_geomed_eval_host",
+    "flsim_attack_tile_elems", "flsim_attack_entries", "flsim_attack_eval_host",
 ]
 COMM_ID_BYTES = 128      # FLSIM_COMM_ID_BYTES
 
@@ -127,6 +128,18 @@ class FlsimGeomedScratch(ctypes.Structure):
     _fields_ = [("partials", ctypes.c_void_p), ("n_partials", ctypes.c_long),
                 ("w", ctypes.c_void_p), ("d2", ctypes.c_void_p), ("obj", ctypes.c_void_p),
                 ("state", ctypes.c_void_p)]
+
+
+# FLSIM_ATTACK_IPM / _ALIE
+ATTACK_KINDS = {"ipm": 0, "alie": 1}
+
+
+class FlsimAttack(ctypes.Structure):
+    """flsim_attack (include/flsim.h): IPM / ALIE over k bucket sums, their honest and Byzantine
+    worker counts."""
+    _fields_ = [("kind", ctypes.c_int32), ("k", ctypes.c_int32), ("strength", ctypes.c_double),
+                ("entries", ctypes.c_void_p * MAX_ARRAYS), ("honest", ctypes.c_int32 * MAX_ARRAYS),
+                ("byz", ctypes.c_int32 * MAX_ARRAYS)]
 
 
 # FLSIM_OPT_ADAM / _ADAMW / _SGD / _ADAGRAD / _YOGI
@@ -269,6 +282,10 @@ def lib():
     L.flsim_geomed_optim_step.argtypes = [vp, vp, vp, vp, vp, vp, vp, ctypes.c_long, ctypes.c_long,
                                           vp, vp]
     L.flsim_geomed_eval_host.argtypes = [vp, ctypes.c_long, vp, vp, vp, vp]
+    L.flsim_attack_tile_elems.restype = ctypes.c_long
+    L.flsim_attack_tile_elems.argtypes = [ctypes.c_int]
+    L.flsim_attack_entries.argtypes = [vp, vp, ctypes.c_long, vp]
+    L.flsim_attack_eval_host.argtypes = [vp, vp, ctypes.c_long]
     L.flsim_cascade_program.argtypes = [ctypes.c_int, vp, vp, ctypes.c_int, vp, ctypes.c_int, vp]
     L.flsim_cascade_eval_host.argtypes = [vp, vp, vp, vp, ctypes.c_int, vp, ctypes.c_long, vp]
     L.flsim_probe_enable.argtypes = [ctypes.c_int]

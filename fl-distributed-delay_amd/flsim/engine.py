@@ -20,10 +20,10 @@ import torch
 
 import math
 
-from ._lib import (MAX_ARRAYS, OPT_KINDS, ROBUST_KINDS, FlsimClip, FlsimGeomed,
-                   FlsimGeomedScratch, FlsimKrum, FlsimKrumScratch, FlsimOptim, FlsimRobust,
-                   FlsimRule, FlsimRuleComp, FlsimRuleWeights, WorkerRec, check, lib, ptr,
-                   stream_ptr)
+from ._lib import (ATTACK_KINDS, MAX_ARRAYS, OPT_KINDS, ROBUST_KINDS, FlsimAttack, FlsimClip,
+                   FlsimGeomed, FlsimGeomedScratch, FlsimKrum, FlsimKrumScratch, FlsimOptim,
+                   FlsimRobust, FlsimRule, FlsimRuleComp, FlsimRuleWeights, WorkerRec, check, lib,
+                   ptr, stream_ptr)
 
 # named_parameters() order of models.py:PerformantNet1 (models.py:13-25)
 PN1_SHAPES = [
@@ -478,6 +478,12 @@ class NetEngine:
         over this network's P parameters; clip (a Clip) and g_out as geomed_step."""
         geomed_step(geomed, theta, m, v, step, self.P, lr, betas, eps, optim=optim, clip=clip,
                     g_out=g_out)
+
+    def attack_entries(self, attack, b_out=None):
+        """Simulated Byzantine workers (an Attack over bucket sums) over this network's P
+        parameters: the crafted vector is mixed into the entries in place; b_out as
+        attack_entries."""
+        attack_entries(attack, b_out, self.P)
 
 
 class PN1Engine(NetEngine):
@@ -1103,6 +1109,51 @@ def geomed_step(geomed, theta, m, v, step, P=None, lr=1e-3, betas=(0.9, 0.999), 
     check(lib().flsim_geomed_optim_step(
         ctypes.byref(r), ctypes.byref(s), c, ptr(g_out), ptr(theta), ptr(m), ptr(v), int(P),
         int(step), o, stream_ptr()))
+
+
+class Attack:
+    """Simulated Byzantine workers over bucket sums (flsim_attack, include/flsim.h): kind "ipm"
+    (every Byzantine worker sends -strength * mu) or "alie" (mu - strength * sigma), mu and sigma
+    the coordinate-wise mean and population standard deviation of entries[j] / honest[j] over the
+    entries with honest[j] >= 1.  entries: flat fp32 device tensors of the same length, updated in
+    place where byz[j] >= 1 (never read where honest[j] == 0); honest, byz: the workers of either
+    side summed into each.  flsim/robust.py (attack_flat) is the text."""
+
+    def __init__(self, kind, strength, entries, honest, byz):
+        entries = list(entries)
+        honest, byz = [int(c) for c in honest], [int(c) for c in byz]
+        if len(entries) != len(honest) or len(entries) != len(byz):
+            raise ValueError(f"{len(honest)} honest and {len(byz)} Byzantine counts for "
+                             f"{len(entries)} entries")
+        if len(entries) > MAX_ARRAYS:
+            raise ValueError(f"attack over k = {len(entries)} entries (1 .. {MAX_ARRAYS})")
+        self.kind, self.strength = kind, float(strength)
+        self.entries, self.honest, self.byz = entries, honest, byz   # (keeps the tensors alive)
+
+    @property
+    def k(self):
+        return len(self.entries)
+
+    def c_struct(self):
+        a = FlsimAttack()
+        a.kind = ATTACK_KINDS.get(self.kind, -1)
+        a.k = len(self.entries)
+        a.strength = self.strength
+        for j, (e, h, b) in enumerate(zip(self.entries, self.honest, self.byz)):
+            a.entries[j] = e.data_ptr() if e is not None else None
+            # (int32 fields: a count they cannot hold is refused as the library refuses one < 0)
+            a.honest[j] = h if -2 ** 31 <= h < 2 ** 31 else -1
+            a.byz[j] = b if -2 ** 31 <= b < 2 ** 31 else -1
+        return a
+
+
+def attack_entries(attack, b_out=None, P=None):
+    """Mix the attack's crafted vector into its entries in place, in one launch
+    (flsim_attack_entries); b_out (optional, [P] fp32) receives the vector itself."""
+    if P is None:
+        P = int(next(e for e in attack.entries if e is not None).numel())
+    a = attack.c_struct()
+    check(lib().flsim_attack_entries(ctypes.byref(a), ptr(b_out), int(P), stream_ptr()))
 
 
 def worker_table(recs, device):

@@ -316,3 +316,115 @@ def parse_rule(spec):
     if trim < 0 or (kind == "median" and trim != 0):
         raise ValueError(f"robust_rule {spec!r}: trim must be >= 0, and 0 for the median")
     return kind, trim
+
+
+# ---- simulated Byzantine workers: the omniscient attacks the robust rules are measured against.
+# IPM (inner-product manipulation, Xie et al. 2020): every Byzantine worker sends -eps * mu.  ALIE
+# ("A Little Is Enough", Baruch et al. 2019): every Byzantine worker sends mu - z * sigma.  The
+# yardstick of flsim_attack_entries (include/flsim.h) and of its host twin: both equal attack_flat
+# as numbers -- the same 32 bits wherever the text's value is neither zero nor NaN, a zero where it
+# gives a zero, a NaN where it gives a NaN.
+# One limit: the simulator holds bucket SUMS, not per-worker gradients, so mu and sigma are taken
+# over the honest-part means of the buckets, unweighted.  With one worker per bucket that is exactly
+# the papers' definition; with larger buckets the attacker sees sigma at bucket granularity.  The
+# population standard deviation (not the unbiased one) is chosen so that a single honest entry is
+# defined (sigma = 0).
+ATTACK_KINDS = ("ipm", "alie")
+
+
+def attack_vector(sums, honest, kind, strength):
+    """sums[j]: fp32 [P] sum of bucket j's honest workers (read only where honest[j] >= 1),
+    honest[j] >= 0.  fp64 throughout, one rounding per operation, never an fma."""
+    y = [sums[j].double() / honest[j] for j in range(len(sums)) if honest[j] >= 1]   # IEEE fp64 division
+    kh = len(y)
+    mu = _seqsum(y) / kh                               # index order
+    if kind == "ipm":
+        b = mu * (-strength)
+    else:                                              # alie
+        var = _seqsum([(t - mu) * (t - mu) for t in y]) / kh      # population variance
+        b = mu - _sqrt_rn(var) * strength              # correctly rounded sqrt, multiply, subtract
+    return b.float()                                   # one fp64 -> fp32 rounding
+
+
+def check_attack(kind, strength, honest, byz):
+    """The cases the library refuses (ValueError), in its order.  Returns (kind, strength)."""
+    import math
+    if kind not in ATTACK_KINDS:
+        raise ValueError(f"Invalid attack kind {kind!r} (supported: {ATTACK_KINDS})")
+    honest, byz = [int(h) for h in honest], [int(b) for b in byz]
+    if len(honest) != len(byz):
+        raise ValueError(f"{len(byz)} Byzantine counts for {len(honest)} honest counts")
+    if not 1 <= len(honest) <= 64:
+        raise ValueError(f"attack over k = {len(honest)} entries (1 .. 64)")
+    strength = float(strength)
+    if not (math.isfinite(strength) and strength >= 0):
+        raise ValueError(f"Invalid attack strength = {strength}: it must be finite and >= 0")
+    for j, (h, b) in enumerate(zip(honest, byz)):
+        if h < 0:
+            raise ValueError(f"Invalid honest count {h} of entry {j}: it must be >= 0")
+        if b < 0:
+            raise ValueError(f"Invalid Byzantine count {b} of entry {j}: it must be >= 0")
+        if h + b == 0:
+            raise ValueError(f"entry {j} holds no worker: honest + byz must be >= 1")
+    if not any(h >= 1 for h in honest):
+        raise ValueError("no entry holds an honest worker: the attacker has nothing to observe")
+    if not any(b >= 1 for b in byz):
+        raise ValueError("no entry holds a Byzantine worker: nothing to attack")
+    return kind, strength
+
+
+def attack_flat(sums, honest, byz, kind, strength):
+    """-> (entries, counts, b): entries[j] = sums[j] + b * float(byz[j])   (fp32: a multiply, then an add)
+    where honest[j] >= 1 and byz[j] >= 1; b * float(byz[j]) where honest[j] == 0; sums[j] itself
+    (same bits) where byz[j] == 0.  counts[j] = honest[j] + byz[j].  sums[j] is not looked at
+    where honest[j] == 0 (it may be None).
+
+    mu and sigma are taken over the honest-part means of the entries, unweighted: the simulator
+    holds bucket sums, not per-worker gradients.  With one worker per bucket that is the papers'
+    definition; with larger buckets the attacker sees sigma at bucket granularity."""
+    kind, strength = check_attack(kind, strength, honest, byz)
+    b = attack_vector(sums, honest, kind, strength)
+    entries = []
+    for j in range(len(sums)):
+        if byz[j] == 0:
+            entries.append(sums[j])
+            continue
+        t = b * torch.tensor(float(byz[j]), dtype=torch.float32)
+        entries.append(sums[j] + t if honest[j] >= 1 else t)
+    return entries, [int(h) + int(c) for h, c in zip(honest, byz)], b
+
+
+def alie_z(n, f):
+    """The ALIE paper's default z for n workers of which f are Byzantine: with s = n // 2 + 1 - f
+    honest workers to win over, z = the standard normal quantile of (n - s) / n."""
+    import statistics
+    n, f = int(n), int(f)
+    if not (0 < f and 2 * f < n):
+        raise ValueError(f"Invalid f = {f} Byzantine of n = {n} workers: 0 < f and 2 * f < n")
+    s = n // 2 + 1 - f
+    return statistics.NormalDist().inv_cdf((n - s) / n)
+
+
+def parse_attack(spec):
+    """FLSimulation's attack argument -> None or (kind, strength): None, "ipm" (eps = 1),
+    ("ipm", eps), "alie" (strength None: alie_z of every epoch's fast-worker and Byzantine counts)
+    or ("alie", z)."""
+    import math
+    if spec is None or spec == "none":
+        return None
+    if isinstance(spec, str):
+        spec = (spec,)
+    spec = tuple(spec)
+    if not spec or spec[0] not in ATTACK_KINDS or len(spec) > 2:
+        raise ValueError(f"attack {spec!r} (supported: None, 'ipm', ('ipm', eps), 'alie', "
+                         "('alie', z))")
+    kind = spec[0]
+    if len(spec) == 1 or spec[1] is None:
+        return kind, (1.0 if kind == "ipm" else None)
+    try:
+        strength = float(spec[1])
+    except (TypeError, ValueError):
+        raise ValueError(f"attack {spec!r}: the strength must be a number") from None
+    if not (math.isfinite(strength) and strength >= 0):
+        raise ValueError(f"attack {spec!r}: the strength must be finite and >= 0")
+    return kind, strength

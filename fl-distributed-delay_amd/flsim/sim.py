@@ -33,6 +33,13 @@ and optim.step() (engine.Clip; float("inf") clips nothing and only records the n
 after the all-reduce and is replicated, so it adds no collective; at world = 1 the epoch then ends
 with the slab reduction and the clipped streaming step (three launches) instead of the one fused
 launch.  grad_norms() returns the norm of every epoch's aggregate.
+
+attack (None, "ipm", ("ipm", eps), "alie", ("alie", z)) with n_byz and byz_placement ("spread",
+"block") turns n_byz of the delay-0 workers into simulated Byzantine workers that mount an
+omniscient attack on the epoch's fresh bucket entries (flsim/robust.py: attack_flat; needs
+robust_rule, ("trimmed_mean", 0) being the undefended mean over buckets).  They compute nothing:
+one launch mixes the crafted vector into the bucket sums before the robust step reads them.
+attack_log() returns every epoch's (kind, strength used, Byzantine workers present).
 """
 from __future__ import annotations
 
@@ -44,7 +51,7 @@ import torch
 from .data import DevicePool, make_test_pool
 from .engine import (PN1_SIZES, Clip, Optim, ProgramStager, Rule, engine_class, optim_defaults,
                      padded, split_views, staleness_weight)
-from .robust import GEOMED_KIND, KRUM_KINDS, check_krum, parse_rule
+from .robust import GEOMED_KIND, KRUM_KINDS, alie_z, check_krum, parse_attack, parse_rule
 from .schedule import Schedule, reference_delays
 
 SEMANTICS = ("reference", "torch1", "independent")
@@ -88,7 +95,7 @@ class FLSimulation:
                  dampening=0.0, nesterov=False, stale_weight=None, stale_normalize="weights",
                  delay_comp=None, clip_grad_norm=None, lr_decay=0.0,
                  initial_accumulator_value=None, robust_rule=None, buckets=8,
-                 keep_entries=False):
+                 keep_entries=False, attack=None, n_byz=0, byz_placement="spread"):
         if semantics not in SEMANTICS:
             raise NotImplementedError(f"semantics {semantics!r} (supported: {SEMANTICS})")
         # a robust rule in place of the mean (None: off; today's code paths exactly): (kind, trim),
@@ -101,6 +108,28 @@ class FLSimulation:
         self.sel_log = []               # per epoch: list of ints (read back) or a device tensor
         self.last_geomed = None         # the geometric median with keep_entries: the epoch's GeoMed
         self.geomed_entries = []        # per epoch: (obj, final w), device tensors or read back
+        # simulated Byzantine workers (None: off; today's code paths exactly): (kind, strength) of
+        # the attack n_byz of the delay-0 workers mount on the epoch's fresh entries
+        self.attack = parse_attack(attack)
+        self.n_byz = int(n_byz)
+        self.byz_placement = byz_placement
+        self.byz_workers = np.zeros(0, np.int64)
+        self.last_attack = None         # with keep_entries: (b, honest, byz) of the last attack
+        self.last_honest = None         # ... and the fresh entries' honest sums before it
+        self.attack_entries_log = []    # per epoch: (kind, strength used, Byzantine present)
+        if byz_placement not in ("spread", "block"):
+            raise ValueError(f"byz_placement {byz_placement!r} (supported: 'spread', 'block')")
+        if self.attack is not None and self.robust is None:
+            # the bucketed path is the only place where entries exist
+            raise NotImplementedError("an attack needs robust_rule: the bucketed entries are what "
+                                      "it acts on (robust_rule=('trimmed_mean', 0) is the "
+                                      "undefended mean over buckets)")
+        if self.n_byz < 0:
+            raise ValueError(f"n_byz = {self.n_byz}: it must be >= 0")
+        if self.n_byz >= 1 and self.attack is None:
+            raise ValueError(f"n_byz = {self.n_byz} Byzantine workers without an attack")
+        if self.attack is not None and self.n_byz == 0:
+            raise ValueError(f"attack {self.attack[0]!r} with n_byz = 0: no worker mounts it")
         if self.robust is not None:
             if self.buckets < 1:
                 raise ValueError(f"buckets = {self.buckets}: it must be >= 1")
@@ -141,6 +170,17 @@ class FLSimulation:
         self.delays = np.asarray(delays if delays is not None else reference_delays(self.n, delay),
                                  np.int32)
         self.delay_arg = delay
+        if self.attack is not None:
+            # the Byzantine set, fixed for the run, among the delay-0 workers in index order; slow
+            # workers are never Byzantine
+            F = np.nonzero(self.delays == 0)[0].astype(np.int64)
+            nF, nb = len(F), self.n_byz
+            if nb >= nF:
+                raise ValueError(f"n_byz = {nb} of {nF} delay-0 workers: at least one of them "
+                                 "must stay honest")
+            pick = list(range(nb)) if byz_placement == "block" else \
+                [((2 * q + 1) * nF) // (2 * nb) for q in range(nb)]
+            self.byz_workers = F[pick]
         self.throttle = bool(throttle)
         # betas / eps / initial_accumulator_value None: the kind's conventional value (for "adam",
         # "adamw" and "sgd" (0.9, 0.999), 1e-8 and 0)
@@ -678,9 +718,13 @@ class FLSimulation:
         for i in slow:
             classes.setdefault(dclass(i), []).append(int(i))
         own = sorted(classes.items())
-        losses = self.comm[self.Ppad:self.Ppad + len(fast)]
+        # Byzantine workers compute nothing: they are left out of the passes and of the losses
+        is_byz = np.isin(fast, self.byz_workers)
+        honest_fast = fast[~is_byz]
+        hpos = np.concatenate([[0], np.cumsum(~is_byz)]).astype(np.int64)
+        losses = self.comm[self.Ppad:self.Ppad + len(honest_fast)]
         own_workers = np.asarray([i for _, ws in own for i in ws], np.int64)
-        wt = self._worker_table(t, np.concatenate([own_workers, fast]), ks)
+        wt = self._worker_table(t, np.concatenate([own_workers, honest_fast]), ks)
         cw = self.engine.chunk_workers
         if getattr(self, "_slow_loss", None) is None or self._slow_loss.numel() < cw:
             self._slow_loss = torch.zeros(cw, device=self.device)
@@ -698,20 +742,28 @@ class FLSimulation:
             self.stale_store[(d, t)] = slot
             off += n_ws
         ns = off
-        entries, counts = [], []
+        entries, counts, byz = [], [], []
         B, nf = self.buckets, len(fast)
         for j in range(B):                       # fresh entries: one pass per non-empty bucket
             b0, b1 = (j * nf) // B, ((j + 1) * nf) // B
             if b1 == b0:
                 continue
-            eng.begin_epoch(self.theta)
-            for c0, c1 in self.chunks(b0, b1):
-                eng.run_chunk(self.theta, self.pool, wt[ns + c0:ns + c1], c1 - c0, self.n,
-                              self.seed, self.dropout, losses[c0:c1])
-            slot = self._slot()
-            eng.end_epoch(slot[:self.P])
+            # (the boundaries are drawn over all fast workers; the pass runs the honest ones)
+            h0, h1 = int(hpos[b0]), int(hpos[b1])
+            if h1 > h0:
+                eng.begin_epoch(self.theta)
+                for c0, c1 in self.chunks(h0, h1):
+                    eng.run_chunk(self.theta, self.pool, wt[ns + c0:ns + c1], c1 - c0, self.n,
+                                  self.seed, self.dropout, losses[c0:c1])
+                slot = self._slot()
+                eng.end_epoch(slot[:self.P])
+            else:       # no honest worker: no pass, a free slot the attack writes whole
+                slot = self._slot()
             entries.append(slot)
-            counts.append(b1 - b0)
+            counts.append(h1 - h0)
+            byz.append((b1 - b0) - (h1 - h0))
+        if self.attack is not None:
+            self._attack(entries, counts, byz, len(fast))
         popped = {}
         for (i, src) in plan.stale:              # stale entries: one per (class, src) slot
             key = (dclass(int(i)), int(src))
@@ -721,7 +773,7 @@ class FLSimulation:
                 popped[key] = len(entries)
                 entries.append(self.stale_store.pop(key))
                 counts.append(1)
-        self.rank_worker_steps.append(len(fast) + len(own_workers))
+        self.rank_worker_steps.append(len(honest_fast) + len(own_workers))
         if not entries:
             raise IndexError("empty weight_ups (reference: IndexError in rule, main.py:25)")
         if len(entries) > 64:
@@ -767,8 +819,41 @@ class FLSimulation:
             val = float(np.mean(lv.astype(np.float32))) if len(lv) else float("nan")
             self.loss_log.append(val)
             return val
-        self.loss_log.append((losses.detach().clone(), np.arange(len(fast))))
+        self.loss_log.append((losses.detach().clone(), np.arange(len(honest_fast))))
         return None
+
+    def _attack(self, entries, counts, byz, n_fast):
+        """The epoch's attack on the fresh entries (bucket sums of their honest workers, `counts`;
+        `byz` Byzantine workers each): one launch mixes the crafted vector into the slots in place
+        and the counts become honest + Byzantine.  An epoch whose fast set holds no Byzantine
+        worker (throttling) runs none; one with no honest fast worker raises the library's
+        ValueError."""
+        from .engine import Attack
+        kind, strength = self.attack
+        present = int(sum(byz))
+        if present == 0:
+            self.attack_entries_log.append((kind, None, 0))
+            return
+        if strength is None:                    # ALIE's default: the paper's z for this epoch
+            strength = alie_z(n_fast, present)
+        b = None
+        if self.keep_entries:
+            b = torch.empty(self.P, device=self.device)
+            self.last_honest = [e[:self.P].clone() if h else None
+                                for e, h in zip(entries, counts)]
+        self.engine.attack_entries(Attack(kind, strength, [e[:self.P] for e in entries],
+                                          counts, byz), b_out=b)
+        if self.keep_entries:
+            self.last_attack = (b, list(counts), list(byz))
+        for j, nb in enumerate(byz):
+            counts[j] += nb
+        self.attack_entries_log.append((kind, float(strength), present))
+
+    def attack_log(self):
+        """Per epoch of a run under attack (else []) the triple (kind, strength used, Byzantine
+        workers among the epoch's fast set) as Python values; (kind, None, 0) for an epoch whose
+        fast set held no Byzantine worker.  Never synchronises."""
+        return list(self.attack_entries_log)
 
     def _log_norm(self):
         """Keep this epoch's norm: a clone of the device scalar, read back only by grad_norms()."""
@@ -896,7 +981,9 @@ class FLSimulation:
         return {"stale_weight": spec, "stale_normalize": self.stale_normalize,
                 "delay_comp": self.delay_comp, "clip_grad_norm": self.clip_grad_norm,
                 "robust_rule": None if self.robust is None else list(self.robust),
-                "buckets": self.buckets}
+                "buckets": self.buckets,
+                "attack": None if self.attack is None else list(self.attack),
+                "n_byz": self.n_byz, "byz_placement": self.byz_placement}
 
     def save_checkpoint(self, path):
         torch.save(self.checkpoint(), path)
@@ -927,7 +1014,9 @@ class FLSimulation:
                      # ... and from before gradient clipping: off
                      ("clip_grad_norm", None),
                      # ... and from before the robust rules: off, the default bucket count
-                     ("robust_rule", None), ("buckets", 8)):
+                     ("robust_rule", None), ("buckets", 8),
+                     # ... and from before the simulated Byzantine workers: none
+                     ("attack", None), ("n_byz", 0), ("byz_placement", "spread")):
             cfg.setdefault(k, v)
         delays = cfg["delays"].numpy().astype(np.int32)
         if fmt == "flsim-checkpoint-1":

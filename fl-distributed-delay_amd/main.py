@@ -18,6 +18,14 @@ the M such entries (Blanchard et al. 2017), and logs the chosen entries as 'Krum
 --robust_rule geomed with --geomed_iters R, --geomed_nu NU and --geomed_weights {uniform,count}
 takes the geometric median of the entries by R smoothed Weiszfeld iterations (RFA, Pillutla et
 al. 2022; no Byzantine count needed) and logs the objective at every iterate as 'GeoMed Objective'.
+--attack {none,ipm,alie} with --n_byz N, --attack_strength X and --byz_placement {spread,block} turns
+N of the fast workers into simulated Byzantine workers (needs --robust_rule; trimmed_mean with
+--trim 0 is the undefended mean over buckets): under ipm each sends -X * mu (inner-product
+manipulation, Xie et al. 2020; default X = 1), under alie mu - X * sigma ("A Little Is Enough",
+Baruch et al. 2019; default X = the paper's z for the epoch's worker counts), mu and sigma being the
+coordinate-wise mean and standard deviation of the honest buckets' means.  --attack_strength is not
+--byz_f, which stays the count Krum tolerates.  'Attack' per epoch logs (kind, strength, Byzantine
+workers present).
 The training loop (main.py:126-188) runs as flsim.sim.FLSimulation: host schedule,
 worker-batched HIP forward/backward, fused rule()+Adam; with
 `torchrun --nproc-per-node N` the computing workers are sharded over N GPUs with one RCCL
@@ -115,6 +123,19 @@ def parse(argv=None):
     p.add_argument('--buckets', type=int, default=8, metavar='B',
                    help="--robust_rule: contiguous buckets the epoch's fast workers are averaged "
                         'in before the rule (default 8)')
+    p.add_argument('--attack', default='none', choices=['none', 'ipm', 'alie'],
+                   help='simulated Byzantine workers: inner-product manipulation (-X * mu) or "A '
+                        'Little Is Enough" (mu - X * sigma) mixed into the bucket entries (needs '
+                        '--robust_rule and --n_byz; default: none)')
+    p.add_argument('--n_byz', type=int, default=0, metavar='N',
+                   help='--attack: how many of the fast (delay-0) workers are Byzantine, fewer '
+                        'than all of them (default 0)')
+    p.add_argument('--attack_strength', type=float, default=None, metavar='X',
+                   help="--attack: ipm's eps (default 1) or alie's z (default: the paper's z for "
+                        "the epoch's fast-worker and Byzantine counts); not --byz_f")
+    p.add_argument('--byz_placement', default='spread', choices=['spread', 'block'],
+                   help='--attack: the Byzantine workers are spread evenly over the fast workers, '
+                        'or are the first N of them, filling whole buckets (default spread)')
     p.add_argument('--seed', type=int, default=0)
     p.add_argument('--semantics', default='reference', choices=['reference', 'torch1', 'independent'],
                    help='stale entry = S_{t-d} (torch>=2 aliasing), zeros (torch 1.x) or the slow '
@@ -160,6 +181,13 @@ def robust_spec(args):
     return 'median' if args.robust_rule == 'median' else ('trimmed_mean', args.trim)
 
 
+def attack_spec(args):
+    """--attack / --attack_strength as FLSimulation's attack spec."""
+    if args.attack == 'none':
+        return None
+    return args.attack if args.attack_strength is None else (args.attack, args.attack_strength)
+
+
 def optim_kwargs(args):
     """--lr_decay / --initial_accumulator_value / --eps / --beta1 / --beta2 as FLSimulation's
     arguments; a flag left out resolves to the kind's default (flsim.engine.optim_defaults)."""
@@ -203,6 +231,8 @@ def main(argv=None):
                        stale_weight=stale_spec(args), stale_normalize=args.stale_normalize,
                        delay_comp=args.delay_comp, clip_grad_norm=args.clip_grad_norm,
                        robust_rule=robust_spec(args), buckets=args.buckets,
+                       attack=attack_spec(args), n_byz=args.n_byz,
+                       byz_placement=args.byz_placement,
                        **optim_kwargs(args))
     if buffers:
         sim.engine.load_buffers(buffers)
@@ -228,6 +258,8 @@ def main(argv=None):
             emit("Grad Norm", sim.grad_norms()[-1], t)
         if args.robust_rule in ('krum', 'multi_krum'):
             emit("Krum Selected", sim.selections()[-1], t)
+        if args.attack != 'none':
+            emit("Attack", list(sim.attack_log()[-1]), t)
         if rank == 0 and (t % 10 == 0 or t == args.n_epochs - 1):
             print(f"epoch {t} Avg. Loss {loss:.5f}", flush=True)
         if args.save_model and t % 100 == 0 and t > 0 and rank == 0:   # main.py:192-194

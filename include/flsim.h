@@ -787,6 +787,66 @@ int flsim_geomed_optim_step(const flsim_geomed* r, const flsim_geomed_scratch* s
  * kernel runs; refuses what the entry point refuses about r */
 int flsim_geomed_eval_host(const flsim_geomed* r, long P, double* w, double* d2, double* obj, float* g_out);
 
+/* ---------------------------------------------------------------------------------------------
+ * Simulated Byzantine workers: the omniscient attacks IPM (inner-product manipulation, Xie et al.
+ * 2020: every Byzantine worker sends -eps * mu) and ALIE ("A Little Is Enough", Baruch et al. 2019:
+ * every Byzantine worker sends mu - z * sigma) mixed into the bucket SUMS a robust step then reads.
+ * mu and sigma are the coordinate-wise mean and population standard deviation of the honest parts'
+ * means of the entries, unweighted: the simulator holds bucket sums, not per-worker gradients, so
+ * with one worker a bucket this is the papers' definition and with larger buckets the attacker sees
+ * sigma at bucket granularity.  The text (flsim/robust.py, plain torch):
+ *
+ *   def attack_vector(sums, honest, kind, strength):
+ *       y  = [sums[j].double() / honest[j] for j in range(len(sums)) if honest[j] >= 1]   # IEEE fp64 division
+ *       kh = len(y)
+ *       mu = _seqsum(y) / kh                               # index order
+ *       if kind == "ipm":
+ *           b = mu * (-strength)
+ *       else:                                              # alie
+ *           var = _seqsum([(t - mu) * (t - mu) for t in y]) / kh      # population variance
+ *           b = mu - _sqrt_rn(var) * strength              # correctly rounded sqrt, multiply, subtract
+ *       return b.float()                                   # one fp64 -> fp32 rounding
+ *   def attack_flat(sums, honest, byz, kind, strength):    # -> (entries, counts, b)
+ *       entries[j] = sums[j] + b * float(byz[j])           # fp32: a multiply, then an add
+ *                    where honest[j] >= 1 and byz[j] >= 1; b * float(byz[j]) where honest[j] == 0;
+ *                    sums[j] itself (same bits) where byz[j] == 0
+ *       counts[j]  = honest[j] + byz[j]
+ *
+ * fp64 throughout, one rounding per operation, never an fma.  One launch on `stream`: no
+ * allocation, no synchronisation, no atomics and no reduction across elements; the result is
+ * purely element-wise, so its bits cannot depend on the launch geometry.  A thread issues the loads
+ * of all honest entries for its elements before any arithmetic, forms y_j, mu, var and b in fp64
+ * registers in the text's order (correctly rounded divisions and sqrt), rounds b to fp32 once and
+ * stores.  An entry with honest[j] >= 1 is read; an entry with byz[j] >= 1 is written; an entry
+ * with honest[j] == 0 is never read (its previous contents, any bytes, do not matter); an entry
+ * with byz[j] == 0 is never written.  b_out (nullable) receives the crafted vector b.  The result
+ * equals attack_flat "as numbers" in the sense of flsim_robust_optim_step: the same 32 bits
+ * wherever the text's value is neither zero nor NaN, a zero where it gives a zero, a NaN where it
+ * gives a NaN.  A NaN or an inf in an honest entry propagates into b exactly as the text propagates
+ * it: there is no dead-entry logic here.  P need not be a multiple of anything.
+ * Checked before any pointer, status 1: an unknown kind; k outside [1, FLSIM_MAX_ARRAYS]; a strength
+ * that is NaN, inf or < 0; a negative honest or byz; honest[j] + byz[j] == 0; no entry with
+ * honest >= 1 (the attacker has nothing to observe: "ValueError: ..."); no entry with byz >= 1.
+ * Then: a NULL or misaligned (16 bytes) entry (every entry is read or written); a misaligned
+ * b_out; P outside [1, 2^31); two entries, or an entry and b_out, that overlap.
+ * ------------------------------------------------------------------------------------------- */
+#define FLSIM_ATTACK_IPM 0
+#define FLSIM_ATTACK_ALIE 1
+typedef struct flsim_attack {
+    int32_t kind, k;                      /* FLSIM_ATTACK_*; 1 <= k <= FLSIM_MAX_ARRAYS */
+    double  strength;                     /* ipm: eps; alie: z; finite, >= 0 */
+    float*  entries[FLSIM_MAX_ARRAYS];    /* in/out bucket SUMS, updated in place */
+    int32_t honest[FLSIM_MAX_ARRAYS];     /* >= 0: the honest workers summed into the entry */
+    int32_t byz[FLSIM_MAX_ARRAYS];        /* >= 0: its Byzantine workers; honest[j] + byz[j] >= 1 */
+} flsim_attack;
+/* (tests) the launch's tile: the elements of every entry a block takes at a time (0: k out of range) */
+long flsim_attack_tile_elems(int k);
+int flsim_attack_entries(const flsim_attack* a, float* b_out /* nullable, [P] */, long P,
+                         flsim_stream_t stream);
+/* host (testing): the same for host pointers, by the same element code; refuses what the entry
+ * point refuses */
+int flsim_attack_eval_host(const flsim_attack* a, float* b_out, long P);
+
 #ifdef __cplusplus
 }
 #endif
