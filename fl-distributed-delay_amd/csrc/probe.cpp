@@ -20,7 +20,8 @@ static const char* KNAME[K_COUNT] = {
     "aggregate_gout", "clip_finish", "clip_apply", "robust_step",
     "krum_dist", "krum_finish", "krum_apply",
     "geomed_dist", "geomed_finish", "geomed_apply",
-    "attack_entries"};
+    "attack_entries",
+    "cclip_dist", "cclip_finish", "cclip_apply"};
 
 struct Probe {
     bool on = false;

@@ -24,7 +24,9 @@ enum KernelId {
     // distances, finish, apply); the geometric-median step's (distances to the iterate, finish, apply)
     K_AGG_SEQ, K_STEP, K_STEP_SEQ, K_SLABSUM, K_AGG_GOUT, K_CLIP_FIN, K_CLIP_APPLY, K_ROBUST,
     K_KRUM_DIST, K_KRUM_FIN, K_KRUM_APPLY, K_GEOMED_DIST, K_GEOMED_FIN, K_GEOMED_APPLY,
-    K_ATTACK, K_COUNT
+    // the Byzantine attack on the entries; the centered-clipping step's launches (distances to the
+    // iterate, finish, apply)
+    K_ATTACK, K_CCLIP_DIST, K_CCLIP_FIN, K_CCLIP_APPLY, K_COUNT
 };
 
 // Event pair for the launch that follows (nullptr events when the probe is off or full).  The

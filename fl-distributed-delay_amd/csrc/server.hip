@@ -37,6 +37,7 @@
 #include <string.h>
 
 #include "attack.h"
+#include "cclip.h"
 #include "common.h"
 #include "flsim.h"
 #include "geomed.h"
@@ -2851,6 +2852,485 @@ static void attack_eval_host(const flsim_attack* a, int kh, float* b_out, long P
     }
 }
 
+// ================================================================================================
+// Centered clipping with a carried center (CClip): distances to the iterate, the scalar step, apply
+// (include/flsim.h: flsim_cclip; csrc/cclip.h: the scalar code shared with the host; the geometry
+// is csrc/geomed.h's)
+// ================================================================================================
+struct CclipDistArgs {
+    const float* ent[RULE_MAX_ARR];     // bucket / class sums; nullptr = an all-zero entry
+    float cnt[RULE_MAX_ARR];            // x_j = ent[j][e] / cnt[j], as k_robust forms it
+    float rcnt[RULE_MAX_ARR];
+    const float* center;                // [P]; not read by a FRESH launch
+    const double* u;                    // later pairs: s->u, written by the finish launches
+    const double* w;                    // later pairs: s->w
+    const int32_t* state;               // later pairs: the dead flags [k]
+    double* partials;                   // [k + 1][grid]
+    long P;
+    int k, ntiles, pair;
+};
+static_assert(sizeof(CclipDistArgs) <= 4096, "kernel argument block");
+
+// One streaming pass over the k entries and the center for the iterate z = u * c + sum_j w_j * x_j:
+// the geometry, the LDS table, the load pattern and the reduction of k_geomed_dist (its comment),
+// plus the center as one more operand of z: the center's term first, then the entries in index
+// order, one multiply and one add per term with contraction off.  z starts from c * u (+0.0 with
+// no center term) and a term of weight 0 adds +-0: as in k_geomed_dist that differs from _wsum in
+// the sign of a zero z at most, which (x - z)^2 does not see.  No distance is taken for the center.
+// PAIR0: w = 0 by construction, so z = c (+0.0 when FRESH) and no entry enters z: a NaN or an inf
+// in an entry cannot reach another entry's distance, and there is no redo pass.  Every entry is
+// loaded for its distance and for the "held a NaN or an inf" mask in slot k; an entry's value is
+// used as soon as it arrives, so only the sums stay in registers over a tile.
+// Later pairs: u and w are read from s->u and s->w; a dead entry is not loaded; the center is not
+// loaded while u is +-0 (_wsum's skip-zero rule), nor by a FRESH launch at all.
+template <int KPAD, bool PAIR0, bool FRESH>
+__global__ void __launch_bounds__(256) k_cclip_dist(CclipDistArgs A) {
+#pragma clang fp contract(off)
+    constexpr int U = geomed_unroll(KPAD), E = geomed_tile_elems(KPAD);
+    constexpr int GRP = KPAD < 8 ? KPAD : 8;
+    __shared__ unsigned long long s_ent[KPAD];  // the address loaded for entry j
+    __shared__ double s_w[KPAD];
+    __shared__ float s_cnt[KPAD], s_rcnt[KPAD];
+    __shared__ unsigned long long s_mask;       // bit j: entry j is loaded
+    __shared__ double s_u;
+    {
+        const int j = threadIdx.x;
+        if (j < 64) {                           // (wave 0: lane j is entry j)
+            const float* src = nullptr;
+            double w = 0.0;
+            float c = 1.f, rc = 1.f;
+            if (j < A.k) {
+                src = A.ent[j];
+                c = A.cnt[j];
+                rc = A.rcnt[j];
+                if constexpr (!PAIR0) {
+                    w = A.w[(long)A.pair * A.k + j];
+                    if (A.state[j]) src = nullptr;
+                }
+            }
+            const unsigned long long ml = __ballot(src != nullptr);
+            const int first = ml ? __builtin_ctzll(ml) : 0;
+            const unsigned long long any = __shfl((unsigned long long)(uintptr_t)src, first, 64);
+            if (j < KPAD) {
+                s_ent[j] = src ? (unsigned long long)(uintptr_t)src : any;
+                s_w[j] = w;
+                s_cnt[j] = c;
+                s_rcnt[j] = rc;
+            }
+            if (j == 0) {
+                s_mask = ml;
+                double u = 1.0;
+                if constexpr (!PAIR0) u = A.u[A.pair];
+                s_u = u;
+            }
+        }
+        __syncthreads();
+    }
+    // launch-uniform: a scalar register pair, tested by scalar bit compares
+    const uint64_t ld_mask =
+        ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(s_mask >> 32)) << 32) |
+        (uint32_t)__builtin_amdgcn_readfirstlane((int)s_mask);
+    const GeomedGlobalF32 cen = (GeomedGlobalF32)(uintptr_t)A.center;
+    double acc[KPAD];
+#pragma unroll
+    for (int j = 0; j < KPAD; ++j) acc[j] = 0.0;
+    uint32_t bad_lo = 0, bad_hi = 0;
+    for (int tl = blockIdx.x; tl < A.ntiles; tl += gridDim.x) {
+        // the table is read, and the mask and k tested, again in every tile (k_geomed_dist)
+        asm volatile("" ::: "memory");
+        int m_lo = (int)ld_mask, m_hi = (int)(ld_mask >> 32), k = A.k;
+        asm volatile("" : "+v"(m_lo), "+v"(m_hi), "+v"(k));
+        k = __builtin_amdgcn_readfirstlane(k);
+        const uint64_t ldm = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane(m_hi) << 32) |
+                             (uint32_t)__builtin_amdgcn_readfirstlane(m_lo);
+        const long e0 = (long)tl * E + threadIdx.x;
+        bool inb[U];
+        long off[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            inb[u] = e0 + u * 256 < A.P;
+            off[u] = inb[u] ? e0 + u * 256 : 0;
+        }
+        // the center's term: launch-uniform whether it is loaded
+        double z[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) z[u] = 0.0;
+        if constexpr (!FRESH) {
+            const double uw = s_u;
+            const uint64_t ub = __builtin_bit_cast(uint64_t, uw) << 1;
+            const bool ldc = (__builtin_amdgcn_readfirstlane((int)(ub >> 32)) |
+                              __builtin_amdgcn_readfirstlane((int)ub)) != 0;
+            if (PAIR0 || ldc) {
+                float c[U];
+#pragma unroll
+                for (int u = 0; u < U; ++u) c[u] = __builtin_nontemporal_load(cen + off[u]);
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    if constexpr (PAIR0) z[u] = (double)c[u];
+                    else z[u] = (double)c[u] * uw;
+                }
+            }
+        }
+        if constexpr (PAIR0) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) z[u] = inb[u] ? z[u] : 0.0;    // (past P: the sums gain 0)
+#pragma unroll
+            for (int j0 = 0; j0 < KPAD; j0 += GRP) {
+                if (j0 < k) {
+                    float x[U][GRP];
+                    if (ldm != 0) {
+#pragma unroll
+                        for (int j = 0; j < GRP; ++j) {
+                            const GeomedGlobalF32 src = (GeomedGlobalF32)s_ent[j0 + j];
+#pragma unroll
+                            for (int u = 0; u < U; ++u)
+                                x[u][j] = __builtin_nontemporal_load(src + off[u]);
+                        }
+                    } else {
+#pragma unroll
+                        for (int j = 0; j < GRP; ++j)
+#pragma unroll
+                            for (int u = 0; u < U; ++u) x[u][j] = 0.f;
+                    }
+#pragma unroll
+                    for (int j = 0; j < GRP; ++j) {
+                        const float c = s_cnt[j0 + j], rc = s_rcnt[j0 + j];
+                        const bool ld = (ldm >> (j0 + j)) & 1;
+#pragma unroll
+                        for (int u = 0; u < U; ++u) {
+                            const float y = div_const((ld && inb[u]) ? x[u][j] : 0.f, c, rc);
+                            const uint32_t nf =
+                                !(fabsf(y) < __builtin_inff()) ? 1u << ((j0 + j) & 31) : 0u;
+                            if (j0 + j < 32) bad_lo |= nf;
+                            else bad_hi |= nf;
+                            const double d = (double)y - z[u];
+                            acc[j0 + j] = __builtin_fma(d, d, acc[j0 + j]);
+                        }
+                    }
+                }
+            }
+        } else {
+            float x[U][KPAD];
+#pragma unroll
+            for (int j0 = 0; j0 < KPAD; j0 += GRP) {
+                if (j0 < k && ldm != 0) {
+#pragma unroll
+                    for (int j = j0; j < j0 + GRP; ++j) {
+                        const GeomedGlobalF32 src = (GeomedGlobalF32)s_ent[j];
+#pragma unroll
+                        for (int u = 0; u < U; ++u)
+                            x[u][j] = __builtin_nontemporal_load(src + off[u]);
+                    }
+                } else {
+#pragma unroll
+                    for (int j = j0; j < j0 + GRP; ++j)
+#pragma unroll
+                        for (int u = 0; u < U; ++u) x[u][j] = 0.f;
+                }
+            }
+#pragma unroll
+            for (int j0 = 0; j0 < KPAD; j0 += GRP) {
+                if (j0 < k) {
+#pragma unroll
+                    for (int j = j0; j < j0 + GRP; ++j) {
+                        const float c = s_cnt[j], rc = s_rcnt[j];
+                        const double w = s_w[j];
+                        const bool ld = (ldm >> j) & 1;
+#pragma unroll
+                        for (int u = 0; u < U; ++u) {
+                            const float y = div_const((ld && inb[u]) ? x[u][j] : 0.f, c, rc);
+                            x[u][j] = y;
+                            const double t = (double)y * w;
+                            z[u] = z[u] + t;
+                        }
+                    }
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) z[u] = inb[u] ? z[u] : 0.0;    // (past P: the sums gain 0)
+#pragma unroll
+            for (int j0 = 0; j0 < KPAD; j0 += GRP) {
+                if (j0 < k) {
+#pragma unroll
+                    for (int j = j0; j < j0 + GRP; ++j)
+#pragma unroll
+                        for (int u = 0; u < U; ++u) {
+                            const double d = (double)x[u][j] - z[u];
+                            acc[j] = __builtin_fma(d, d, acc[j]);
+                        }
+                }
+            }
+        }
+    }
+    __shared__ double red[4][KPAD + 1];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int j = 0; j < KPAD; ++j) {
+        if (j < A.k) {
+            double a = acc[j];
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
+            if (lane == 0) red[wave][j] = a;
+        }
+    }
+    if constexpr (PAIR0) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            bad_lo |= (uint32_t)__shfl_xor((int)bad_lo, o, 64);
+            bad_hi |= (uint32_t)__shfl_xor((int)bad_hi, o, 64);
+        }
+        if (lane == 0)
+            red[wave][KPAD] = __builtin_bit_cast(double, ((uint64_t)bad_hi << 32) | bad_lo);
+    }
+    __syncthreads();
+    const int t = threadIdx.x;
+    if (t < A.k)
+        A.partials[(long)t * gridDim.x + blockIdx.x] =
+            (red[0][t] + red[1][t]) + (red[2][t] + red[3][t]);
+    if constexpr (PAIR0) {
+        if (t == 64) {
+            uint64_t mk = 0;
+#pragma unroll
+            for (int w = 0; w < 4; ++w) mk |= __builtin_bit_cast(uint64_t, red[w][KPAD]);
+            reinterpret_cast<uint64_t*>(A.partials)[(long)A.k * gridDim.x + blockIdx.x] = mk;
+        }
+    }
+}
+
+struct CclipFinArgs {
+    int32_t count[RULE_MAX_ARR];
+    const double* partials;             // [k + 1][nblocks]
+    double* u;                          // s->u
+    double* w;                          // s->w
+    double* d2;                         // s->d2
+    double* s;                          // s->s
+    int32_t* state;                     // s->state
+    double tau;
+    int nblocks, k, pair, weighted;
+};
+
+// One block of 16 waves, the sums as k_geomed_finish takes them (entry j's sum belongs to one wave:
+// lane l adds the partials of the blocks l, l + 64, ... in index order, a butterfly adds the 64
+// lanes -- a fixed order for a given (P, k)).  Pair 0 also ORs the blocks' masks, writes the dead
+// flags and the control words, and u[0] = 1, w[0] = 0.  Then csrc/cclip.h's scalar code of one
+// iteration on the sums in LDS, and d2[r], s[r], u[r + 1] and w[r + 1].
+__global__ void __launch_bounds__(GEOMED_FIN_THREADS) k_cclip_finish(CclipFinArgs A) {
+    __shared__ double sd[RULE_MAX_ARR], sa[RULE_MAX_ARR], sw[RULE_MAX_ARR], ss[RULE_MAX_ARR];
+    __shared__ double sterm[RULE_MAX_ARR], swn[RULE_MAX_ARR];
+    __shared__ double ssum[CCLIP_SUM_WORDS];
+    __shared__ int32_t sdead[RULE_MAX_ARR];
+    __shared__ unsigned long long smask[GEOMED_FIN_THREADS / 64];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, k = A.k, r = A.pair;
+    for (int j = wave; j < k; j += GEOMED_FIN_THREADS / 64) {
+        const double* src = A.partials + (long)j * A.nblocks;
+        double a = 0.0;
+#pragma unroll 8
+        for (int b = lane; b < A.nblocks; b += 64) a += src[b];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
+        if (lane == 0) sd[j] = a;
+    }
+    double u = 1.0;
+    if (r == 0) {
+        const unsigned long long* src =
+            reinterpret_cast<const unsigned long long*>(A.partials) + (long)k * A.nblocks;
+        unsigned long long mk = 0;
+        for (int b = t; b < A.nblocks; b += GEOMED_FIN_THREADS) mk |= src[b];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) mk |= __shfl_xor(mk, o, 64);
+        if (lane == 0) smask[wave] = mk;
+        __syncthreads();
+        if (t < k) {
+            unsigned long long all = 0;
+            for (int w = 0; w < GEOMED_FIN_THREADS / 64; ++w) all |= smask[w];
+            const int32_t dead = (int32_t)((all >> t) & 1);
+            sdead[t] = dead;
+            A.state[t] = dead;
+            sa[t] = geomed_alpha(A.weighted, A.count[t], dead);
+            sw[t] = 0.0;
+            A.w[t] = 0.0;
+        }
+        __syncthreads();
+        if (t == 0) {
+            int nd = 0;
+            for (int j = 0; j < k; ++j) nd += sdead[j];
+            A.state[k + CCLIP_ST_NDEAD] = nd;
+            for (int c = 1; c < CCLIP_ST_WORDS; ++c) A.state[k + c] = 0;
+            A.u[0] = 1.0;
+        }
+    } else {
+        u = A.u[r];
+        if (t < k) {
+            const int32_t dead = A.state[t];
+            sdead[t] = dead;
+            sa[t] = geomed_alpha(A.weighted, A.count[t], dead);
+            sw[t] = A.w[(long)r * k + t];
+        }
+    }
+    __syncthreads();
+    cclip_iterate(sd, sa, sdead, k, A.tau, u, sw, ss, sterm, ssum, swn, t, GEOMED_FIN_THREADS,
+                  [] { __syncthreads(); });
+    if (t < k) {
+        A.d2[(long)r * k + t] = sd[t];
+        A.s[(long)r * k + t] = ss[t];
+        A.w[(long)(r + 1) * k + t] = swn[t];
+    }
+    if (t == 0) A.u[r + 1] = ssum[CCLIP_SUM_U];
+}
+
+struct CclipApplyArgs {
+    const float* ent[RULE_MAX_ARR];
+    float cnt[RULE_MAX_ARR];
+    float rcnt[RULE_MAX_ARR];
+    const double* u;                    // &u[iters] (device memory, written by a finish launch)
+    const double* w;                    // w[iters]
+    float* center;                      // read (unless fresh or u = +-0), then g
+    float* g_out;                       // nullable: g is also written here
+    float* G;                           // OK_GOUT, nullable: the clipped step's G
+    double* partials;                   // OK_GOUT, nullable: block b's sum of g * g (fp64)
+    float* p;
+    float* m;
+    float* v;
+    long P;
+    int k, fresh;
+    AdamConst ac;
+    OptConst oc;
+};
+static_assert(sizeof(CclipApplyArgs) <= 4096, "kernel argument block");
+
+// One thread owns one element, as k_geomed_apply: z as _wsum forms it over the center (first; not
+// loaded when fresh or while its weight is +-0) and the entries of non-zero weight, g = (float)z,
+// center[e] = g (the unclipped g; the element's only reader is this thread, before the store),
+// then the update of kind OK, or OK_GOUT as k_robust.
+template <int OK>
+__global__ void __launch_bounds__(256) k_cclip_apply(CclipApplyArgs A) {
+#pragma clang fp contract(off)
+    constexpr bool HAS_M = opt_n_state(OK) >= 1, HAS_V = opt_n_state(OK) == 2;
+    const long e = (long)blockIdx.x * 256 + threadIdx.x;
+    const bool live = e < A.P;
+    if constexpr (OK != OK_GOUT) {
+        if (!live) return;
+    }
+    float p = 0.f, m = 0.f, v = 0.f;
+    if constexpr (OK != OK_GOUT) p = __builtin_nontemporal_load(A.p + e);
+    if constexpr (HAS_M) m = __builtin_nontemporal_load(A.m + e);
+    if constexpr (HAS_V) v = __builtin_nontemporal_load(A.v + e);
+    GeomedConstF64 wdev = (GeomedConstF64)(uintptr_t)A.w;
+    GeomedConstF64 udev = (GeomedConstF64)(uintptr_t)A.u;
+    double z = 0.0;
+    bool have = false;
+    if (!A.fresh) {
+        const double uw = udev[0];
+        if (geomed_nonzero(uw)) {
+            const float c = live ? __builtin_nontemporal_load(A.center + e) : 0.f;
+            z = (double)c * uw;
+            have = true;
+        }
+    }
+    for (int j0 = 0; j0 < A.k; j0 += 8) {
+        float x[8], c[8], rc[8];
+        double w[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            x[u] = 0.f;
+            c[u] = 1.f;
+            rc[u] = 1.f;
+            w[u] = 0.0;
+            if (j0 + u < A.k) {
+                const int j = j0 + u;
+                const float* src = A.ent[j];
+                w[u] = wdev[j];
+                c[u] = A.cnt[j];
+                rc[u] = A.rcnt[j];
+                if (geomed_nonzero(w[u]) && src && live) x[u] = __builtin_nontemporal_load(src + e);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            if (j0 + u < A.k && geomed_nonzero(w[u])) {
+                const double t = (double)div_const(x[u], c[u], rc[u]) * w[u];
+                z = have ? z + t : t;
+                have = true;
+            }
+        }
+    }
+    const float g = (float)z;
+    if constexpr (OK == OK_GOUT) {
+        if (live) {
+            __builtin_nontemporal_store(g, A.center + e);
+            if (A.g_out) __builtin_nontemporal_store(g, A.g_out + e);
+            if (A.G) __builtin_nontemporal_store(g, A.G + e);
+        }
+        if (A.partials) {
+            __shared__ double red[4];
+            const double s = block_sum_f64(live ? (double)g * (double)g : 0.0, red);
+            if (threadIdx.x == 0) A.partials[blockIdx.x] = s;
+        }
+    } else {
+        __builtin_nontemporal_store(g, A.center + e);
+        if (A.g_out) __builtin_nontemporal_store(g, A.g_out + e);
+        opt_update<OK>(A.ac, A.oc, g, p, m, v);
+        __builtin_nontemporal_store(p, A.p + e);
+        if constexpr (HAS_M) __builtin_nontemporal_store(m, A.m + e);
+        if constexpr (HAS_V) __builtin_nontemporal_store(v, A.v + e);
+    }
+}
+
+template <int KPAD>
+static void launch_cclip_dist(bool pair0, bool fresh, dim3 grid, hipStream_t stream,
+                              const ProbeSlot& ps, const CclipDistArgs& A) {
+#define FLSIM_CCLIP_DIST(P0, FR)                                                                  \
+    hipExtLaunchKernelGGL((k_cclip_dist<KPAD, P0, FR>), grid, dim3(256), 0, stream, ps.start,     \
+                          ps.stop, 0, A)
+    if (pair0 && fresh) FLSIM_CCLIP_DIST(true, true);
+    else if (pair0) FLSIM_CCLIP_DIST(true, false);
+    else if (fresh) FLSIM_CCLIP_DIST(false, true);
+    else FLSIM_CCLIP_DIST(false, false);
+#undef FLSIM_CCLIP_DIST
+}
+
+static void launch_cclip_apply(int ok, dim3 grid, hipStream_t stream, const ProbeSlot& ps,
+                               const CclipApplyArgs& A) {
+#define FLSIM_CCLIP_CASE(K)                                                                      \
+    case K:                                                                                      \
+        hipExtLaunchKernelGGL((k_cclip_apply<K>), grid, dim3(256), 0, stream, ps.start, ps.stop, \
+                              0, A);                                                             \
+        break;
+    switch (ok) {
+        FLSIM_CCLIP_CASE(OK_ADAM)
+        FLSIM_CCLIP_CASE(OK_ADAMD)
+        FLSIM_CCLIP_CASE(OK_SGDM)
+        FLSIM_CCLIP_CASE(OK_GOUT)
+        FLSIM_CCLIP_CASE(OK_ADAGRAD)
+        FLSIM_CCLIP_CASE(OK_YOGI)
+        default:
+            hipExtLaunchKernelGGL((k_cclip_apply<OK_SGD>), grid, dim3(256), 0, stream, ps.start,
+                                  ps.stop, 0, A);
+            break;
+    }
+#undef FLSIM_CCLIP_CASE
+}
+
+// flsim_cclip's hyper-parameters; before any pointer check, like check_optim
+static int check_cclip(const flsim_cclip* r) {
+    FLSIM_REQUIRE(r, "null centered-clipping rule");
+    FLSIM_REQUIRE(r->k >= 1 && r->k <= RULE_MAX_ARR,
+                  "centered clipping over k = %d entries (1 .. %d)", r->k, RULE_MAX_ARR);
+    FLSIM_REQUIRE(r->iters >= 1 && r->iters <= FLSIM_CCLIP_MAX_ITERS,
+                  "Invalid iters = %d: 1 <= iters <= %d", r->iters, FLSIM_CCLIP_MAX_ITERS);
+    FLSIM_REQUIRE(r->tau > 0.0 && r->tau < (double)__builtin_inff(),
+                  "Invalid tau = %g: it must be finite and > 0", r->tau);
+    FLSIM_REQUIRE(r->weighted == 0 || r->weighted == 1,
+                  "Invalid weighted = %d: 0 (uniform) or 1 (count)", r->weighted);
+    FLSIM_REQUIRE(r->fresh == 0 || r->fresh == 1,
+                  "Invalid fresh = %d: 0 (the center is read) or 1 (it counts as all zero)",
+                  r->fresh);
+    for (int j = 0; j < r->k; ++j)
+        FLSIM_REQUIRE(r->count[j] >= 1, "Invalid count %d of entry %d: it must be >= 1",
+                      r->count[j], j);
+    return 0;
+}
+
 }  // namespace flsim
 
 using namespace flsim;
@@ -3834,6 +4314,260 @@ int flsim_attack_eval_host(const flsim_attack* a, float* b_out, long P) {
         attack_eval_host<FLSIM_ATTACK_IPM>(a, kh, b_out, P);
     else
         attack_eval_host<FLSIM_ATTACK_ALIE>(a, kh, b_out, P);
+    return 0;
+}
+
+// ---- centered clipping (CClip) over bucket means + the update (include/flsim.h) -------------------
+long flsim_cclip_partials(long P, int k) {
+    if (k < 1 || k > RULE_MAX_ARR || P < 1 || P >= (1L << 31)) return 0;
+    return geomed_blocks(P, geomed_kpad(k)) * (k + 1);
+}
+
+long flsim_cclip_tile_elems(int k) {
+    if (k < 1 || k > RULE_MAX_ARR) return 0;
+    return geomed_tile_elems(geomed_kpad(k));
+}
+
+// iters pairs (k_cclip_dist -> s->partials; k_cclip_finish -> s->d2, s->s, s->u, s->w, s->state),
+// then k_cclip_apply in the optimizer's kind, which also stores g to r->center (optim == NULL:
+// OK_GOUT writing g_out alone; clip: OK_GOUT writing clip->G and the per-block partials, then
+// k_clip_finish and k_clip_apply).
+int flsim_cclip_optim_step(const flsim_cclip* r, const flsim_cclip_scratch* s,
+                           const flsim_clip* clip, float* g_out, float* p, float* m, float* v,
+                           long P, long step, const flsim_optim* optim, hipStream_t stream) {
+    RC(check_cclip(r));
+    if (optim) RC(check_optim(optim));
+    RC(check_clip(clip));
+    FLSIM_REQUIRE(optim || (g_out && !clip), "null optimizer (only a step that writes g_out alone, "
+                  "unclipped, takes none)");
+    OptLaunch ol{};
+    ol.ok = OK_GOUT;
+    int nstate = 0;
+    if (optim) {
+        nstate = optim_n_state(optim);
+        RC(make_opt_launch(optim, 1.0, step, &ol));
+        FLSIM_REQUIRE(p && (m || nstate < 1) && (v || nstate < 2), "null pointer");
+    } else {
+        p = nullptr;
+    }
+    if (nstate < 2) v = nullptr;
+    if (nstate < 1) m = nullptr;
+    FLSIM_REQUIRE(P > 0 && P < (1L << 31), "P = %ld out of range", P);
+    FLSIM_REQUIRE((((uintptr_t)p | (uintptr_t)m | (uintptr_t)v | (uintptr_t)g_out) & 15) == 0,
+                  "p/m/v/g_out must be 16-byte aligned");
+    const float* const outs[] = {p, m, v, g_out};
+    for (int a = 0; a < 4; ++a)
+        for (int b = a + 1; b < 4; ++b)
+            FLSIM_REQUIRE(!overlaps(outs[a], outs[b], P), "p/m/v/g_out overlap each other");
+    float* const center = r->center;
+    FLSIM_REQUIRE(center, "null centered-clipping center");
+    FLSIM_REQUIRE(((uintptr_t)center & 15) == 0, "centered-clipping center must be 16-byte aligned");
+    for (const float* o : outs)
+        FLSIM_REQUIRE(!overlaps(center, o, P), "centered-clipping center overlaps p/m/v/g_out");
+    FLSIM_REQUIRE(s && s->partials && s->u && s->w && s->d2 && s->s && s->state,
+                  "null centered-clipping scratch");
+    FLSIM_REQUIRE((((uintptr_t)s->partials | (uintptr_t)s->u | (uintptr_t)s->w | (uintptr_t)s->d2 |
+                    (uintptr_t)s->s | (uintptr_t)s->state) & 15) == 0,
+                  "centered-clipping scratch must be 16-byte aligned");
+    const int k = r->k, iters = r->iters;
+    const int kpad = geomed_kpad(k);
+    const long nblocks = geomed_blocks(P, kpad);
+    const long n_dist = nblocks * (k + 1);
+    FLSIM_REQUIRE(s->n_partials >= n_dist,
+                  "centered-clipping n_partials = %ld, this step writes %ld", s->n_partials, n_dist);
+    constexpr int NS = 6;
+    const void* const sb[NS] = {s->partials, s->u, s->w, s->d2, s->s, s->state};
+    const long sn[NS] = {8 * n_dist, 8L * (iters + 1), 8L * (iters + 1) * k, 8L * iters * k,
+                         8L * iters * k, 4L * (k + CCLIP_ST_WORDS)};
+    for (int a = 0; a < NS; ++a) {
+        for (int b = a + 1; b < NS; ++b)
+            FLSIM_REQUIRE(!overlaps_bytes(sb[a], sn[a], sb[b], sn[b]),
+                          "centered-clipping scratch buffers overlap each other");
+        for (const float* o : outs)
+            FLSIM_REQUIRE(!overlaps_bytes(sb[a], sn[a], o, 4 * P),
+                          "centered-clipping scratch overlaps p/m/v/g_out");
+        FLSIM_REQUIRE(!clip || !overlaps_bytes(sb[a], sn[a], clip->G, 4 * P),
+                      "centered-clipping scratch overlaps clip G");
+        FLSIM_REQUIRE(!overlaps_bytes(sb[a], sn[a], center, 4 * P),
+                      "centered-clipping center overlaps the centered-clipping scratch");
+    }
+    long n_part = 0;
+    if (clip) {
+        FLSIM_REQUIRE(clip->G && clip->partials && clip->out, "null clip buffer");
+        FLSIM_REQUIRE((((uintptr_t)clip->G | (uintptr_t)clip->partials | (uintptr_t)clip->out) &
+                       15) == 0, "clip G/partials/out must be 16-byte aligned");
+        for (const float* o : outs)
+            FLSIM_REQUIRE(!overlaps(clip->G, o, P), "clip G overlaps p/m/v/g_out");
+        FLSIM_REQUIRE(!overlaps(clip->G, center, P), "centered-clipping center overlaps clip G");
+    }
+    CclipDistArgs D{};
+    CclipFinArgs F{};
+    CclipApplyArgs A{};
+    int distinct = 0;
+    for (int j = 0; j < k; ++j) {
+        const float* e = r->entries[j];
+        FLSIM_REQUIRE(((uintptr_t)e & 3) == 0, "entry %d must be 4-byte aligned", j);
+        for (const float* o : outs)
+            FLSIM_REQUIRE(!overlaps(e, o, P), "entry %d overlaps p/m/v/g_out", j);
+        FLSIM_REQUIRE(!clip || !overlaps(e, clip->G, P), "entry %d overlaps clip G", j);
+        for (int a = 0; a < NS; ++a)
+            FLSIM_REQUIRE(!overlaps_bytes(e, 4 * P, sb[a], sn[a]),
+                          "entry %d overlaps the centered-clipping scratch", j);
+        FLSIM_REQUIRE(!overlaps(e, center, P), "entry %d overlaps the centered-clipping center", j);
+        volatile float one = 1.f, c = (float)r->count[j];    // RN(1 / count) in fp32
+        D.ent[j] = A.ent[j] = e;
+        D.cnt[j] = A.cnt[j] = c;
+        D.rcnt[j] = A.rcnt[j] = one / c;
+        F.count[j] = r->count[j];
+        bool seen = e == nullptr;
+        for (int q = 0; q < j && !seen; ++q) seen = r->entries[q] == e;
+        distinct += !seen;
+    }
+    const long nblk = (P + 255) / 256;
+    if (clip) {
+        n_part = nblk;
+        FLSIM_REQUIRE(clip->n_partials >= n_part, "clip n_partials = %ld, this step writes %ld",
+                      clip->n_partials, n_part);
+    }
+    const bool fresh = r->fresh != 0;
+    D.center = center;
+    D.u = s->u;
+    D.w = s->w;
+    D.state = s->state;
+    D.partials = s->partials;
+    D.P = P;
+    D.k = k;
+    D.ntiles = (int)geomed_tiles(P, kpad);
+    F.partials = s->partials;
+    F.u = s->u;
+    F.w = s->w;
+    F.d2 = s->d2;
+    F.s = s->s;
+    F.state = s->state;
+    F.tau = r->tau;
+    F.nblocks = (int)nblocks;
+    F.k = k;
+    F.weighted = r->weighted;
+    for (int pair = 0; pair < iters; ++pair) {
+        D.pair = F.pair = pair;
+        {
+            const ProbeSlot ps = probe_begin();
+            const dim3 grid((unsigned)nblocks);
+            switch (kpad) {
+                case 4: launch_cclip_dist<4>(pair == 0, fresh, grid, stream, ps, D); break;
+                case 8: launch_cclip_dist<8>(pair == 0, fresh, grid, stream, ps, D); break;
+                case 16: launch_cclip_dist<16>(pair == 0, fresh, grid, stream, ps, D); break;
+                case 32: launch_cclip_dist<32>(pair == 0, fresh, grid, stream, ps, D); break;
+                default: launch_cclip_dist<64>(pair == 0, fresh, grid, stream, ps, D); break;
+            }
+            FLSIM_LAUNCH_CHECK();
+            // algorithmic HBM bytes: each distinct entry and (unless fresh) the center read once
+            if (probe_end(ps, K_CCLIP_DIST, 4.0 * (double)P * (distinct + (fresh ? 0 : 1))))
+                return 2;
+        }
+        const ProbeSlot ps = probe_begin();
+        hipExtLaunchKernelGGL(k_cclip_finish, dim3(1), dim3(GEOMED_FIN_THREADS), 0, stream,
+                              ps.start, ps.stop, 0, F);
+        FLSIM_LAUNCH_CHECK();
+        if (probe_end(ps, K_CCLIP_FIN, 8.0 * (double)nblocks * (k + (pair == 0)) + 8.0 * (4 * k + 2)))
+            return 2;
+    }
+    A.u = s->u + iters;
+    A.w = s->w + (long)iters * k;
+    A.center = center;
+    A.g_out = g_out;
+    A.G = clip ? clip->G : nullptr;
+    A.partials = clip ? clip->partials : nullptr;
+    A.p = p;
+    A.m = m;
+    A.v = v;
+    A.P = P;
+    A.k = k;
+    A.fresh = fresh;
+    A.ac = ol.ac;
+    A.oc = ol.oc;
+    const int ok_launch = clip ? (int)OK_GOUT : ol.ok;
+    // algorithmic HBM bytes: the distinct entries and (unless fresh) the center read; the center,
+    // g_out / G written; p and the kind's state arrays read + written (not by a launch that only
+    // writes g)
+    const int nst_launch = ok_launch == OK_GOUT ? 0 : nstate;
+    const double bytes = 4.0 * (double)P * (distinct + (fresh ? 1 : 2) + (g_out ? 1 : 0) +
+                                            (clip ? 1 : 0) +
+                                            (ok_launch == OK_GOUT ? 0 : 2 + 2 * nst_launch));
+    const ProbeSlot ps = probe_begin();
+    launch_cclip_apply(ok_launch, dim3((unsigned)nblk), stream, ps, A);
+    FLSIM_LAUNCH_CHECK();
+    if (probe_end(ps, K_CCLIP_APPLY, bytes)) return 2;
+    if (!clip) return 0;
+    return clip_finish_apply(clip, n_part, ol, p, m, v, P, stream);
+}
+
+// host (testing): the text for host pointers.  The bucket means by one fp32 division each; z as
+// _wsum forms it, the center's term first; every distance as the fp64 sum of ((double)x_j - z)^2
+// in element order (one fma each, as the kernel's); then csrc/cclip.h's scalar code, and
+// g = (float)z at (u[iters], w[iters]).
+int flsim_cclip_eval_host(const flsim_cclip* r, long P, double* u, double* w, double* d2, double* s,
+                          float* g_out, float* center_out) {
+    RC(check_cclip(r));
+    const int k = r->k, iters = r->iters;
+    const bool fresh = r->fresh != 0;
+    FLSIM_REQUIRE(u && w && d2 && s, "null pointer");
+    FLSIM_REQUIRE(fresh || r->center, "null centered-clipping center");
+    FLSIM_REQUIRE(P > 0, "P = %ld out of range", P);
+    auto mean = [&](int j, long e) -> float {
+        volatile float x = r->entries[j] ? r->entries[j][e] : 0.f;
+        volatile float c = (float)r->count[j];
+        return x / c;
+    };
+    auto wsum = [&](double uw, const double* wt, long e) -> double {
+        double z = 0.0;
+        bool have = false;
+        if (!fresh && geomed_nonzero(uw)) {
+            volatile double t = (double)r->center[e] * uw;
+            z = t;
+            have = true;
+        }
+        for (int j = 0; j < k; ++j) {
+            if (!geomed_nonzero(wt[j])) continue;
+            volatile double t = (double)mean(j, e) * wt[j];
+            z = have ? z + t : (double)t;
+            have = true;
+        }
+        return z;
+    };
+    int32_t dead[RULE_MAX_ARR];
+    double a[RULE_MAX_ARR], term[RULE_MAX_ARR], sums[CCLIP_SUM_WORDS];
+    for (int j = 0; j < k; ++j) {
+        dead[j] = 0;
+        for (long e = 0; e < P && !dead[j]; ++e) {
+            const float y = mean(j, e);
+            dead[j] = !(__builtin_fabsf(y) < __builtin_inff());
+        }
+        a[j] = geomed_alpha(r->weighted, r->count[j], dead[j]);
+        w[j] = 0.0;
+    }
+    u[0] = 1.0;
+    for (int it = 0; it < iters; ++it) {
+        double* d = d2 + (long)it * k;
+        for (int j = 0; j < k; ++j) d[j] = 0.0;
+        for (long e = 0; e < P; ++e) {
+            const double z = wsum(u[it], w + (long)it * k, e);
+            for (int j = 0; j < k; ++j) {
+                if (dead[j]) continue;
+                const double df = (double)mean(j, e) - z;
+                d[j] = __builtin_fma(df, df, d[j]);
+            }
+        }
+        cclip_iterate(d, a, dead, k, r->tau, u[it], w + (long)it * k, s + (long)it * k, term, sums,
+                      w + (long)(it + 1) * k, 0, 1, [] {});
+        u[it + 1] = sums[CCLIP_SUM_U];
+    }
+    if (!g_out && !center_out) return 0;
+    for (long e = 0; e < P; ++e) {
+        const float g = (float)wsum(u[iters], w + (long)iters * k, e);
+        if (g_out) g_out[e] = g;
+        if (center_out) center_out[e] = g;
+    }
     return 0;
 }
 

@@ -56,6 +56,8 @@ EXPORTS = [
     "flsim_geomed_partials", "flsim_geomed_tile_elems", "flsim_geomed_optim_step",
     "flsim_geomed_eval_host",
     "flsim_attack_tile_elems", "flsim_attack_entries", "flsim_attack_eval_host",
+    "flsim_cclip_partials", "flsim_cclip_tile_elems", "flsim_cclip_optim_step",
+    "flsim_cclip_eval_host",
 ]
 COMM_ID_BYTES = 128      # FLSIM_COMM_ID_BYTES
 
@@ -128,6 +130,22 @@ class FlsimGeomedScratch(ctypes.Structure):
     _fields_ = [("partials", ctypes.c_void_p), ("n_partials", ctypes.c_long),
                 ("w", ctypes.c_void_p), ("d2", ctypes.c_void_p), ("obj", ctypes.c_void_p),
                 ("state", ctypes.c_void_p)]
+
+
+class FlsimCclip(ctypes.Structure):
+    """flsim_cclip (include/flsim.h): centered clipping over k bucket / class sums around the
+    carried center."""
+    _fields_ = [("iters", ctypes.c_int32), ("weighted", ctypes.c_int32), ("k", ctypes.c_int32),
+                ("fresh", ctypes.c_int32), ("tau", ctypes.c_double),
+                ("entries", ctypes.c_void_p * MAX_ARRAYS), ("count", ctypes.c_int32 * MAX_ARRAYS),
+                ("center", ctypes.c_void_p)]
+
+
+class FlsimCclipScratch(ctypes.Structure):
+    """flsim_cclip_scratch (include/flsim.h): the caller's scratch and outputs of a step."""
+    _fields_ = [("partials", ctypes.c_void_p), ("n_partials", ctypes.c_long),
+                ("u", ctypes.c_void_p), ("w", ctypes.c_void_p), ("d2", ctypes.c_void_p),
+                ("s", ctypes.c_void_p), ("state", ctypes.c_void_p)]
 
 
 # FLSIM_ATTACK_IPM / _ALIE
@@ -286,6 +304,13 @@ def lib():
     L.flsim_attack_tile_elems.argtypes = [ctypes.c_int]
     L.flsim_attack_entries.argtypes = [vp, vp, ctypes.c_long, vp]
     L.flsim_attack_eval_host.argtypes = [vp, vp, ctypes.c_long]
+    L.flsim_cclip_partials.restype = ctypes.c_long
+    L.flsim_cclip_partials.argtypes = [ctypes.c_long, ctypes.c_int]
+    L.flsim_cclip_tile_elems.restype = ctypes.c_long
+    L.flsim_cclip_tile_elems.argtypes = [ctypes.c_int]
+    L.flsim_cclip_optim_step.argtypes = [vp, vp, vp, vp, vp, vp, vp, ctypes.c_long, ctypes.c_long,
+                                         vp, vp]
+    L.flsim_cclip_eval_host.argtypes = [vp, ctypes.c_long, vp, vp, vp, vp, vp, vp]
     L.flsim_cascade_program.argtypes = [ctypes.c_int, vp, vp, ctypes.c_int, vp, ctypes.c_int, vp]
     L.flsim_cascade_eval_host.argtypes = [vp, vp, vp, vp, ctypes.c_int, vp, ctypes.c_long, vp]
     L.flsim_probe_enable.argtypes = [ctypes.c_int]

@@ -20,8 +20,9 @@ import torch
 
 import math
 
-from ._lib import (ATTACK_KINDS, MAX_ARRAYS, OPT_KINDS, ROBUST_KINDS, FlsimAttack, FlsimClip,
-                   FlsimGeomed, FlsimGeomedScratch, FlsimKrum, FlsimKrumScratch, FlsimOptim,
+from ._lib import (ATTACK_KINDS, MAX_ARRAYS, OPT_KINDS, ROBUST_KINDS, FlsimAttack, FlsimCclip,
+                   FlsimCclipScratch, FlsimClip, FlsimGeomed, FlsimGeomedScratch, FlsimKrum,
+                   FlsimKrumScratch, FlsimOptim,
                    FlsimRobust, FlsimRule, FlsimRuleComp, FlsimRuleWeights, WorkerRec, check, lib,
                    ptr, stream_ptr)
 
@@ -478,6 +479,14 @@ class NetEngine:
         over this network's P parameters; clip (a Clip) and g_out as geomed_step."""
         geomed_step(geomed, theta, m, v, step, self.P, lr, betas, eps, optim=optim, clip=clip,
                     g_out=g_out)
+
+    def cclip_step(self, cclip, theta, m, v, step, lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
+                   optim=None, clip=None, g_out=None):
+        """Centered clipping (a CClip over bucket sums and its carried center) + Adam (or the
+        update rule `optim`) over this network's P parameters; clip (a Clip) and g_out as
+        cclip_step."""
+        cclip_step(cclip, theta, m, v, step, self.P, lr, betas, eps, optim=optim, clip=clip,
+                   g_out=g_out)
 
     def attack_entries(self, attack, b_out=None):
         """Simulated Byzantine workers (an Attack over bucket sums) over this network's P
@@ -1107,6 +1116,97 @@ def geomed_step(geomed, theta, m, v, step, P=None, lr=1e-3, betas=(0.9, 0.999), 
     s = geomed.c_scratch(dev, int(P))
     c = ctypes.byref(clip.c_struct(dev, int(P))) if clip is not None else None
     check(lib().flsim_geomed_optim_step(
+        ctypes.byref(r), ctypes.byref(s), c, ptr(g_out), ptr(theta), ptr(m), ptr(v), int(P),
+        int(step), o, stream_ptr()))
+
+
+class CClip:
+    """Centered clipping over bucket / class sums around a carried center (flsim_cclip,
+    include/flsim.h; Karimireddy, He and Jaggi 2021): `iters` iterations of v <- v + sum_j lam_j
+    min(1, tau / ||x_j - v||) (x_j - v) from v = center over the k = len(entries) values
+    entries[j] / counts[j], lam = alpha / sum alpha, alpha = 1 or (weighted) the counts.  center:
+    a flat fp32 device tensor of P elements, read (unless fresh: it then counts as all zero and is
+    not read) and overwritten with the aggregate g, the next step's center.  entries, counts as
+    for Robust.  The object owns its scratch per (device, P, k, iters), allocated at the first
+    step; after a step u ([iters + 1] fp64), w ([iters + 1, k] fp64), d2 and s ([iters, k] fp64)
+    and dead ([k] int32) are device tensors, read with no synchronisation beyond the stream's
+    order; the next step overwrites them.  flsim/robust.py is the rule's text."""
+    _scratch = {}       # (device, P, k, iters) -> buffers, shared by the objects of a run
+
+    def __init__(self, tau, iters, weighted, entries, counts, center, fresh=False):
+        entries, counts = list(entries), [int(c) for c in counts]
+        if len(entries) != len(counts):
+            raise ValueError(f"{len(counts)} counts for {len(entries)} entries")
+        if len(entries) > MAX_ARRAYS:
+            raise ValueError(f"centered clipping over k = {len(entries)} entries "
+                             f"(1 .. {MAX_ARRAYS})")
+        self.tau, self.iters, self.weighted = float(tau), int(iters), bool(weighted)
+        self.entries, self.counts = entries, counts     # (the rule keeps the tensors alive)
+        self.center, self.fresh = center, bool(fresh)
+        self.u = self.w = self.d2 = self.s = self.dead = None
+
+    @property
+    def k(self):
+        return len(self.entries)
+
+    def c_struct(self):
+        r = FlsimCclip()
+        r.iters, r.weighted, r.k = self.iters, int(self.weighted), len(self.entries)
+        r.fresh, r.tau = int(self.fresh), self.tau
+        for j, (e, c) in enumerate(zip(self.entries, self.counts)):
+            r.entries[j] = e.data_ptr() if e is not None else None
+            r.count[j] = c if -2 ** 31 <= c < 2 ** 31 else 0
+        r.center = self.center.data_ptr() if self.center is not None else None
+        return r
+
+    def c_scratch(self, device, P):
+        """flsim_cclip_scratch over this device's scratch for a step over P elements."""
+        k = len(self.entries)
+        it = max(min(self.iters, 32), 1)
+        key = (str(device), int(P), k, it)
+        if key not in CClip._scratch:
+            n = max(int(lib().flsim_cclip_partials(int(P), k)), 2)
+            f64 = dict(dtype=torch.float64, device=device)
+            CClip._scratch[key] = (torch.empty(n, **f64), torch.empty(it + 1 + 2, **f64),
+                                   torch.empty((it + 1) * k + 2, **f64),
+                                   torch.empty(it * k + 2, **f64), torch.empty(it * k + 2, **f64),
+                                   torch.empty(k + 4 + 4, dtype=torch.int32, device=device))
+        partials, u, w, d2, sc, state = CClip._scratch[key]
+        s = FlsimCclipScratch()
+        s.partials = partials.data_ptr()
+        s.n_partials = int(partials.numel())
+        s.u = u.data_ptr()
+        s.w = w.data_ptr()
+        s.d2 = d2.data_ptr()
+        s.s = sc.data_ptr()
+        s.state = state.data_ptr()
+        self.partials = partials
+        self.u = u[:it + 1]
+        self.w = w[:(it + 1) * k].view(it + 1, k)
+        self.d2 = d2[:it * k].view(it, k)
+        self.s = sc[:it * k].view(it, k)
+        self.dead = state[:k]
+        return s
+
+
+def cclip_step(cclip, theta, m, v, step, P=None, lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
+               optim=None, clip=None, g_out=None):
+    """Centered clipping + Adam(lr, betas, eps), or the update rule `optim`, in 2 * iters + 1
+    launches (flsim_cclip_optim_step); cclip.center then holds the (unclipped) aggregate.  m / v,
+    clip, g_out and optim=False as robust_step."""
+    if optim is False:
+        o = None
+    else:
+        o = ctypes.byref((as_optim(optim) if optim is not None else
+                          Optim(lr=lr, betas=tuple(betas), eps=eps)).c_struct())
+    if P is None:
+        P = int((theta if theta is not None else g_out).numel())
+    r = cclip.c_struct()
+    dev = next((t.device for t in (theta, g_out, cclip.center, *cclip.entries) if t is not None),
+               None)
+    s = cclip.c_scratch(dev, int(P))
+    c = ctypes.byref(clip.c_struct(dev, int(P))) if clip is not None else None
+    check(lib().flsim_cclip_optim_step(
         ctypes.byref(r), ctypes.byref(s), c, ptr(g_out), ptr(theta), ptr(m), ptr(v), int(P),
         int(step), o, stream_ptr()))
 

@@ -10,6 +10,7 @@ NaN where it gives a NaN.
     Agg(lambda ups: trimmed_mean_rule(ups, trim=1))   # drop the lowest and the highest, average
     Agg(lambda ups: krum_rule(ups, f=1))              # the update closest to its neighbours
     Agg(lambda ups: multi_krum_rule(ups, f=1, m=3))   # the mean of the three closest
+    Agg(CenteredClip(tau=10.0, iters=1))              # centered clipping; the object keeps its center
 """
 from __future__ import annotations
 
@@ -279,18 +280,168 @@ def geomed_flat(entries, counts, iters=3, nu=1e-6, weighted=False):
     return geomed_steps(cols, geomed_alpha(counts, weighted), iters, nu)
 
 
+# ---- centered clipping with a carried center ("CClip", Karimireddy, He and Jaggi 2021: "Learning
+# from History for Byzantine Robust Optimization"): every entry is pulled towards the iterate with
+# weight min(1, tau / distance), and the first iterate is the previous epoch's aggregate, so the
+# rule has memory across epochs.  The iterate v_l = v_(l-1) + sum_j lam_j s_j (x_j - v_(l-1)) is
+# never formed: it is the affine combination u_l * c + sum_j w_l[j] * x_j of the center and the
+# entries.  The yardstick of flsim_cclip_optim_step (include/flsim.h) and of its host twin, stage by
+# stage at the device's own inputs: d2[r] within 2 (P + 2) 2^-53 relative of the distances at
+# (u[r], w[r]); s[r], u[r + 1], w[r + 1] (cclip_scalar on d2[r]) and g bit for bit.  fp64
+# throughout, one rounding per operation, never an fma.
+CCLIP_KIND = "cclip"
+CCLIP_WEIGHTS = GEOMED_WEIGHTS
+CCLIP_MAX_ITERS = 32
+
+
+def _cclip_z(x, c, u_r, w_r):
+    """u_r * c + sum_j w_r[j] * x[j] as _wsum forms it: the center's term first, then the entries
+    in index order; c is None (fresh): no center term."""
+    z = None
+    if c is not None and u_r != 0:           # (_wsum's rule for the center's term)
+        z = c * u_r
+    for j in range(x.shape[0]):
+        if w_r[j] == 0:
+            continue
+        t = x[j] * w_r[j]
+        z = t if z is None else z + t
+    return torch.zeros_like(x[0]) if z is None else z
+
+
+def cclip_dist2(x, c, u_r, w_r, alive):
+    """The squared distances of the entries x [k, numel] fp64 to the iterate of weights
+    (u_r, w_r); dead: +inf."""
+    z = _cclip_z(x, c, u_r, w_r)
+    d2_r = ((x - z) ** 2).sum(1)
+    d2_r[~alive] = float("inf")
+    return d2_r
+
+
+def cclip_scalar(d2_r, a, alive, tau, u_r, w_r):
+    """One iteration's scalar code from the squared distances (dead: +inf) -> (s, u_next, w_next)."""
+    d = _sqrt_rn(d2_r)
+    q = torch.tensor(tau, dtype=torch.float64) / d           # d = 0: +inf
+    one = torch.ones_like(q)
+    s = torch.where(q < 1, q, torch.where(q >= 1, one, q))   # min(1, q); a NaN q stays
+    s[~alive] = 0.0
+    # (no entry alive: lam = 0, not 0 / 0: g is the center, "keep the last aggregate")
+    lam = a / _seqsum(a) if bool(alive.any()) else torch.zeros_like(a)
+    t = lam * s
+    om = 1.0 - _seqsum(t)
+    return s, u_r * om, w_r * om + t                         # a multiply, then an add
+
+
+def cclip_steps(cols, center, alpha, iters, tau):
+    """cols [k, numel] fp32 (bucket means), center [numel] fp32 or None (fresh: all zero),
+    alpha [k] fp64 > 0 -> (g, u, w, d2, s): u iters + 1 scalars, w iters + 1 tensors [k], d2 and
+    s iters tensors [k].  The next step's center is g."""
+    x = cols.double()
+    c = None if center is None else center.double()
+    alive = torch.isfinite(x).all(1)         # an entry with any NaN / inf element is dead
+    a = torch.where(alive, alpha, torch.zeros_like(alpha))
+    u = [torch.tensor(1.0, dtype=torch.float64)]             # v_0 = c
+    w = [torch.zeros(x.shape[0], dtype=torch.float64)]
+    d2, s = [], []
+    for r in range(iters):
+        d2_r = cclip_dist2(x, c, u[r], w[r], alive)
+        s_r, u_next, w_next = cclip_scalar(d2_r, a, alive, tau, u[r], w[r])
+        d2.append(d2_r)
+        s.append(s_r)
+        u.append(u_next)
+        w.append(w_next)
+    g = _cclip_z(x, c, u[iters], w[iters]).float()           # one fp64 -> fp32 rounding
+    return g, u, w, d2, s
+
+
+def check_cclip(iters, tau, weights, k):
+    """The cases the library refuses (ValueError), and rule()'s IndexError on an empty list.
+    Returns (iters, tau, weights) with weights None -> "uniform"."""
+    import math
+    if k == 0:
+        raise IndexError("empty weight_ups (reference: IndexError in rule, main.py:25)")
+    iters, tau = int(iters), float(tau)
+    weights = "uniform" if weights is None else weights
+    if iters < 1 or iters > CCLIP_MAX_ITERS:
+        raise ValueError(f"Invalid iters = {iters}: 1 <= iters <= {CCLIP_MAX_ITERS}")
+    if not (math.isfinite(tau) and tau > 0):
+        raise ValueError(f"Invalid tau = {tau}: it must be finite and > 0")
+    if weights not in CCLIP_WEIGHTS:
+        raise ValueError(f"Invalid weights {weights!r} (supported: {CCLIP_WEIGHTS})")
+    return iters, tau, weights
+
+
+def cclip_flat(entries, counts, center, tau, iters=1, weighted=False):
+    """The text over flat bucket SUMS (None = an all-zero entry) with their counts and the center
+    (None: fresh): what flsim_cclip_optim_step computes.  Returns (g, u, w, d2, s)."""
+    iters, tau, _ = check_cclip(iters, tau, "count" if weighted else "uniform", len(entries))
+    ref = next(e for e in entries if e is not None)
+    sums = [torch.zeros_like(ref) if e is None else e for e in entries]
+    cols = torch.stack(bucket_means(sums, counts))
+    return cclip_steps(cols, center, geomed_alpha(counts, weighted), iters, tau)
+
+
+def cclip_rule(ups_list, center, tau, iters=1, weights=None):
+    """rule() with centered clipping of the updates around `center` (a flat fp32 tensor over all
+    tensors flattened together, or None: all zero), `iters` iterations.  weights: None (uniform)
+    or a sequence of positive per-update weights.  Returns (out_list, new_center_flat): the rule
+    is stateful, the caller passes new_center_flat as the next call's center (CenteredClip)."""
+    alpha = None
+    if weights is not None and not isinstance(weights, str):
+        alpha = torch.as_tensor(list(weights), dtype=torch.float64)
+        if alpha.numel() != len(ups_list) or not bool((alpha > 0).all()):
+            raise ValueError("weights: one positive weight per update")
+        weights = "count"
+    iters, tau, _ = check_cclip(iters, tau, weights, len(ups_list))
+    if alpha is None:
+        alpha = torch.ones(len(ups_list), dtype=torch.float64)
+    cols = torch.stack([torch.cat([u.reshape(-1) for u in ups]) for ups in ups_list])
+    g = cclip_steps(cols, center, alpha, iters, tau)[0]
+    out, off = [], 0
+    for u in ups_list[0]:
+        out.append(g[off:off + u.numel()].view(u.shape))
+        off += u.numel()
+    return out, g
+
+
+class CenteredClip:
+    """cclip_rule with its center kept between calls, usable as Agg(CenteredClip(tau, iters)): the
+    first call clips around zero, every later one around the previous aggregate.  It stays unfused
+    like any custom rule."""
+
+    def __init__(self, tau, iters=1, weights=None):
+        check_cclip(iters, tau, weights if isinstance(weights, str) or weights is None else "count", 1)
+        self.tau, self.iters, self.weights = float(tau), int(iters), weights
+        self.center = None
+
+    def __call__(self, ups_list):
+        out, self.center = cclip_rule(ups_list, self.center, self.tau, self.iters, self.weights)
+        return out
+
+
 def parse_rule(spec):
     """FLSimulation's robust_rule argument -> (kind, trim): None, "median", "trimmed_mean" (trim
     0), or ("trimmed_mean", trim); or ("krum", f) -> ("krum", f, 1) and ("multi_krum", f, m) as
     it stands (f has no default: the bare strings are refused); or "geomed", ("geomed", iters),
     ("geomed", iters, nu), ("geomed", iters, nu, "uniform" | "count") -> ("geomed", iters, nu,
-    weights), defaults 3, 1e-6, "uniform"."""
+    weights), defaults 3, 1e-6, "uniform"; or ("cclip", tau), ("cclip", tau, iters), ("cclip", tau,
+    iters, "uniform" | "count") -> ("cclip", tau, iters, weights), defaults 1, "uniform" (tau has
+    no default, its scale is the gradients': the bare string is refused)."""
     if spec is None or spec == "none":
         return None
     if isinstance(spec, str):
         spec = (spec,)
     spec = tuple(spec)
     kind = spec[0]
+    if kind == CCLIP_KIND:
+        if len(spec) < 2 or len(spec) > 4:
+            raise ValueError(f"robust_rule {spec!r} (supported: ('cclip', tau), ('cclip', tau, "
+                             "iters), ('cclip', tau, iters, 'uniform' | 'count'))")
+        try:
+            iters, tau, weights = check_cclip(spec[2] if len(spec) > 2 else 1, spec[1],
+                                              spec[3] if len(spec) > 3 else None, 1)
+        except (TypeError, ValueError) as e:
+            raise ValueError(f"robust_rule {spec!r}: {e}") from None
+        return kind, tau, iters, weights
     if kind == GEOMED_KIND:
         if len(spec) > 4:
             raise ValueError(f"robust_rule {spec!r} (supported: 'geomed', ('geomed', iters), "

@@ -51,7 +51,7 @@ import torch
 from .data import DevicePool, make_test_pool
 from .engine import (PN1_SIZES, Clip, Optim, ProgramStager, Rule, engine_class, optim_defaults,
                      padded, split_views, staleness_weight)
-from .robust import GEOMED_KIND, KRUM_KINDS, alie_z, check_krum, parse_attack, parse_rule
+from .robust import CCLIP_KIND, GEOMED_KIND, KRUM_KINDS, alie_z, check_krum, parse_attack, parse_rule
 from .schedule import Schedule, reference_delays
 
 SEMANTICS = ("reference", "torch1", "independent")
@@ -99,7 +99,8 @@ class FLSimulation:
         if semantics not in SEMANTICS:
             raise NotImplementedError(f"semantics {semantics!r} (supported: {SEMANTICS})")
         # a robust rule in place of the mean (None: off; today's code paths exactly): (kind, trim),
-        # ("krum" | "multi_krum", f, m), or ("geomed", iters, nu, weights)
+        # ("krum" | "multi_krum", f, m), ("geomed", iters, nu, weights), or ("cclip", tau, iters,
+        # weights)
         self.robust = parse_rule(robust_rule)
         self.buckets = int(buckets)
         self.keep_entries = bool(keep_entries)
@@ -108,6 +109,13 @@ class FLSimulation:
         self.sel_log = []               # per epoch: list of ints (read back) or a device tensor
         self.last_geomed = None         # the geometric median with keep_entries: the epoch's GeoMed
         self.geomed_entries = []        # per epoch: (obj, final w), device tensors or read back
+        # centered clipping: the carried center ([P] device tensor; None before the first step),
+        # with keep_entries the epoch's CClip and a clone of the center before the step (None:
+        # the step ran fresh); per epoch (final u, final w, last s), device tensors or read back
+        self.center = None
+        self.last_cclip = None
+        self.last_center = None
+        self.cclip_entries = []
         # simulated Byzantine workers (None: off; today's code paths exactly): (kind, strength) of
         # the attack n_byz of the delay-0 workers mount on the epoch's fresh entries
         self.attack = parse_attack(attack)
@@ -793,6 +801,26 @@ class FLSimulation:
             self.sel_log.append(krum.sel.detach().clone())      # (a device tensor: no sync)
             if self.keep_entries:           # (reads the device selection back: synchronises)
                 self.last_selected = [int(j) for j in krum.sel.tolist()]
+        elif self.robust[0] == CCLIP_KIND:
+            # centered clipping around the last epoch's aggregate (the first step: around zero,
+            # the center's memory is then not read)
+            from .engine import CClip
+            _, tau, iters, weights = self.robust
+            fresh = self.center is None
+            if fresh:
+                self.center = torch.empty(self.P, device=self.theta.device)
+            if self.keep_entries:
+                self.last_center = None if fresh else self.center.clone()
+            self.step += 1
+            cc = CClip(tau, iters, weights == "count", [e[:self.P] for e in entries], counts,
+                       self.center, fresh=fresh)
+            eng.cclip_step(cc, self.theta, self.m, self.v, self.step, optim=self.optim,
+                           clip=self.clip)
+            # (device tensors, cloned: no sync; the scratch is the next epoch's too)
+            self.cclip_entries.append((cc.u[-1].detach().clone(), cc.w[-1].detach().clone(),
+                                       cc.s[-1].detach().clone()))
+            if self.keep_entries:
+                self.last_cclip = cc
         elif self.robust[0] == GEOMED_KIND:
             # the geometric median (RFA): alpha = 1, or the entries' counts
             from .engine import GeoMed
@@ -883,6 +911,21 @@ class FLSimulation:
                                 w if isinstance(w, list) else [float(x) for x in w.tolist()])
                                for o, w in self.geomed_entries]
         return [(list(o), list(w)) for o, w in self.geomed_entries]
+
+    def cclip_log(self):
+        """Per epoch of a centered-clipping run (else []) the triple (u, w, n_clipped): the final
+        weight of the center and the final weights of the epoch's entries (the fresh buckets
+        first, then the popped slots) in g = u * center + sum_j w[j] * x_j, as a float and a list
+        of floats, and the number of entries the last iteration clipped (s < 1; a dead entry, s =
+        0, counts).  Synchronises on the first call after new epochs."""
+        def read(e):
+            if not torch.is_tensor(e[0]):
+                return e
+            u, w, s = e
+            return (float(u), [float(x) for x in w.tolist()],
+                    sum(1 for x in s.tolist() if x < 1))
+        self.cclip_entries = [read(e) for e in self.cclip_entries]
+        return [(u, list(w), n) for u, w, n in self.cclip_entries]
 
     def losses(self):
         out = []

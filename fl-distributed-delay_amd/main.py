@@ -18,6 +18,10 @@ the M such entries (Blanchard et al. 2017), and logs the chosen entries as 'Krum
 --robust_rule geomed with --geomed_iters R, --geomed_nu NU and --geomed_weights {uniform,count}
 takes the geometric median of the entries by R smoothed Weiszfeld iterations (RFA, Pillutla et
 al. 2022; no Byzantine count needed) and logs the objective at every iterate as 'GeoMed Objective'.
+--robust_rule cclip with --cclip_tau T (required), --cclip_iters L and --cclip_weights {uniform,count}
+clips every entry to the radius T around the previous epoch's aggregate (centered clipping,
+Karimireddy et al. 2021) and logs the center's final weight, the entries' and the number of
+clipped entries as 'CClip Weights'.
 --attack {none,ipm,alie} with --n_byz N, --attack_strength X and --byz_placement {spread,block} turns
 N of the fast workers into simulated Byzantine workers (needs --robust_rule; trimmed_mean with
 --trim 0 is the undefended mean over buckets): under ipm each sends -X * mu (inner-product
@@ -99,10 +103,20 @@ def parse(argv=None):
                    help='clip the aggregated gradient to this global 2-norm before the update, '
                         'as torch.nn.utils.clip_grad_norm_ (default: off; inf only logs the norm)')
     p.add_argument('--robust_rule', default='none',
-                   choices=['none', 'median', 'trimmed_mean', 'krum', 'multi_krum', 'geomed'],
+                   choices=['none', 'median', 'trimmed_mean', 'krum', 'multi_krum', 'geomed',
+                            'cclip'],
                    help='aggregate with the coordinate-wise median or trimmed mean, with Krum / '
-                        'Multi-Krum, or with the geometric median (RFA), over bucket means instead '
-                        'of the mean (needs --semantics independent; default: none)')
+                        'Multi-Krum, with the geometric median (RFA) or with centered clipping, '
+                        'over bucket means instead of the mean (needs --semantics independent; '
+                        'default: none)')
+    p.add_argument('--cclip_tau', type=float, default=None, metavar='T',
+                   help="--robust_rule cclip: the clipping radius, finite and > 0, on the scale of "
+                        "the gradients' norm (required: no default)")
+    p.add_argument('--cclip_iters', type=int, default=1, metavar='L',
+                   help='--robust_rule cclip: clipping iterations an epoch, 1 .. 32 (default 1)')
+    p.add_argument('--cclip_weights', default='uniform', choices=['uniform', 'count'],
+                   help="--robust_rule cclip: weigh every entry alike, or by its workers' count "
+                        '(default uniform)')
     p.add_argument('--geomed_iters', type=int, default=3, metavar='R',
                    help='--robust_rule geomed: smoothed Weiszfeld iterations, 0 .. 32 (default 3)')
     p.add_argument('--geomed_nu', type=float, default=1e-6, metavar='NU',
@@ -178,6 +192,10 @@ def robust_spec(args):
             ('multi_krum', args.byz_f, args.krum_m)
     if args.robust_rule == 'geomed':
         return ('geomed', args.geomed_iters, args.geomed_nu, args.geomed_weights)
+    if args.robust_rule == 'cclip':
+        if args.cclip_tau is None:
+            raise SystemExit("--robust_rule cclip needs --cclip_tau T")
+        return ('cclip', args.cclip_tau, args.cclip_iters, args.cclip_weights)
     return 'median' if args.robust_rule == 'median' else ('trimmed_mean', args.trim)
 
 
@@ -277,6 +295,8 @@ def main(argv=None):
     # (read back once, here: the epochs themselves never wait for the device)
     for i, (obj, _) in enumerate(sim.geomed_log()):
         emit("GeoMed Objective", obj, first + i)
+    for i, (u, w, n_clipped) in enumerate(sim.cclip_log()):
+        emit("CClip Weights", [u] + w + [n_clipped], first + i)
     acc, per = sim.evaluate()                                           # main.py:205-210
     emit("Avg. Test Accuracy", acc, t)
     emit("Class 9 Test Accuracy", per[-1], t)

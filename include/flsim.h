@@ -847,6 +847,81 @@ int flsim_attack_entries(const flsim_attack* a, float* b_out /* nullable, [P] */
  * point refuses */
 int flsim_attack_eval_host(const flsim_attack* a, float* b_out, long P);
 
+/* ---------------------------------------------------------------------------------------------
+ * Centered clipping with a carried center ("CClip", Karimireddy, He and Jaggi 2021), fused with
+ * the update.  The clipping center c of an epoch is the previous epoch's aggregate (all zero on
+ * the first step): every entry is pulled towards the iterate with weight min(1, tau / distance),
+ * so an entry far from where the model now is counts by tau / distance instead of whole or not at
+ * all.  The text (flsim/robust.py, plain torch; _seqsum and _wsum as for flsim_geomed):
+ *
+ *   def cclip_steps(cols, center, alpha, iters, tau):     # cols [k, numel] fp32 (bucket means),
+ *       x = cols.double()                                 # center [numel] fp32 or None (fresh)
+ *       alive = torch.isfinite(x).all(1)                  # an entry with any NaN / inf element is dead
+ *       a = torch.where(alive, alpha, 0.0)
+ *       lam = a / _seqsum(a) if alive.any() else zeros    # every entry dead: g is the center
+ *       u, w = [1.0], [zeros(k)]                          # v_l = u[l] * c + sum_j w[l][j] * x_j
+ *       for r in range(iters):
+ *           z = _wsum([c; x], [u[r]; w[r]])               # the center first; c is None: no such term
+ *           d2_r = ((x - z) ** 2).sum(1); d2_r[~alive] = inf
+ *           q = tau / sqrt(d2_r)                          # correctly rounded sqrt; d = 0: +inf
+ *           s_r = q where q < 1, 1 where q >= 1, q (a NaN) otherwise; s_r[~alive] = 0
+ *           t = lam * s_r; om = 1 - _seqsum(t)
+ *           u.append(u[r] * om); w.append(w[r] * om + t)  # a multiply, then an add
+ *       g = _wsum([c; x], [u[iters]; w[iters]]).float()   # one fp64 -> fp32 rounding
+ *       return g, u, w, d2, s                             # and the next step's center is g
+ *
+ * The iterate v_l = v_(l-1) + sum_j lam_j s_j (x_j - v_(l-1)) is never materialised: it is the
+ * affine combination above, so an iteration is one streaming distance launch (z formed on the fly
+ * from the k + 1 fp64 weights) and a one-block finish launch, and one apply launch at the end forms
+ * g, stores it to `center` (unclipped) and runs the update: 2 * iters + 1 launches on `stream`, no
+ * temporary of P elements, no host synchronisation, no atomics; the grid and the element-to-block
+ * map depend on (P, k) alone.  alpha_j, x_j, NULL entries, g_out, optim == NULL and clip as for
+ * flsim_geomed_optim_step.  Pair 0 has w = 0, so z = c (+0 when fresh) and a NaN or an inf in an
+ * entry cannot reach z: it notes the dead entries in its mask and there is no redo pass; later
+ * pairs do not load the dead entries.  The center is not loaded while its weight u is +-0, nor at
+ * all when fresh = 1.
+ *   d2[r]: within 2 (P + 2) 2^-53 relative of the text's distances at the device's own u[r], w[r];
+ *   s[r], u[r + 1], w[r + 1] equal, bit for bit, the text's scalar code applied to d2[r]; g equals
+ *   the text's at the device's u[iters], w[iters] bit for bit, and `center` holds the bits of g.
+ * Checked before any pointer, status 1: k outside [1, FLSIM_MAX_ARRAYS]; iters outside
+ * [1, FLSIM_CCLIP_MAX_ITERS]; tau NaN, inf or <= 0; weighted not 0 or 1; fresh not 0 or 1; a
+ * count < 1; what flsim_optim and flsim_clip are refused for.  Then: what flsim_geomed_optim_step
+ * refuses about p / m / v / g_out / P / clip, the entries and the scratch; a NULL or misaligned
+ * (16 bytes) center; the center overlapping p / m / v / g_out, clip G, the scratch or an entry.
+ * ------------------------------------------------------------------------------------------- */
+#define FLSIM_CCLIP_MAX_ITERS 32
+typedef struct flsim_cclip {
+    int32_t iters, weighted, k, fresh;        /* 1..32; 0: alpha = 1, 1: alpha = count; 1..FLSIM_MAX_ARRAYS;
+                                                 fresh 1: the center counts as all zero and is NOT read */
+    double tau;                               /* the clipping radius: finite, > 0 */
+    const float* entries[FLSIM_MAX_ARRAYS];   /* bucket / class SUMS; NULL = all zero */
+    int32_t count[FLSIM_MAX_ARRAYS];          /* >= 1: x_j[e] = entries[j][e] / (float)count[j] */
+    float* center;                            /* [P], 16-byte aligned, non-NULL: read (unless fresh), then
+                                                 overwritten with g */
+} flsim_cclip;
+typedef struct flsim_cclip_scratch {          /* caller-provided, 16-byte aligned, never pre-initialised */
+    double* partials; long n_partials;        /* >= flsim_cclip_partials(P, k) */
+    double* u;                                /* [iters + 1]       out: the center's weight in v_0 .. v_iters */
+    double* w;                                /* [(iters + 1) * k] out: the entries' weights */
+    double* d2;                               /* [iters * k]       out: squared distances; +inf for a dead entry */
+    double* s;                                /* [iters * k]       out: min(1, tau / distance); 0 for a dead entry */
+    int32_t* state;                           /* [k + 4] out: dead flags, then control words */
+} flsim_cclip_scratch;
+/* the doubles a distance launch writes for P elements and k entries (0: k or P out of range) */
+long flsim_cclip_partials(long P, int k);
+/* (tests) the distance launch's tile: the elements of every entry a block takes at a time */
+long flsim_cclip_tile_elems(int k);
+int flsim_cclip_optim_step(const flsim_cclip* r, const flsim_cclip_scratch* s, const flsim_clip* clip,
+                           float* g_out, float* p, float* m, float* v, long P, long step,
+                           const flsim_optim* optim, flsim_stream_t stream);
+/* host (testing): u [iters + 1], w [(iters + 1) * k], d2 [iters * k], s [iters * k], g (g_out
+ * nullable) and the next center (center_out nullable, [P]: the bits of g) of the text for host
+ * pointers: the distances summed in element order, then the scalar code the finish kernel runs.
+ * r->center is read unless fresh (then it may be NULL) and is not written; refuses what the entry
+ * point refuses about r's numbers */
+int flsim_cclip_eval_host(const flsim_cclip* r, long P, double* u, double* w, double* d2, double* s,
+                          float* g_out, float* center_out);
+
 #ifdef __cplusplus
 }
 #endif
