@@ -36,6 +36,8 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <type_traits>
+
 #include "attack.h"
 #include "cclip.h"
 #include "common.h"
@@ -1532,17 +1534,48 @@ static void launch_slab_rule(bool seq, unsigned nblk, hipStream_t stream, const 
                               ps.start, ps.stop, 0, A);
 }
 
+// The two dispatches from a runtime value to a template argument.  f is a generic lambda called
+// with a std::integral_constant; `decltype(x)::value` is the constant.
+// with_kind: the update kind.  GOUT says whether the site has an OK_GOUT instantiation; a site
+// without one takes OK_SGD for it, like any value that is no case.
+template <int K>
+using IntC = std::integral_constant<int, K>;
+
+template <bool GOUT, class F>
+static void with_kind(int ok, F&& f) {
+    switch (ok) {
+        case OK_ADAM: f(IntC<OK_ADAM>{}); break;
+        case OK_ADAMD: f(IntC<OK_ADAMD>{}); break;
+        case OK_SGDM: f(IntC<OK_SGDM>{}); break;
+        case OK_ADAGRAD: f(IntC<OK_ADAGRAD>{}); break;
+        case OK_YOGI: f(IntC<OK_YOGI>{}); break;
+        case OK_GOUT:
+            if constexpr (GOUT) {
+                f(IntC<OK_GOUT>{});
+                break;
+            }
+            [[fallthrough]];
+        default: f(IntC<OK_SGD>{}); break;
+    }
+}
+
+// with_kpad: a padded entry count, a power of two from KMIN to 64 (anything else takes 64)
+template <int KMIN, class F>
+static void with_kpad(int kpad, F&& f) {
+    if constexpr (KMIN < 64) {
+        if (kpad == KMIN) f(IntC<KMIN>{});
+        else with_kpad<2 * KMIN>(kpad, f);
+    } else {
+        f(IntC<64>{});
+    }
+}
+
 template <bool W, bool C = false>
 static void launch_slab_kind(int ok, bool seq, unsigned nblk, hipStream_t stream,
                              const ProbeSlot& ps, const StepArgs& A) {
-    switch (ok) {
-        case OK_ADAM: launch_slab_rule<OK_ADAM, W, C>(seq, nblk, stream, ps, A); break;
-        case OK_ADAMD: launch_slab_rule<OK_ADAMD, W, C>(seq, nblk, stream, ps, A); break;
-        case OK_SGDM: launch_slab_rule<OK_SGDM, W, C>(seq, nblk, stream, ps, A); break;
-        case OK_ADAGRAD: launch_slab_rule<OK_ADAGRAD, W, C>(seq, nblk, stream, ps, A); break;
-        case OK_YOGI: launch_slab_rule<OK_YOGI, W, C>(seq, nblk, stream, ps, A); break;
-        default: launch_slab_rule<OK_SGD, W, C>(seq, nblk, stream, ps, A); break;
-    }
+    with_kind<false>(ok, [&](auto k) {
+        launch_slab_rule<decltype(k)::value, W, C>(seq, nblk, stream, ps, A);
+    });
 }
 
 int slab_step_launch_optim(float* gradstate, const StepPlan& plan, long cnt_off, long part_off,
@@ -1647,15 +1680,9 @@ static void launch_agg(bool reg, int G, dim3 grid, hipStream_t stream, const Pro
 template <bool W, bool C = false>
 static void launch_agg_kind(int ok, bool reg, int G, dim3 grid, hipStream_t stream,
                             const ProbeSlot& ps, const AggArgs& A) {
-    switch (ok) {
-        case OK_ADAM: launch_agg<OK_ADAM, W, C>(reg, G, grid, stream, ps, A); break;
-        case OK_ADAMD: launch_agg<OK_ADAMD, W, C>(reg, G, grid, stream, ps, A); break;
-        case OK_SGDM: launch_agg<OK_SGDM, W, C>(reg, G, grid, stream, ps, A); break;
-        case OK_GOUT: launch_agg<OK_GOUT, W, C>(reg, G, grid, stream, ps, A); break;
-        case OK_ADAGRAD: launch_agg<OK_ADAGRAD, W, C>(reg, G, grid, stream, ps, A); break;
-        case OK_YOGI: launch_agg<OK_YOGI, W, C>(reg, G, grid, stream, ps, A); break;
-        default: launch_agg<OK_SGD, W, C>(reg, G, grid, stream, ps, A); break;
-    }
+    with_kind<true>(ok, [&](auto k) {
+        launch_agg<decltype(k)::value, W, C>(reg, G, grid, stream, ps, A);
+    });
 }
 
 // Clipping's max_norm (the values for which torch's clip would flip or zero the gradient, or
@@ -1667,10 +1694,12 @@ static int check_clip(const flsim_clip* c) {
     return 0;
 }
 
-// [a, a + n) and [b, b + n) floats share an element
-static bool overlaps(const float* a, const float* b, long n) {
-    return a && b && (uintptr_t)a < (uintptr_t)(b + n) && (uintptr_t)b < (uintptr_t)(a + n);
+// [a, a + na) and [b, b + nb) bytes share a byte; [a, a + n) and [b, b + n) floats share an element
+static bool overlaps(const void* a, long na, const void* b, long nb) {
+    return a && b && (uintptr_t)a < (uintptr_t)b + (uintptr_t)nb &&
+           (uintptr_t)b < (uintptr_t)a + (uintptr_t)na;
 }
+static bool overlaps(const float* a, const float* b, long n) { return overlaps(a, 4 * n, b, 4 * n); }
 
 // the clipped step's second and third launches
 static int clip_finish_apply(const flsim_clip* clip, long n_part, const OptLaunch& ol, float* p,
@@ -1693,45 +1722,26 @@ static int clip_finish_apply(const flsim_clip* clip, long n_part, const OptLaunc
     A.oc = ol.oc;
     const dim3 grid((unsigned)((P + 1023) / 1024));
     const ProbeSlot ps = probe_begin();
-    switch (ol.ok) {
-        case OK_ADAM:
-            hipExtLaunchKernelGGL(k_clip_apply<OK_ADAM>, grid, dim3(256), 0, stream, ps.start,
-                                  ps.stop, 0, A);
-            break;
-        case OK_ADAMD:
-            hipExtLaunchKernelGGL(k_clip_apply<OK_ADAMD>, grid, dim3(256), 0, stream, ps.start,
-                                  ps.stop, 0, A);
-            break;
-        case OK_SGDM:
-            hipExtLaunchKernelGGL(k_clip_apply<OK_SGDM>, grid, dim3(256), 0, stream, ps.start,
-                                  ps.stop, 0, A);
-            break;
-        case OK_ADAGRAD:
-            hipExtLaunchKernelGGL(k_clip_apply<OK_ADAGRAD>, grid, dim3(256), 0, stream, ps.start,
-                                  ps.stop, 0, A);
-            break;
-        case OK_YOGI:
-            hipExtLaunchKernelGGL(k_clip_apply<OK_YOGI>, grid, dim3(256), 0, stream, ps.start,
-                                  ps.stop, 0, A);
-            break;
-        default:
-            hipExtLaunchKernelGGL(k_clip_apply<OK_SGD>, grid, dim3(256), 0, stream, ps.start,
-                                  ps.stop, 0, A);
-            break;
-    }
+    with_kind<false>(ol.ok, [&](auto k) {
+        hipExtLaunchKernelGGL(k_clip_apply<decltype(k)::value>, grid, dim3(256), 0, stream,
+                              ps.start, ps.stop, 0, A);
+    });
     FLSIM_LAUNCH_CHECK();
     // algorithmic HBM bytes: G read; p and the kind's state arrays read + written
     return probe_end(ps, K_CLIP_APPLY, 4.0 * (double)P * (3 + 2 * opt_n_state(ol.ok)));
 }
 
 // ================================================================================================
-// k_robust: coordinate-wise median / trimmed mean over k <= 64 bucket means + the update
-// (include/flsim.h: flsim_robust; csrc/robust.h: the network and select / sum, shared with the host)
+// What the rules over bucket means share (k_robust, Krum, the geometric median, centered clipping):
+// the entry table, the apply kernels' outputs and their per-element head and tail
 // ================================================================================================
-struct RobustArgs {
+struct EntryTable {
     const float* ent[RULE_MAX_ARR];     // bucket / class sums; nullptr = an all-zero entry
     float cnt[RULE_MAX_ARR];            // (float)count[j] and RN(1 / that): x_j = ent[j][e] / cnt[j]
     float rcnt[RULE_MAX_ARR];
+};
+
+struct ApplyOut {
     float* g_out;                       // nullable: g is also written here
     float* G;                           // OK_GOUT, nullable: the clipped step's G
     double* partials;                   // OK_GOUT, nullable: block b's sum of g * g (fp64)
@@ -1739,10 +1749,212 @@ struct RobustArgs {
     float* m;
     float* v;
     long P;
-    int k, kind, trim;
-    float fn;                           // (float)(k - 2 * trim): the trimmed mean's divisor
     AdamConst ac;
     OptConst oc;
+};
+
+// One element of an apply kernel (one thread owns one element; 256 threads per block).
+// begin(): the index and `live`; false when the thread has nothing to do.  load_state(): p and the
+// m / v the kind owns.  finish(): g goes to g_out, then the update of kind OK and its stores.
+// OK_GOUT has no update: g goes to g_out and / or G, and with `partials` every thread of the block
+// stays for the block's fp64 sum of squares (one out of range adds 0).
+template <int OK>
+struct ApplyElem {
+    static constexpr bool HAS_M = opt_n_state(OK) >= 1, HAS_V = opt_n_state(OK) == 2;
+    long e;
+    bool live;
+    float p = 0.f, m = 0.f, v = 0.f;
+
+    __device__ __forceinline__ bool begin(const ApplyOut& O) {
+        e = (long)blockIdx.x * 256 + threadIdx.x;
+        live = e < O.P;
+        return OK == OK_GOUT || live;
+    }
+    __device__ __forceinline__ void load_state(const ApplyOut& O) {
+        if constexpr (OK != OK_GOUT) p = __builtin_nontemporal_load(O.p + e);
+        if constexpr (HAS_M) m = __builtin_nontemporal_load(O.m + e);
+        if constexpr (HAS_V) v = __builtin_nontemporal_load(O.v + e);
+    }
+    __device__ __forceinline__ void finish(const ApplyOut& O, float g) {
+        if constexpr (OK == OK_GOUT) {
+            if (live) {
+                if (O.g_out) __builtin_nontemporal_store(g, O.g_out + e);
+                if (O.G) __builtin_nontemporal_store(g, O.G + e);
+            }
+            if (O.partials) {
+                __shared__ double red[4];
+                const double s = block_sum_f64(live ? (double)g * (double)g : 0.0, red);
+                if (threadIdx.x == 0) O.partials[blockIdx.x] = s;
+            }
+        } else {
+            if (O.g_out) __builtin_nontemporal_store(g, O.g_out + e);
+            opt_update<OK>(O.ac, O.oc, g, p, m, v);
+            __builtin_nontemporal_store(p, O.p + e);
+            if constexpr (HAS_M) __builtin_nontemporal_store(m, O.m + e);
+            if constexpr (HAS_V) __builtin_nontemporal_store(v, O.v + e);
+        }
+    }
+};
+
+// the entry counts (the end of every bucketed rule's hyper-parameter check)
+static int check_counts(const int32_t* count, int k) {
+    for (int j = 0; j < k; ++j)
+        FLSIM_REQUIRE(count[j] >= 1, "Invalid count %d of entry %d: it must be >= 1", count[j], j);
+    return 0;
+}
+
+// ---- the host side of a bucketed step: the stages the four entry points run, in this order ------
+// (after the rule's own hyper-parameter check; a rule's checks of its center and of its scratch
+// pointers come between step_begin and check_scratch)
+struct BucketStep {
+    OptLaunch ol;                       // OK_GOUT without an optimizer
+    int nstate;
+    float *g_out, *p, *m, *v;           // p / m / v: null where the kind does not own them
+    const float* outs[4];               // p, m, v, g_out
+    const flsim_clip* clip;
+    long P, nblk;                       // nblk: the apply launch's blocks = the clip partials
+};
+
+struct Span {                           // a scratch buffer
+    const void* ptr;
+    long bytes;
+};
+
+// the optimizer's and the clip's hyper-parameters (before any pointer), then p / m / v / g_out / P
+static int step_begin(const flsim_optim* optim, const flsim_clip* clip, float* g_out, float* p,
+                      float* m, float* v, long P, long step, BucketStep* B) {
+    if (optim) RC(check_optim(optim));
+    RC(check_clip(clip));
+    FLSIM_REQUIRE(optim || (g_out && !clip), "null optimizer (only a step that writes g_out alone, "
+                  "unclipped, takes none)");
+    B->ol = OptLaunch{};
+    B->ol.ok = OK_GOUT;
+    int nstate = 0;
+    if (optim) {
+        nstate = optim_n_state(optim);
+        RC(make_opt_launch(optim, 1.0, step, &B->ol));
+        FLSIM_REQUIRE(p && (m || nstate < 1) && (v || nstate < 2), "null pointer");
+    } else {
+        p = nullptr;
+    }
+    if (nstate < 2) v = nullptr;
+    if (nstate < 1) m = nullptr;
+    FLSIM_REQUIRE(P > 0 && P < (1L << 31), "P = %ld out of range", P);
+    FLSIM_REQUIRE((((uintptr_t)p | (uintptr_t)m | (uintptr_t)v | (uintptr_t)g_out) & 15) == 0,
+                  "p/m/v/g_out must be 16-byte aligned");
+    const float* const outs[] = {p, m, v, g_out};
+    for (int a = 0; a < 4; ++a) {
+        for (int b = a + 1; b < 4; ++b)
+            FLSIM_REQUIRE(!overlaps(outs[a], outs[b], P), "p/m/v/g_out overlap each other");
+        B->outs[a] = outs[a];
+    }
+    B->nstate = nstate;
+    B->g_out = g_out;
+    B->p = p;
+    B->m = m;
+    B->v = v;
+    B->clip = clip;
+    B->P = P;
+    B->nblk = (P + 255) / 256;
+    return 0;
+}
+
+// the rule's scratch buffers against each other, the outputs, clip G and the rule's center
+// (nullable); `name` is the rule's in the messages; a buffer of no bytes overlaps nothing
+static int check_scratch(const BucketStep& B, const char* name, const Span* sc, int ns,
+                         const float* center) {
+    for (int a = 0; a < ns; ++a) {
+        if (!sc[a].bytes) continue;
+        for (int b = a + 1; b < ns; ++b)
+            FLSIM_REQUIRE(!sc[b].bytes ||
+                          !overlaps(sc[a].ptr, sc[a].bytes, sc[b].ptr, sc[b].bytes),
+                          "%s scratch buffers overlap each other", name);
+        for (const float* o : B.outs)
+            FLSIM_REQUIRE(!overlaps(sc[a].ptr, sc[a].bytes, o, 4 * B.P),
+                          "%s scratch overlaps p/m/v/g_out", name);
+        FLSIM_REQUIRE(!B.clip || !overlaps(sc[a].ptr, sc[a].bytes, B.clip->G, 4 * B.P),
+                      "%s scratch overlaps clip G", name);
+        FLSIM_REQUIRE(!overlaps(sc[a].ptr, sc[a].bytes, center, 4 * B.P),
+                      "%s center overlaps the %s scratch", name, name);
+    }
+    return 0;
+}
+
+// the clip buffers (center: centered clipping's, nullable)
+static int check_clip_buffers(const BucketStep& B, const float* center) {
+    const flsim_clip* clip = B.clip;
+    if (!clip) return 0;
+    FLSIM_REQUIRE(clip->G && clip->partials && clip->out, "null clip buffer");
+    FLSIM_REQUIRE((((uintptr_t)clip->G | (uintptr_t)clip->partials | (uintptr_t)clip->out) & 15) ==
+                  0, "clip G/partials/out must be 16-byte aligned");
+    for (const float* o : B.outs)
+        FLSIM_REQUIRE(!overlaps(clip->G, o, B.P), "clip G overlaps p/m/v/g_out");
+    FLSIM_REQUIRE(!overlaps(clip->G, center, B.P), "centered-clipping center overlaps clip G");
+    return 0;
+}
+
+// the entries: their alignment and their overlap with the outputs, clip G, the scratch (sc
+// nullable) and the center (nullable); fills T; *distinct: the entry arrays read (not NULL, each
+// counted once).  Then the size of the clip partials, the last check before the first launch.
+static int fill_entries(const BucketStep& B, const float* const* entries, const int32_t* count,
+                        int k, const char* name, const Span* sc, int ns, const float* center,
+                        EntryTable* T, int* distinct) {
+    *distinct = 0;
+    for (int j = 0; j < k; ++j) {
+        const float* e = entries[j];
+        FLSIM_REQUIRE(((uintptr_t)e & 3) == 0, "entry %d must be 4-byte aligned", j);
+        for (const float* o : B.outs)
+            FLSIM_REQUIRE(!overlaps(e, o, B.P), "entry %d overlaps p/m/v/g_out", j);
+        FLSIM_REQUIRE(!B.clip || !overlaps(e, B.clip->G, B.P), "entry %d overlaps clip G", j);
+        for (int a = 0; a < ns; ++a)
+            FLSIM_REQUIRE(!sc[a].bytes || !overlaps(e, 4 * B.P, sc[a].ptr, sc[a].bytes),
+                          "entry %d overlaps the %s scratch", j, name);
+        FLSIM_REQUIRE(!overlaps(e, center, B.P), "entry %d overlaps the %s center", j, name);
+        volatile float one = 1.f, c = (float)count[j];    // RN(1 / count) in fp32
+        T->ent[j] = e;
+        T->cnt[j] = c;
+        T->rcnt[j] = one / c;
+        bool seen = e == nullptr;
+        for (int q = 0; q < j && !seen; ++q) seen = entries[q] == e;
+        *distinct += !seen;
+    }
+    FLSIM_REQUIRE(!B.clip || B.clip->n_partials >= B.nblk,
+                  "clip n_partials = %ld, this step writes %ld", B.clip->n_partials, B.nblk);
+    return 0;
+}
+
+// The apply launch (kernel id `kid`), then the clipped step's two: fills A.O, picks the launch's
+// kind (OK_GOUT under clipping) and calls launch(kind constant, grid, probe slot).  `arrays`: the
+// P-element arrays the rule itself reads and writes, for the probe's algorithmic HBM bytes; to
+// them come g_out / G written, and p and the kind's state arrays read + written (not by a launch
+// that only writes g).
+template <class Args, class F>
+static int launch_apply(const BucketStep& B, Args& A, int kid, int arrays, hipStream_t stream,
+                        F&& launch) {
+    const flsim_clip* clip = B.clip;
+    A.O = ApplyOut{B.g_out, clip ? clip->G : nullptr, clip ? clip->partials : nullptr, B.p, B.m,
+                   B.v, B.P, B.ol.ac, B.ol.oc};
+    const int ok_launch = clip ? (int)OK_GOUT : B.ol.ok;
+    const int nst_launch = ok_launch == OK_GOUT ? 0 : B.nstate;
+    const double bytes = 4.0 * (double)B.P * (arrays + (B.g_out ? 1 : 0) + (clip ? 1 : 0) +
+                                              (ok_launch == OK_GOUT ? 0 : 2 + 2 * nst_launch));
+    const ProbeSlot ps = probe_begin();
+    with_kind<true>(ok_launch, [&](auto ok) { launch(ok, dim3((unsigned)B.nblk), ps); });
+    FLSIM_LAUNCH_CHECK();
+    if (probe_end(ps, kid, bytes)) return 2;
+    if (!clip) return 0;
+    return clip_finish_apply(clip, B.nblk, B.ol, B.p, B.m, B.v, B.P, stream);
+}
+
+// ================================================================================================
+// k_robust: coordinate-wise median / trimmed mean over k <= 64 bucket means + the update
+// (include/flsim.h: flsim_robust; csrc/robust.h: the network and select / sum, shared with the host)
+// ================================================================================================
+struct RobustArgs {
+    EntryTable T;
+    ApplyOut O;
+    int k, kind, trim;
+    float fn;                           // (float)(k - 2 * trim): the trimmed mean's divisor
 };
 static_assert(sizeof(RobustArgs) <= 4096, "kernel argument block");
 
@@ -1751,71 +1963,24 @@ static_assert(sizeof(RobustArgs) <= 4096, "kernel argument block");
 // of a thread are issued before any arithmetic, non-temporally (each byte is read once; a wave's
 // load is one coalesced 256 B row); then p / m / v; then the k divisions, the keys, the network,
 // select / sum and the update of kind OK.  KPAD is the network's size, not k: the runtime k, kind
-// and trim are launch-uniform (scalar branches skip the loads past k).
-// OK_GOUT has no update: g goes to g_out and / or G, and with `partials` every thread of the block
-// stays for the block's fp64 sum of squares (one out of range adds 0).
+// and trim are launch-uniform (scalar branches skip the loads past k).  OK_GOUT: ApplyElem.
 template <int KPAD, int OK>
 __global__ void __launch_bounds__(256) k_robust(RobustArgs A) {
-    constexpr bool HAS_M = opt_n_state(OK) >= 1, HAS_V = opt_n_state(OK) == 2;
-    const long e = (long)blockIdx.x * 256 + threadIdx.x;
-    const bool live = e < A.P;
-    if constexpr (OK != OK_GOUT) {
-        if (!live) return;
-    }
+    ApplyElem<OK> el;
+    if (!el.begin(A.O)) return;
+    const long e = el.e;
     float x[KPAD];
 #pragma unroll
     for (int j = 0; j < KPAD; ++j)
-        x[j] = (j < A.k && A.ent[j] && live) ? __builtin_nontemporal_load(A.ent[j] + e) : 0.f;
-    float p = 0.f, m = 0.f, v = 0.f;
-    if constexpr (OK != OK_GOUT) p = __builtin_nontemporal_load(A.p + e);
-    if constexpr (HAS_M) m = __builtin_nontemporal_load(A.m + e);
-    if constexpr (HAS_V) v = __builtin_nontemporal_load(A.v + e);
+        x[j] = (j < A.k && A.T.ent[j] && el.live) ? __builtin_nontemporal_load(A.T.ent[j] + e) : 0.f;
+    el.load_state(A.O);
     uint32_t key[KPAD];
 #pragma unroll
     for (int j = 0; j < KPAD; ++j)
-        key[j] = j < A.k ? robust_key(div_const(x[j], A.cnt[j], A.rcnt[j])) : ROBUST_PAD;
+        key[j] = j < A.k ? robust_key(div_const(x[j], A.T.cnt[j], A.T.rcnt[j])) : ROBUST_PAD;
     float g = robust_select<KPAD>(key, A.kind, A.trim, A.k);
     if (A.kind != FLSIM_ROBUST_MEDIAN) g = __fdiv_rn(g, A.fn);
-    if constexpr (OK == OK_GOUT) {
-        if (live) {
-            if (A.g_out) __builtin_nontemporal_store(g, A.g_out + e);
-            if (A.G) __builtin_nontemporal_store(g, A.G + e);
-        }
-        if (A.partials) {
-            __shared__ double red[4];
-            const double t = block_sum_f64(live ? (double)g * (double)g : 0.0, red);
-            if (threadIdx.x == 0) A.partials[blockIdx.x] = t;
-        }
-    } else {
-        if (A.g_out) __builtin_nontemporal_store(g, A.g_out + e);
-        opt_update<OK>(A.ac, A.oc, g, p, m, v);
-        __builtin_nontemporal_store(p, A.p + e);
-        if constexpr (HAS_M) __builtin_nontemporal_store(m, A.m + e);
-        if constexpr (HAS_V) __builtin_nontemporal_store(v, A.v + e);
-    }
-}
-
-template <int KPAD>
-static void launch_robust(int ok, dim3 grid, hipStream_t stream, const ProbeSlot& ps,
-                          const RobustArgs& A) {
-#define FLSIM_ROBUST_CASE(K)                                                                   \
-    case K:                                                                                    \
-        hipExtLaunchKernelGGL((k_robust<KPAD, K>), grid, dim3(256), 0, stream, ps.start,       \
-                              ps.stop, 0, A);                                                  \
-        break;
-    switch (ok) {
-        FLSIM_ROBUST_CASE(OK_ADAM)
-        FLSIM_ROBUST_CASE(OK_ADAMD)
-        FLSIM_ROBUST_CASE(OK_SGDM)
-        FLSIM_ROBUST_CASE(OK_GOUT)
-        FLSIM_ROBUST_CASE(OK_ADAGRAD)
-        FLSIM_ROBUST_CASE(OK_YOGI)
-        default:
-            hipExtLaunchKernelGGL((k_robust<KPAD, OK_SGD>), grid, dim3(256), 0, stream,
-                                  ps.start, ps.stop, 0, A);
-            break;
-    }
-#undef FLSIM_ROBUST_CASE
+    el.finish(A.O, g);
 }
 
 // flsim_robust's hyper-parameters; before any pointer check, like check_optim
@@ -1829,10 +1994,7 @@ static int check_robust(const flsim_robust* r) {
                   "Invalid trim %d for k = %d entries: 0 <= 2 * trim < k", r->trim, r->k);
     FLSIM_REQUIRE(r->kind != FLSIM_ROBUST_MEDIAN || r->trim == 0,
                   "the median takes no trim (trim = %d)", r->trim);
-    for (int j = 0; j < r->k; ++j)
-        FLSIM_REQUIRE(r->count[j] >= 1, "Invalid count %d of entry %d: it must be >= 1",
-                      r->count[j], j);
-    return 0;
+    return check_counts(r->count, r->k);
 }
 
 // the host twin's element: the same divisions, keys, network and select / sum as k_robust
@@ -1863,10 +2025,8 @@ static void robust_eval_host(const flsim_robust* r, long P, float* g_out) {
 // csrc/krum.h: the geometry and the score / selection code shared with the host)
 // ================================================================================================
 struct KrumDistArgs {
-    const float* ent[RULE_MAX_ARR];     // bucket / class sums; nullptr = an all-zero entry
-    float cnt[RULE_MAX_ARR];            // x_j = ent[j][e] / cnt[j], as k_robust forms it
-    float rcnt[RULE_MAX_ARR];
-    double* partials;                   // [NPB * 16][grid]
+    EntryTable T;                       // x_j = ent[j][e] / cnt[j], as k_robust forms it
+    double* partials;                  // [NPB * 16][grid]
     long P;
     int k;
     int ntiles;
@@ -1933,7 +2093,7 @@ __global__ void __launch_bounds__(KrumGeom<KPAD>::NT) k_krum_dist(KrumDistArgs A
             x[u] = f32x4{0.f, 0.f, 0.f, 0.f};
             if (idx < A.k * Q) {
                 const int j = idx / Q, q = idx - j * Q;
-                const float* src = A.ent[j];
+                const float* src = A.T.ent[j];
                 const long e = e0 + 4 * q;
                 if (src) {
                     if ((((uintptr_t)src & 15) == 0) && e + 4 <= A.P) {
@@ -1951,7 +2111,7 @@ __global__ void __launch_bounds__(KrumGeom<KPAD>::NT) k_krum_dist(KrumDistArgs A
             const int idx = u * NT + t;
             if (idx < A.k * Q) {
                 const int j = idx / Q, q = idx - j * Q;
-                const float c = A.cnt[j], rc = A.rcnt[j];
+                const float c = A.T.cnt[j], rc = A.T.rcnt[j];
                 f32x4 y;
 #pragma unroll
                 for (int w = 0; w < 4; ++w) y[w] = div_const(x[u][w], c, rc);
@@ -2075,21 +2235,11 @@ k_krum_finish(const double* partials, int nblocks, int nb, int k, int f, int m, 
 }
 
 struct KrumApplyArgs {
-    const float* ent[RULE_MAX_ARR];
-    float cnt[RULE_MAX_ARR];
-    float rcnt[RULE_MAX_ARR];
+    EntryTable T;
+    ApplyOut O;
     const int32_t* sel;                 // [m] the selection k_krum_finish wrote (device memory)
-    float* g_out;                       // nullable: g is also written here
-    float* G;                           // OK_GOUT, nullable: the clipped step's G
-    double* partials;                   // OK_GOUT, nullable: block b's sum of g * g (fp64)
-    float* p;
-    float* m;
-    float* v;
-    long P;
     int nsel;
     float fm;                           // (float)m: the divisor of the selected entries' sum
-    AdamConst ac;
-    OptConst oc;
 };
 static_assert(sizeof(KrumApplyArgs) <= 4096, "kernel argument block");
 
@@ -2100,16 +2250,11 @@ static_assert(sizeof(KrumApplyArgs) <= 4096, "kernel argument block");
 // one IEEE division, as the text.  Then the update of kind OK, or OK_GOUT as k_robust.
 template <int OK>
 __global__ void __launch_bounds__(256) k_krum_apply(KrumApplyArgs A) {
-    constexpr bool HAS_M = opt_n_state(OK) >= 1, HAS_V = opt_n_state(OK) == 2;
-    const long e = (long)blockIdx.x * 256 + threadIdx.x;
-    const bool live = e < A.P;
-    if constexpr (OK != OK_GOUT) {
-        if (!live) return;
-    }
-    float p = 0.f, m = 0.f, v = 0.f;
-    if constexpr (OK != OK_GOUT) p = __builtin_nontemporal_load(A.p + e);
-    if constexpr (HAS_M) m = __builtin_nontemporal_load(A.m + e);
-    if constexpr (HAS_V) v = __builtin_nontemporal_load(A.v + e);
+    ApplyElem<OK> el;
+    if (!el.begin(A.O)) return;
+    el.load_state(A.O);
+    const long e = el.e;
+    const bool live = el.live;
     float acc = 0.f;
     for (int t0 = 0; t0 < A.nsel; t0 += 8) {
         float x[8], c[8], rc[8];
@@ -2120,9 +2265,9 @@ __global__ void __launch_bounds__(256) k_krum_apply(KrumApplyArgs A) {
             rc[u] = 1.f;
             if (t0 + u < A.nsel) {
                 const int j = __builtin_amdgcn_readfirstlane(A.sel[t0 + u]) & (RULE_MAX_ARR - 1);
-                const float* src = A.ent[j];
-                c[u] = A.cnt[j];
-                rc[u] = A.rcnt[j];
+                const float* src = A.T.ent[j];
+                c[u] = A.T.cnt[j];
+                rc[u] = A.T.rcnt[j];
                 if (src && live) x[u] = __builtin_nontemporal_load(src + e);
             }
         }
@@ -2134,53 +2279,7 @@ __global__ void __launch_bounds__(256) k_krum_apply(KrumApplyArgs A) {
             }
         }
     }
-    const float g = __fdiv_rn(acc, A.fm);
-    if constexpr (OK == OK_GOUT) {
-        if (live) {
-            if (A.g_out) __builtin_nontemporal_store(g, A.g_out + e);
-            if (A.G) __builtin_nontemporal_store(g, A.G + e);
-        }
-        if (A.partials) {
-            __shared__ double red[4];
-            const double s = block_sum_f64(live ? (double)g * (double)g : 0.0, red);
-            if (threadIdx.x == 0) A.partials[blockIdx.x] = s;
-        }
-    } else {
-        if (A.g_out) __builtin_nontemporal_store(g, A.g_out + e);
-        opt_update<OK>(A.ac, A.oc, g, p, m, v);
-        __builtin_nontemporal_store(p, A.p + e);
-        if constexpr (HAS_M) __builtin_nontemporal_store(m, A.m + e);
-        if constexpr (HAS_V) __builtin_nontemporal_store(v, A.v + e);
-    }
-}
-
-template <int KPAD>
-static void launch_krum_dist(dim3 grid, hipStream_t stream, const ProbeSlot& ps,
-                             const KrumDistArgs& A) {
-    hipExtLaunchKernelGGL((k_krum_dist<KPAD>), grid, dim3(KrumGeom<KPAD>::NT), 0, stream, ps.start,
-                          ps.stop, 0, A);
-}
-
-static void launch_krum_apply(int ok, dim3 grid, hipStream_t stream, const ProbeSlot& ps,
-                              const KrumApplyArgs& A) {
-#define FLSIM_KRUM_CASE(K)                                                                     \
-    case K:                                                                                    \
-        hipExtLaunchKernelGGL((k_krum_apply<K>), grid, dim3(256), 0, stream, ps.start, ps.stop, \
-                              0, A);                                                           \
-        break;
-    switch (ok) {
-        FLSIM_KRUM_CASE(OK_ADAM)
-        FLSIM_KRUM_CASE(OK_ADAMD)
-        FLSIM_KRUM_CASE(OK_SGDM)
-        FLSIM_KRUM_CASE(OK_GOUT)
-        FLSIM_KRUM_CASE(OK_ADAGRAD)
-        FLSIM_KRUM_CASE(OK_YOGI)
-        default:
-            hipExtLaunchKernelGGL((k_krum_apply<OK_SGD>), grid, dim3(256), 0, stream, ps.start,
-                                  ps.stop, 0, A);
-            break;
-    }
-#undef FLSIM_KRUM_CASE
+    el.finish(A.O, __fdiv_rn(acc, A.fm));
 }
 
 // flsim_krum's hyper-parameters; before any pointer check, like check_optim
@@ -2193,16 +2292,7 @@ static int check_krum(const flsim_krum* r) {
     FLSIM_REQUIRE(r->m >= 1 && r->m <= r->k - r->f,
                   "Invalid m = %d for k = %d entries and f = %d: 1 <= m <= k - f", r->m, r->k,
                   r->f);
-    for (int j = 0; j < r->k; ++j)
-        FLSIM_REQUIRE(r->count[j] >= 1, "Invalid count %d of entry %d: it must be >= 1",
-                      r->count[j], j);
-    return 0;
-}
-
-// [a, a + na) and [b, b + nb) bytes share a byte
-static bool overlaps_bytes(const void* a, long na, const void* b, long nb) {
-    return a && b && (uintptr_t)a < (uintptr_t)b + (uintptr_t)nb &&
-           (uintptr_t)b < (uintptr_t)a + (uintptr_t)na;
+    return check_counts(r->count, r->k);
 }
 
 // ================================================================================================
@@ -2211,9 +2301,7 @@ static bool overlaps_bytes(const void* a, long na, const void* b, long nb) {
 // host)
 // ================================================================================================
 struct GeomedDistArgs {
-    const float* ent[RULE_MAX_ARR];     // bucket / class sums; nullptr = an all-zero entry
-    float cnt[RULE_MAX_ARR];            // x_j = ent[j][e] / cnt[j], as k_robust forms it
-    float rcnt[RULE_MAX_ARR];
+    EntryTable T;                       // x_j = ent[j][e] / cnt[j], as k_robust forms it
     double w0[RULE_MAX_ARR];            // pair 0: w^(0) of "every entry alive" (the host's, fp64)
     const double* w;                    // later pairs: s->w, written by the finish launches
     const int32_t* state;               // later pairs: the dead flags [k], then the control words
@@ -2252,6 +2340,88 @@ typedef const double __attribute__((address_space(4)))* GeomedConstF64;
 // dead entry is not loaded (its sum is ignored by the finish launch).
 typedef const float __attribute__((address_space(1)))* GeomedGlobalF32;
 
+// The distance kernels' table in LDS (k_geomed_dist, k_cclip_dist), written by wave 0 (lane j is
+// entry j) and followed by the block's barrier: the address loaded for entry j (its own, or for an
+// entry that is not loaded the first loaded one's), its weight weight(j), count and reciprocal,
+// and the mask of the loaded entries, which is returned.  Unless PAIR0 an entry with dead[j] set
+// is not loaded.
+template <int KPAD, bool PAIR0, class WF>
+__device__ __forceinline__ uint64_t dist_table(const EntryTable& T, int k, const int32_t* dead,
+                                               WF&& weight, unsigned long long* s_ent, double* s_w,
+                                               float* s_cnt, float* s_rcnt,
+                                               unsigned long long* s_mask) {
+    const int j = threadIdx.x;
+    if (j < 64) {
+        const float* src = nullptr;
+        double w = 0.0;
+        float c = 1.f, rc = 1.f;
+        if (j < k) {
+            src = T.ent[j];
+            c = T.cnt[j];
+            rc = T.rcnt[j];
+            w = weight(j);
+            if constexpr (!PAIR0) {
+                if (dead[j]) src = nullptr;
+            }
+        }
+        const unsigned long long ml = __ballot(src != nullptr);
+        const int first = ml ? __builtin_ctzll(ml) : 0;
+        const unsigned long long any = __shfl((unsigned long long)(uintptr_t)src, first, 64);
+        if (j < KPAD) {
+            s_ent[j] = src ? (unsigned long long)(uintptr_t)src : any;
+            s_w[j] = w;
+            s_cnt[j] = c;
+            s_rcnt[j] = rc;
+        }
+        if (j == 0) *s_mask = ml;
+    }
+    __syncthreads();
+    // launch-uniform: a scalar register pair, tested by scalar bit compares
+    return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(*s_mask >> 32)) << 32) |
+           (uint32_t)__builtin_amdgcn_readfirstlane((int)*s_mask);
+}
+
+// The distance kernels' end: each of the thread's k sums is added over the wave by a butterfly
+// and over the four waves as (w0 + w1) + (w2 + w3), a fixed order, and written slot-major; PAIR0:
+// the threads' "held a NaN or an inf" masks are OR-ed over the block into slot k.
+template <int KPAD, bool PAIR0>
+__device__ __forceinline__ void dist_reduce(const double (&acc)[KPAD], uint32_t bad_lo,
+                                            uint32_t bad_hi, int k, double* partials) {
+    __shared__ double red[4][KPAD + 1];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int j = 0; j < KPAD; ++j) {
+        if (j < k) {
+            double a = acc[j];
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
+            if (lane == 0) red[wave][j] = a;
+        }
+    }
+    if constexpr (PAIR0) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            bad_lo |= (uint32_t)__shfl_xor((int)bad_lo, o, 64);
+            bad_hi |= (uint32_t)__shfl_xor((int)bad_hi, o, 64);
+        }
+        if (lane == 0)
+            red[wave][KPAD] = __builtin_bit_cast(double, ((uint64_t)bad_hi << 32) | bad_lo);
+    }
+    __syncthreads();
+    const int t = threadIdx.x;
+    if (t < k)
+        partials[(long)t * gridDim.x + blockIdx.x] =
+            (red[0][t] + red[1][t]) + (red[2][t] + red[3][t]);
+    if constexpr (PAIR0) {
+        if (t == 64) {
+            uint64_t mk = 0;
+#pragma unroll
+            for (int w = 0; w < 4; ++w) mk |= __builtin_bit_cast(uint64_t, red[w][KPAD]);
+            reinterpret_cast<uint64_t*>(partials)[(long)k * gridDim.x + blockIdx.x] = mk;
+        }
+    }
+}
+
 template <int KPAD, bool PAIR0>
 __global__ void __launch_bounds__(256) k_geomed_dist(GeomedDistArgs A) {
 #pragma clang fp contract(off)
@@ -2261,45 +2431,18 @@ __global__ void __launch_bounds__(256) k_geomed_dist(GeomedDistArgs A) {
     __shared__ double s_w[KPAD];
     __shared__ float s_cnt[KPAD], s_rcnt[KPAD];
     __shared__ unsigned long long s_mask;       // bit j: entry j is loaded
-    {
-        int it = 0;
-        if constexpr (!PAIR0) {
-            it = A.pair - A.state[A.k + GEOMED_ST_REDO];
-            if (it >= A.iters) return;
-        }
-        const int j = threadIdx.x;
-        if (j < 64) {                           // (wave 0: lane j is entry j)
-            const float* src = nullptr;
-            double w = 0.0;
-            float c = 1.f, rc = 1.f;
-            if (j < A.k) {
-                src = A.ent[j];
-                c = A.cnt[j];
-                rc = A.rcnt[j];
-                if constexpr (PAIR0) {
-                    w = A.w0[j];
-                } else {
-                    w = A.w[(long)it * A.k + j];
-                    if (A.state[j]) src = nullptr;
-                }
-            }
-            const unsigned long long ml = __ballot(src != nullptr);
-            const int first = ml ? __builtin_ctzll(ml) : 0;
-            const unsigned long long any = __shfl((unsigned long long)(uintptr_t)src, first, 64);
-            if (j < KPAD) {
-                s_ent[j] = src ? (unsigned long long)(uintptr_t)src : any;
-                s_w[j] = w;
-                s_cnt[j] = c;
-                s_rcnt[j] = rc;
-            }
-            if (j == 0) s_mask = ml;
-        }
-        __syncthreads();
+    int it = 0;
+    if constexpr (!PAIR0) {
+        it = A.pair - A.state[A.k + GEOMED_ST_REDO];
+        if (it >= A.iters) return;
     }
-    // launch-uniform: a scalar register pair, tested by scalar bit compares
-    const uint64_t ld_mask =
-        ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(s_mask >> 32)) << 32) |
-        (uint32_t)__builtin_amdgcn_readfirstlane((int)s_mask);
+    const uint64_t ld_mask = dist_table<KPAD, PAIR0>(
+        A.T, A.k, A.state,
+        [&](int j) {
+            if constexpr (PAIR0) return A.w0[j];
+            else return A.w[(long)it * A.k + j];
+        },
+        s_ent, s_w, s_cnt, s_rcnt, &s_mask);
     double acc[KPAD];
 #pragma unroll
     for (int j = 0; j < KPAD; ++j) acc[j] = 0.0;
@@ -2381,39 +2524,7 @@ __global__ void __launch_bounds__(256) k_geomed_dist(GeomedDistArgs A) {
             }
         }
     }
-    __shared__ double red[4][KPAD + 1];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int j = 0; j < KPAD; ++j) {
-        if (j < A.k) {
-            double a = acc[j];
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
-            if (lane == 0) red[wave][j] = a;
-        }
-    }
-    if constexpr (PAIR0) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            bad_lo |= (uint32_t)__shfl_xor((int)bad_lo, o, 64);
-            bad_hi |= (uint32_t)__shfl_xor((int)bad_hi, o, 64);
-        }
-        if (lane == 0)
-            red[wave][KPAD] = __builtin_bit_cast(double, ((uint64_t)bad_hi << 32) | bad_lo);
-    }
-    __syncthreads();
-    const int t = threadIdx.x;
-    if (t < A.k)
-        A.partials[(long)t * gridDim.x + blockIdx.x] =
-            (red[0][t] + red[1][t]) + (red[2][t] + red[3][t]);
-    if constexpr (PAIR0) {
-        if (t == 64) {
-            uint64_t mk = 0;
-#pragma unroll
-            for (int w = 0; w < 4; ++w) mk |= __builtin_bit_cast(uint64_t, red[w][KPAD]);
-            reinterpret_cast<uint64_t*>(A.partials)[(long)A.k * gridDim.x + blockIdx.x] = mk;
-        }
-    }
+    dist_reduce<KPAD, PAIR0>(acc, bad_lo, bad_hi, A.k, A.partials);
 }
 
 struct GeomedFinArgs {
@@ -2506,40 +2617,36 @@ __global__ void __launch_bounds__(GEOMED_FIN_THREADS) k_geomed_finish(GeomedFinA
 }
 
 struct GeomedApplyArgs {
-    const float* ent[RULE_MAX_ARR];
-    float cnt[RULE_MAX_ARR];
-    float rcnt[RULE_MAX_ARR];
+    EntryTable T;
+    ApplyOut O;
     const double* w;                    // w^(iters) (device memory, written by a finish launch)
-    float* g_out;                       // nullable: g is also written here
-    float* G;                           // OK_GOUT, nullable: the clipped step's G
-    double* partials;                   // OK_GOUT, nullable: block b's sum of g * g (fp64)
-    float* p;
-    float* m;
-    float* v;
-    long P;
     int k;
-    AdamConst ac;
-    OptConst oc;
 };
 static_assert(sizeof(GeomedApplyArgs) <= 4096, "kernel argument block");
 
 // One thread owns one element, as k_krum_apply.  The weights are launch-uniform scalar loads;
 // an entry of weight 0 (a dead one) is not loaded, eight loads in flight.  z as _wsum forms it
 // (k_geomed_dist), g = (float)z: one fp64 -> fp32 rounding.  Then the update of kind OK, or
-// OK_GOUT as k_robust.
+// OK_GOUT.
+// This kernel keeps its own copy of two shared pieces, both measured (profiles/bucket_step/
+// README.md).  The head and tail are ApplyElem's, text for text: with ApplyElem the OK_GOUT
+// instantiation is 1 us (2 %) slower at k = 9.  The loop over the entries is k_cclip_apply's,
+// text for text: as a shared __forceinline__ function it costs both kernels 8 VGPRs and 14
+// branches (the table then reaches the loop through a reference to the kernel argument).
 template <int OK>
 __global__ void __launch_bounds__(256) k_geomed_apply(GeomedApplyArgs A) {
 #pragma clang fp contract(off)
     constexpr bool HAS_M = opt_n_state(OK) >= 1, HAS_V = opt_n_state(OK) == 2;
+    const ApplyOut& O = A.O;
     const long e = (long)blockIdx.x * 256 + threadIdx.x;
-    const bool live = e < A.P;
+    const bool live = e < O.P;
     if constexpr (OK != OK_GOUT) {
         if (!live) return;
     }
     float p = 0.f, m = 0.f, v = 0.f;
-    if constexpr (OK != OK_GOUT) p = __builtin_nontemporal_load(A.p + e);
-    if constexpr (HAS_M) m = __builtin_nontemporal_load(A.m + e);
-    if constexpr (HAS_V) v = __builtin_nontemporal_load(A.v + e);
+    if constexpr (OK != OK_GOUT) p = __builtin_nontemporal_load(O.p + e);
+    if constexpr (HAS_M) m = __builtin_nontemporal_load(O.m + e);
+    if constexpr (HAS_V) v = __builtin_nontemporal_load(O.v + e);
     GeomedConstF64 wdev = (GeomedConstF64)(uintptr_t)A.w;
     double z = 0.0;
     bool have = false;
@@ -2554,10 +2661,10 @@ __global__ void __launch_bounds__(256) k_geomed_apply(GeomedApplyArgs A) {
             w[u] = 0.0;
             if (j0 + u < A.k) {
                 const int j = j0 + u;
-                const float* src = A.ent[j];
+                const float* src = A.T.ent[j];
                 w[u] = wdev[j];
-                c[u] = A.cnt[j];
-                rc[u] = A.rcnt[j];
+                c[u] = A.T.cnt[j];
+                rc[u] = A.T.rcnt[j];
                 if (geomed_nonzero(w[u]) && src && live) x[u] = __builtin_nontemporal_load(src + e);
             }
         }
@@ -2573,54 +2680,21 @@ __global__ void __launch_bounds__(256) k_geomed_apply(GeomedApplyArgs A) {
     const float g = (float)z;
     if constexpr (OK == OK_GOUT) {
         if (live) {
-            if (A.g_out) __builtin_nontemporal_store(g, A.g_out + e);
-            if (A.G) __builtin_nontemporal_store(g, A.G + e);
+            if (O.g_out) __builtin_nontemporal_store(g, O.g_out + e);
+            if (O.G) __builtin_nontemporal_store(g, O.G + e);
         }
-        if (A.partials) {
+        if (O.partials) {
             __shared__ double red[4];
             const double s = block_sum_f64(live ? (double)g * (double)g : 0.0, red);
-            if (threadIdx.x == 0) A.partials[blockIdx.x] = s;
+            if (threadIdx.x == 0) O.partials[blockIdx.x] = s;
         }
     } else {
-        if (A.g_out) __builtin_nontemporal_store(g, A.g_out + e);
-        opt_update<OK>(A.ac, A.oc, g, p, m, v);
-        __builtin_nontemporal_store(p, A.p + e);
-        if constexpr (HAS_M) __builtin_nontemporal_store(m, A.m + e);
-        if constexpr (HAS_V) __builtin_nontemporal_store(v, A.v + e);
+        if (O.g_out) __builtin_nontemporal_store(g, O.g_out + e);
+        opt_update<OK>(O.ac, O.oc, g, p, m, v);
+        __builtin_nontemporal_store(p, O.p + e);
+        if constexpr (HAS_M) __builtin_nontemporal_store(m, O.m + e);
+        if constexpr (HAS_V) __builtin_nontemporal_store(v, O.v + e);
     }
-}
-
-template <int KPAD>
-static void launch_geomed_dist(bool pair0, dim3 grid, hipStream_t stream, const ProbeSlot& ps,
-                               const GeomedDistArgs& A) {
-    if (pair0)
-        hipExtLaunchKernelGGL((k_geomed_dist<KPAD, true>), grid, dim3(256), 0, stream, ps.start,
-                              ps.stop, 0, A);
-    else
-        hipExtLaunchKernelGGL((k_geomed_dist<KPAD, false>), grid, dim3(256), 0, stream, ps.start,
-                              ps.stop, 0, A);
-}
-
-static void launch_geomed_apply(int ok, dim3 grid, hipStream_t stream, const ProbeSlot& ps,
-                                const GeomedApplyArgs& A) {
-#define FLSIM_GEOMED_CASE(K)                                                                     \
-    case K:                                                                                      \
-        hipExtLaunchKernelGGL((k_geomed_apply<K>), grid, dim3(256), 0, stream, ps.start, ps.stop, \
-                              0, A);                                                             \
-        break;
-    switch (ok) {
-        FLSIM_GEOMED_CASE(OK_ADAM)
-        FLSIM_GEOMED_CASE(OK_ADAMD)
-        FLSIM_GEOMED_CASE(OK_SGDM)
-        FLSIM_GEOMED_CASE(OK_GOUT)
-        FLSIM_GEOMED_CASE(OK_ADAGRAD)
-        FLSIM_GEOMED_CASE(OK_YOGI)
-        default:
-            hipExtLaunchKernelGGL((k_geomed_apply<OK_SGD>), grid, dim3(256), 0, stream, ps.start,
-                                  ps.stop, 0, A);
-            break;
-    }
-#undef FLSIM_GEOMED_CASE
 }
 
 // flsim_geomed's hyper-parameters; before any pointer check, like check_optim
@@ -2634,10 +2708,7 @@ static int check_geomed(const flsim_geomed* r) {
                   "Invalid nu = %g: it must be finite and > 0", r->nu);
     FLSIM_REQUIRE(r->weighted == 0 || r->weighted == 1,
                   "Invalid weighted = %d: 0 (uniform) or 1 (count)", r->weighted);
-    for (int j = 0; j < r->k; ++j)
-        FLSIM_REQUIRE(r->count[j] >= 1, "Invalid count %d of entry %d: it must be >= 1",
-                      r->count[j], j);
-    return 0;
+    return check_counts(r->count, r->k);
 }
 
 // ================================================================================================
@@ -2858,10 +2929,8 @@ static void attack_eval_host(const flsim_attack* a, int kh, float* b_out, long P
 // is csrc/geomed.h's)
 // ================================================================================================
 struct CclipDistArgs {
-    const float* ent[RULE_MAX_ARR];     // bucket / class sums; nullptr = an all-zero entry
-    float cnt[RULE_MAX_ARR];            // x_j = ent[j][e] / cnt[j], as k_robust forms it
-    float rcnt[RULE_MAX_ARR];
-    const float* center;                // [P]; not read by a FRESH launch
+    EntryTable T;                       // x_j = ent[j][e] / cnt[j], as k_robust forms it
+    const float* center;               // [P]; not read by a FRESH launch
     const double* u;                    // later pairs: s->u, written by the finish launches
     const double* w;                    // later pairs: s->w
     const int32_t* state;               // later pairs: the dead flags [k]
@@ -2893,43 +2962,18 @@ __global__ void __launch_bounds__(256) k_cclip_dist(CclipDistArgs A) {
     __shared__ float s_cnt[KPAD], s_rcnt[KPAD];
     __shared__ unsigned long long s_mask;       // bit j: entry j is loaded
     __shared__ double s_u;
-    {
-        const int j = threadIdx.x;
-        if (j < 64) {                           // (wave 0: lane j is entry j)
-            const float* src = nullptr;
-            double w = 0.0;
-            float c = 1.f, rc = 1.f;
-            if (j < A.k) {
-                src = A.ent[j];
-                c = A.cnt[j];
-                rc = A.rcnt[j];
-                if constexpr (!PAIR0) {
-                    w = A.w[(long)A.pair * A.k + j];
-                    if (A.state[j]) src = nullptr;
-                }
-            }
-            const unsigned long long ml = __ballot(src != nullptr);
-            const int first = ml ? __builtin_ctzll(ml) : 0;
-            const unsigned long long any = __shfl((unsigned long long)(uintptr_t)src, first, 64);
-            if (j < KPAD) {
-                s_ent[j] = src ? (unsigned long long)(uintptr_t)src : any;
-                s_w[j] = w;
-                s_cnt[j] = c;
-                s_rcnt[j] = rc;
-            }
-            if (j == 0) {
-                s_mask = ml;
-                double u = 1.0;
-                if constexpr (!PAIR0) u = A.u[A.pair];
-                s_u = u;
-            }
-        }
-        __syncthreads();
+    if (threadIdx.x == 0) {                     // (before dist_table's barrier)
+        double u = 1.0;
+        if constexpr (!PAIR0) u = A.u[A.pair];
+        s_u = u;
     }
-    // launch-uniform: a scalar register pair, tested by scalar bit compares
-    const uint64_t ld_mask =
-        ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(s_mask >> 32)) << 32) |
-        (uint32_t)__builtin_amdgcn_readfirstlane((int)s_mask);
+    const uint64_t ld_mask = dist_table<KPAD, PAIR0>(
+        A.T, A.k, A.state,
+        [&](int j) {
+            if constexpr (PAIR0) return 0.0;
+            else return A.w[(long)A.pair * A.k + j];
+        },
+        s_ent, s_w, s_cnt, s_rcnt, &s_mask);
     const GeomedGlobalF32 cen = (GeomedGlobalF32)(uintptr_t)A.center;
     double acc[KPAD];
 #pragma unroll
@@ -3062,39 +3106,7 @@ __global__ void __launch_bounds__(256) k_cclip_dist(CclipDistArgs A) {
             }
         }
     }
-    __shared__ double red[4][KPAD + 1];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int j = 0; j < KPAD; ++j) {
-        if (j < A.k) {
-            double a = acc[j];
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
-            if (lane == 0) red[wave][j] = a;
-        }
-    }
-    if constexpr (PAIR0) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            bad_lo |= (uint32_t)__shfl_xor((int)bad_lo, o, 64);
-            bad_hi |= (uint32_t)__shfl_xor((int)bad_hi, o, 64);
-        }
-        if (lane == 0)
-            red[wave][KPAD] = __builtin_bit_cast(double, ((uint64_t)bad_hi << 32) | bad_lo);
-    }
-    __syncthreads();
-    const int t = threadIdx.x;
-    if (t < A.k)
-        A.partials[(long)t * gridDim.x + blockIdx.x] =
-            (red[0][t] + red[1][t]) + (red[2][t] + red[3][t]);
-    if constexpr (PAIR0) {
-        if (t == 64) {
-            uint64_t mk = 0;
-#pragma unroll
-            for (int w = 0; w < 4; ++w) mk |= __builtin_bit_cast(uint64_t, red[w][KPAD]);
-            reinterpret_cast<uint64_t*>(A.partials)[(long)A.k * gridDim.x + blockIdx.x] = mk;
-        }
-    }
+    dist_reduce<KPAD, PAIR0>(acc, bad_lo, bad_hi, A.k, A.partials);
 }
 
 struct CclipFinArgs {
@@ -3179,42 +3191,34 @@ __global__ void __launch_bounds__(GEOMED_FIN_THREADS) k_cclip_finish(CclipFinArg
 }
 
 struct CclipApplyArgs {
-    const float* ent[RULE_MAX_ARR];
-    float cnt[RULE_MAX_ARR];
-    float rcnt[RULE_MAX_ARR];
+    EntryTable T;
+    ApplyOut O;
     const double* u;                    // &u[iters] (device memory, written by a finish launch)
     const double* w;                    // w[iters]
     float* center;                      // read (unless fresh or u = +-0), then g
-    float* g_out;                       // nullable: g is also written here
-    float* G;                           // OK_GOUT, nullable: the clipped step's G
-    double* partials;                   // OK_GOUT, nullable: block b's sum of g * g (fp64)
-    float* p;
-    float* m;
-    float* v;
-    long P;
     int k, fresh;
-    AdamConst ac;
-    OptConst oc;
 };
 static_assert(sizeof(CclipApplyArgs) <= 4096, "kernel argument block");
 
 // One thread owns one element, as k_geomed_apply: z as _wsum forms it over the center (first; not
 // loaded when fresh or while its weight is +-0) and the entries of non-zero weight, g = (float)z,
 // center[e] = g (the unclipped g; the element's only reader is this thread, before the store),
-// then the update of kind OK, or OK_GOUT as k_robust.
+// then the update of kind OK, or OK_GOUT.  Like k_geomed_apply it keeps its own copy of the head and
+// tail and of the loop over the entries, for the same measured reasons (its comment).
 template <int OK>
 __global__ void __launch_bounds__(256) k_cclip_apply(CclipApplyArgs A) {
 #pragma clang fp contract(off)
     constexpr bool HAS_M = opt_n_state(OK) >= 1, HAS_V = opt_n_state(OK) == 2;
+    const ApplyOut& O = A.O;
     const long e = (long)blockIdx.x * 256 + threadIdx.x;
-    const bool live = e < A.P;
+    const bool live = e < O.P;
     if constexpr (OK != OK_GOUT) {
         if (!live) return;
     }
     float p = 0.f, m = 0.f, v = 0.f;
-    if constexpr (OK != OK_GOUT) p = __builtin_nontemporal_load(A.p + e);
-    if constexpr (HAS_M) m = __builtin_nontemporal_load(A.m + e);
-    if constexpr (HAS_V) v = __builtin_nontemporal_load(A.v + e);
+    if constexpr (OK != OK_GOUT) p = __builtin_nontemporal_load(O.p + e);
+    if constexpr (HAS_M) m = __builtin_nontemporal_load(O.m + e);
+    if constexpr (HAS_V) v = __builtin_nontemporal_load(O.v + e);
     GeomedConstF64 wdev = (GeomedConstF64)(uintptr_t)A.w;
     GeomedConstF64 udev = (GeomedConstF64)(uintptr_t)A.u;
     double z = 0.0;
@@ -3238,10 +3242,10 @@ __global__ void __launch_bounds__(256) k_cclip_apply(CclipApplyArgs A) {
             w[u] = 0.0;
             if (j0 + u < A.k) {
                 const int j = j0 + u;
-                const float* src = A.ent[j];
+                const float* src = A.T.ent[j];
                 w[u] = wdev[j];
-                c[u] = A.cnt[j];
-                rc[u] = A.rcnt[j];
+                c[u] = A.T.cnt[j];
+                rc[u] = A.T.rcnt[j];
                 if (geomed_nonzero(w[u]) && src && live) x[u] = __builtin_nontemporal_load(src + e);
             }
         }
@@ -3258,21 +3262,21 @@ __global__ void __launch_bounds__(256) k_cclip_apply(CclipApplyArgs A) {
     if constexpr (OK == OK_GOUT) {
         if (live) {
             __builtin_nontemporal_store(g, A.center + e);
-            if (A.g_out) __builtin_nontemporal_store(g, A.g_out + e);
-            if (A.G) __builtin_nontemporal_store(g, A.G + e);
+            if (O.g_out) __builtin_nontemporal_store(g, O.g_out + e);
+            if (O.G) __builtin_nontemporal_store(g, O.G + e);
         }
-        if (A.partials) {
+        if (O.partials) {
             __shared__ double red[4];
             const double s = block_sum_f64(live ? (double)g * (double)g : 0.0, red);
-            if (threadIdx.x == 0) A.partials[blockIdx.x] = s;
+            if (threadIdx.x == 0) O.partials[blockIdx.x] = s;
         }
     } else {
         __builtin_nontemporal_store(g, A.center + e);
-        if (A.g_out) __builtin_nontemporal_store(g, A.g_out + e);
-        opt_update<OK>(A.ac, A.oc, g, p, m, v);
-        __builtin_nontemporal_store(p, A.p + e);
-        if constexpr (HAS_M) __builtin_nontemporal_store(m, A.m + e);
-        if constexpr (HAS_V) __builtin_nontemporal_store(v, A.v + e);
+        if (O.g_out) __builtin_nontemporal_store(g, O.g_out + e);
+        opt_update<OK>(O.ac, O.oc, g, p, m, v);
+        __builtin_nontemporal_store(p, O.p + e);
+        if constexpr (HAS_M) __builtin_nontemporal_store(m, O.m + e);
+        if constexpr (HAS_V) __builtin_nontemporal_store(v, O.v + e);
     }
 }
 
@@ -3289,28 +3293,6 @@ static void launch_cclip_dist(bool pair0, bool fresh, dim3 grid, hipStream_t str
 #undef FLSIM_CCLIP_DIST
 }
 
-static void launch_cclip_apply(int ok, dim3 grid, hipStream_t stream, const ProbeSlot& ps,
-                               const CclipApplyArgs& A) {
-#define FLSIM_CCLIP_CASE(K)                                                                      \
-    case K:                                                                                      \
-        hipExtLaunchKernelGGL((k_cclip_apply<K>), grid, dim3(256), 0, stream, ps.start, ps.stop, \
-                              0, A);                                                             \
-        break;
-    switch (ok) {
-        FLSIM_CCLIP_CASE(OK_ADAM)
-        FLSIM_CCLIP_CASE(OK_ADAMD)
-        FLSIM_CCLIP_CASE(OK_SGDM)
-        FLSIM_CCLIP_CASE(OK_GOUT)
-        FLSIM_CCLIP_CASE(OK_ADAGRAD)
-        FLSIM_CCLIP_CASE(OK_YOGI)
-        default:
-            hipExtLaunchKernelGGL((k_cclip_apply<OK_SGD>), grid, dim3(256), 0, stream, ps.start,
-                                  ps.stop, 0, A);
-            break;
-    }
-#undef FLSIM_CCLIP_CASE
-}
-
 // flsim_cclip's hyper-parameters; before any pointer check, like check_optim
 static int check_cclip(const flsim_cclip* r) {
     FLSIM_REQUIRE(r, "null centered-clipping rule");
@@ -3325,10 +3307,7 @@ static int check_cclip(const flsim_cclip* r) {
     FLSIM_REQUIRE(r->fresh == 0 || r->fresh == 1,
                   "Invalid fresh = %d: 0 (the center is read) or 1 (it counts as all zero)",
                   r->fresh);
-    for (int j = 0; j < r->k; ++j)
-        FLSIM_REQUIRE(r->count[j] >= 1, "Invalid count %d of entry %d: it must be >= 1",
-                      r->count[j], j);
-    return 0;
+    return check_counts(r->count, r->k);
 }
 
 }  // namespace flsim
@@ -3739,95 +3718,26 @@ int flsim_robust_optim_step(const flsim_robust* r, const flsim_clip* clip, float
                             float* m, float* v, long P, long step, const flsim_optim* optim,
                             hipStream_t stream) {
     RC(check_robust(r));
-    if (optim) RC(check_optim(optim));
-    RC(check_clip(clip));
-    FLSIM_REQUIRE(optim || (g_out && !clip), "null optimizer (only a step that writes g_out alone, "
-                  "unclipped, takes none)");
-    OptLaunch ol{};
-    ol.ok = OK_GOUT;
-    int nstate = 0;
-    if (optim) {
-        nstate = optim_n_state(optim);
-        RC(make_opt_launch(optim, 1.0, step, &ol));
-        FLSIM_REQUIRE(p && (m || nstate < 1) && (v || nstate < 2), "null pointer");
-    } else {
-        p = nullptr;
-    }
-    if (nstate < 2) v = nullptr;
-    if (nstate < 1) m = nullptr;
-    FLSIM_REQUIRE(P > 0 && P < (1L << 31), "P = %ld out of range", P);
-    FLSIM_REQUIRE((((uintptr_t)p | (uintptr_t)m | (uintptr_t)v | (uintptr_t)g_out) & 15) == 0,
-                  "p/m/v/g_out must be 16-byte aligned");
-    const float* const outs[] = {p, m, v, g_out};
-    for (int a = 0; a < 4; ++a)
-        for (int b = a + 1; b < 4; ++b)
-            FLSIM_REQUIRE(!overlaps(outs[a], outs[b], P), "p/m/v/g_out overlap each other");
-    long n_part = 0;
-    if (clip) {
-        FLSIM_REQUIRE(clip->G && clip->partials && clip->out, "null clip buffer");
-        FLSIM_REQUIRE((((uintptr_t)clip->G | (uintptr_t)clip->partials | (uintptr_t)clip->out) &
-                       15) == 0, "clip G/partials/out must be 16-byte aligned");
-        for (const float* o : outs)
-            FLSIM_REQUIRE(!overlaps(clip->G, o, P), "clip G overlaps p/m/v/g_out");
-    }
+    BucketStep B;
+    RC(step_begin(optim, clip, g_out, p, m, v, P, step, &B));
+    RC(check_clip_buffers(B, nullptr));
     RobustArgs A{};
-    for (int j = 0; j < r->k; ++j) {
-        const float* e = r->entries[j];
-        FLSIM_REQUIRE(((uintptr_t)e & 3) == 0, "entry %d must be 4-byte aligned", j);
-        for (const float* o : outs)
-            FLSIM_REQUIRE(!overlaps(e, o, P), "entry %d overlaps p/m/v/g_out", j);
-        FLSIM_REQUIRE(!clip || !overlaps(e, clip->G, P), "entry %d overlaps clip G", j);
-        A.ent[j] = e;
-        volatile float one = 1.f, c = (float)r->count[j];    // RN(1 / count) in fp32
-        A.cnt[j] = c;
-        A.rcnt[j] = one / c;
-    }
+    int distinct = 0;
+    RC(fill_entries(B, r->entries, r->count, r->k, "", nullptr, 0, nullptr, &A.T, &distinct));
     const int kpad = robust_kpad(r->k);
-    const long nblk = (P + 255) / 256;
-    if (clip) {
-        n_part = nblk;
-        FLSIM_REQUIRE(clip->n_partials >= n_part, "clip n_partials = %ld, this step writes %ld",
-                      clip->n_partials, n_part);
-    }
-    A.g_out = g_out;
-    A.G = clip ? clip->G : nullptr;
-    A.partials = clip ? clip->partials : nullptr;
-    A.p = p;
-    A.m = m;
-    A.v = v;
-    A.P = P;
     A.k = r->k;
     A.kind = r->kind;
     A.trim = r->trim;
     A.fn = (float)(r->k - 2 * r->trim);
-    A.ac = ol.ac;
-    A.oc = ol.oc;
-    const int ok_launch = clip ? (int)OK_GOUT : ol.ok;
-    int distinct = 0;
-    for (int j = 0; j < r->k; ++j) {
-        bool seen = r->entries[j] == nullptr;
-        for (int s = 0; s < j && !seen; ++s) seen = r->entries[s] == r->entries[j];
-        distinct += !seen;
-    }
-    // algorithmic HBM bytes: each distinct entry read once; g_out / G written; p and the kind's
-    // state arrays read + written (not by a launch that only writes g)
-    const int nst_launch = ok_launch == OK_GOUT ? 0 : nstate;
-    const double bytes = 4.0 * (double)P * (distinct + (g_out ? 1 : 0) + (clip ? 1 : 0) +
-                                            (ok_launch == OK_GOUT ? 0 : 2 + 2 * nst_launch));
-    const ProbeSlot ps = probe_begin();
-    const dim3 grid((unsigned)nblk);
-    switch (kpad) {
-        case 2: launch_robust<2>(ok_launch, grid, stream, ps, A); break;
-        case 4: launch_robust<4>(ok_launch, grid, stream, ps, A); break;
-        case 8: launch_robust<8>(ok_launch, grid, stream, ps, A); break;
-        case 16: launch_robust<16>(ok_launch, grid, stream, ps, A); break;
-        case 32: launch_robust<32>(ok_launch, grid, stream, ps, A); break;
-        default: launch_robust<64>(ok_launch, grid, stream, ps, A); break;
-    }
-    FLSIM_LAUNCH_CHECK();
-    if (probe_end(ps, K_ROBUST, bytes)) return 2;
-    if (!clip) return 0;
-    return clip_finish_apply(clip, n_part, ol, p, m, v, P, stream);
+    // the rule's own arrays: each distinct entry read once
+    return launch_apply(B, A, K_ROBUST, distinct, stream,
+                        [&](auto ok, dim3 grid, const ProbeSlot& ps) {
+                            with_kpad<2>(kpad, [&](auto kp) {
+                                hipExtLaunchKernelGGL(
+                                    (k_robust<decltype(kp)::value, decltype(ok)::value>), grid,
+                                    dim3(256), 0, stream, ps.start, ps.stop, 0, A);
+                            });
+                        });
 }
 
 // host (testing): g of the rule text for host pointers, through robust.h's network and select / sum
@@ -3835,14 +3745,9 @@ int flsim_robust_eval_host(const flsim_robust* r, long P, float* g_out) {
     RC(check_robust(r));
     FLSIM_REQUIRE(g_out, "null pointer");
     FLSIM_REQUIRE(P > 0, "P = %ld out of range", P);
-    switch (robust_kpad(r->k)) {
-        case 2: robust_eval_host<2>(r, P, g_out); break;
-        case 4: robust_eval_host<4>(r, P, g_out); break;
-        case 8: robust_eval_host<8>(r, P, g_out); break;
-        case 16: robust_eval_host<16>(r, P, g_out); break;
-        case 32: robust_eval_host<32>(r, P, g_out); break;
-        default: robust_eval_host<64>(r, P, g_out); break;
-    }
+    with_kpad<2>(robust_kpad(r->k), [&](auto kp) {
+        robust_eval_host<decltype(kp)::value>(r, P, g_out);
+    });
     return 0;
 }
 
@@ -3865,29 +3770,9 @@ int flsim_krum_optim_step(const flsim_krum* r, const flsim_krum_scratch* s, cons
                           float* g_out, float* p, float* m, float* v, long P, long step,
                           const flsim_optim* optim, hipStream_t stream) {
     RC(check_krum(r));
-    if (optim) RC(check_optim(optim));
-    RC(check_clip(clip));
-    FLSIM_REQUIRE(optim || (g_out && !clip), "null optimizer (only a step that writes g_out alone, "
-                  "unclipped, takes none)");
-    OptLaunch ol{};
-    ol.ok = OK_GOUT;
-    int nstate = 0;
-    if (optim) {
-        nstate = optim_n_state(optim);
-        RC(make_opt_launch(optim, 1.0, step, &ol));
-        FLSIM_REQUIRE(p && (m || nstate < 1) && (v || nstate < 2), "null pointer");
-    } else {
-        p = nullptr;
-    }
-    if (nstate < 2) v = nullptr;
-    if (nstate < 1) m = nullptr;
-    FLSIM_REQUIRE(P > 0 && P < (1L << 31), "P = %ld out of range", P);
-    FLSIM_REQUIRE((((uintptr_t)p | (uintptr_t)m | (uintptr_t)v | (uintptr_t)g_out) & 15) == 0,
-                  "p/m/v/g_out must be 16-byte aligned");
-    const float* const outs[] = {p, m, v, g_out};
-    for (int a = 0; a < 4; ++a)
-        for (int b = a + 1; b < 4; ++b)
-            FLSIM_REQUIRE(!overlaps(outs[a], outs[b], P), "p/m/v/g_out overlap each other");
+    BucketStep B;
+    RC(step_begin(optim, clip, g_out, p, m, v, P, step, &B));
+    static const char name[] = "Krum";
     FLSIM_REQUIRE(s && s->partials && s->dist && s->score && s->sel, "null Krum scratch");
     FLSIM_REQUIRE((((uintptr_t)s->partials | (uintptr_t)s->dist | (uintptr_t)s->score |
                     (uintptr_t)s->sel) & 15) == 0, "Krum scratch must be 16-byte aligned");
@@ -3896,52 +3781,18 @@ int flsim_krum_optim_step(const flsim_krum* r, const flsim_krum_scratch* s, cons
     const long n_dist = nblocks * krum_npb(kpad) * 16;
     FLSIM_REQUIRE(s->n_partials >= n_dist, "Krum n_partials = %ld, this step writes %ld",
                   s->n_partials, n_dist);
-    const void* const sb[] = {s->partials, s->dist, s->score, s->sel};
-    const long sn[] = {8 * n_dist, 8L * r->k * r->k, 8L * r->k, 4L * r->m};
-    for (int a = 0; a < 4; ++a) {
-        for (int b = a + 1; b < 4; ++b)
-            FLSIM_REQUIRE(!overlaps_bytes(sb[a], sn[a], sb[b], sn[b]),
-                          "Krum scratch buffers overlap each other");
-        for (const float* o : outs)
-            FLSIM_REQUIRE(!overlaps_bytes(sb[a], sn[a], o, 4 * P),
-                          "Krum scratch overlaps p/m/v/g_out");
-        FLSIM_REQUIRE(!clip || !overlaps_bytes(sb[a], sn[a], clip->G, 4 * P),
-                      "Krum scratch overlaps clip G");
-    }
-    long n_part = 0;
-    if (clip) {
-        FLSIM_REQUIRE(clip->G && clip->partials && clip->out, "null clip buffer");
-        FLSIM_REQUIRE((((uintptr_t)clip->G | (uintptr_t)clip->partials | (uintptr_t)clip->out) &
-                       15) == 0, "clip G/partials/out must be 16-byte aligned");
-        for (const float* o : outs)
-            FLSIM_REQUIRE(!overlaps(clip->G, o, P), "clip G overlaps p/m/v/g_out");
-    }
+    constexpr int NS = 4;
+    const Span sc[NS] = {{s->partials, 8 * n_dist},
+                         {s->dist, 8L * r->k * r->k},
+                         {s->score, 8L * r->k},
+                         {s->sel, 4L * r->m}};
+    RC(check_scratch(B, name, sc, NS, nullptr));
+    RC(check_clip_buffers(B, nullptr));
     KrumDistArgs D{};
     KrumApplyArgs A{};
     int distinct = 0;
-    for (int j = 0; j < r->k; ++j) {
-        const float* e = r->entries[j];
-        FLSIM_REQUIRE(((uintptr_t)e & 3) == 0, "entry %d must be 4-byte aligned", j);
-        for (const float* o : outs)
-            FLSIM_REQUIRE(!overlaps(e, o, P), "entry %d overlaps p/m/v/g_out", j);
-        FLSIM_REQUIRE(!clip || !overlaps(e, clip->G, P), "entry %d overlaps clip G", j);
-        for (int a = 0; a < 4; ++a)
-            FLSIM_REQUIRE(!overlaps_bytes(e, 4 * P, sb[a], sn[a]),
-                          "entry %d overlaps the Krum scratch", j);
-        volatile float one = 1.f, c = (float)r->count[j];    // RN(1 / count) in fp32
-        D.ent[j] = A.ent[j] = e;
-        D.cnt[j] = A.cnt[j] = c;
-        D.rcnt[j] = A.rcnt[j] = one / c;
-        bool seen = e == nullptr;
-        for (int q = 0; q < j && !seen; ++q) seen = r->entries[q] == e;
-        distinct += !seen;
-    }
-    const long nblk = (P + 255) / 256;
-    if (clip) {
-        n_part = nblk;
-        FLSIM_REQUIRE(clip->n_partials >= n_part, "clip n_partials = %ld, this step writes %ld",
-                      clip->n_partials, n_part);
-    }
+    RC(fill_entries(B, r->entries, r->count, r->k, name, sc, NS, nullptr, &D.T, &distinct));
+    A.T = D.T;
     D.partials = s->partials;
     D.P = P;
     D.k = r->k;
@@ -3949,13 +3800,11 @@ int flsim_krum_optim_step(const flsim_krum* r, const flsim_krum_scratch* s, cons
     {
         const ProbeSlot ps = probe_begin();
         const dim3 grid((unsigned)nblocks);
-        switch (kpad) {
-            case 4: launch_krum_dist<4>(grid, stream, ps, D); break;
-            case 8: launch_krum_dist<8>(grid, stream, ps, D); break;
-            case 16: launch_krum_dist<16>(grid, stream, ps, D); break;
-            case 32: launch_krum_dist<32>(grid, stream, ps, D); break;
-            default: launch_krum_dist<64>(grid, stream, ps, D); break;
-        }
+        with_kpad<4>(kpad, [&](auto kp) {
+            constexpr int KPAD = decltype(kp)::value;
+            hipExtLaunchKernelGGL((k_krum_dist<KPAD>), grid, dim3(KrumGeom<KPAD>::NT), 0, stream,
+                                  ps.start, ps.stop, 0, D);
+        });
         FLSIM_LAUNCH_CHECK();
         // algorithmic HBM bytes: each distinct entry read once
         if (probe_end(ps, K_KRUM_DIST, 4.0 * (double)P * distinct)) return 2;
@@ -3971,29 +3820,14 @@ int flsim_krum_optim_step(const flsim_krum* r, const flsim_krum_scratch* s, cons
             return 2;
     }
     A.sel = s->sel;
-    A.g_out = g_out;
-    A.G = clip ? clip->G : nullptr;
-    A.partials = clip ? clip->partials : nullptr;
-    A.p = p;
-    A.m = m;
-    A.v = v;
-    A.P = P;
     A.nsel = r->m;
     A.fm = (float)r->m;
-    A.ac = ol.ac;
-    A.oc = ol.oc;
-    const int ok_launch = clip ? (int)OK_GOUT : ol.ok;
-    // algorithmic HBM bytes: the m selected entries read; g_out / G written; p and the kind's
-    // state arrays read + written (not by a launch that only writes g)
-    const int nst_launch = ok_launch == OK_GOUT ? 0 : nstate;
-    const double bytes = 4.0 * (double)P * (r->m + (g_out ? 1 : 0) + (clip ? 1 : 0) +
-                                            (ok_launch == OK_GOUT ? 0 : 2 + 2 * nst_launch));
-    const ProbeSlot ps = probe_begin();
-    launch_krum_apply(ok_launch, dim3((unsigned)nblk), stream, ps, A);
-    FLSIM_LAUNCH_CHECK();
-    if (probe_end(ps, K_KRUM_APPLY, bytes)) return 2;
-    if (!clip) return 0;
-    return clip_finish_apply(clip, n_part, ol, p, m, v, P, stream);
+    // the rule's own arrays: the m selected entries read
+    return launch_apply(B, A, K_KRUM_APPLY, r->m, stream,
+                        [&](auto ok, dim3 grid, const ProbeSlot& ps) {
+                            hipExtLaunchKernelGGL((k_krum_apply<decltype(ok)::value>), grid,
+                                                  dim3(256), 0, stream, ps.start, ps.stop, 0, A);
+                        });
 }
 
 // host (testing): the text for host pointers.  The bucket means by one fp32 division each, every
@@ -4055,29 +3889,9 @@ int flsim_geomed_optim_step(const flsim_geomed* r, const flsim_geomed_scratch* s
                             const flsim_clip* clip, float* g_out, float* p, float* m, float* v,
                             long P, long step, const flsim_optim* optim, hipStream_t stream) {
     RC(check_geomed(r));
-    if (optim) RC(check_optim(optim));
-    RC(check_clip(clip));
-    FLSIM_REQUIRE(optim || (g_out && !clip), "null optimizer (only a step that writes g_out alone, "
-                  "unclipped, takes none)");
-    OptLaunch ol{};
-    ol.ok = OK_GOUT;
-    int nstate = 0;
-    if (optim) {
-        nstate = optim_n_state(optim);
-        RC(make_opt_launch(optim, 1.0, step, &ol));
-        FLSIM_REQUIRE(p && (m || nstate < 1) && (v || nstate < 2), "null pointer");
-    } else {
-        p = nullptr;
-    }
-    if (nstate < 2) v = nullptr;
-    if (nstate < 1) m = nullptr;
-    FLSIM_REQUIRE(P > 0 && P < (1L << 31), "P = %ld out of range", P);
-    FLSIM_REQUIRE((((uintptr_t)p | (uintptr_t)m | (uintptr_t)v | (uintptr_t)g_out) & 15) == 0,
-                  "p/m/v/g_out must be 16-byte aligned");
-    const float* const outs[] = {p, m, v, g_out};
-    for (int a = 0; a < 4; ++a)
-        for (int b = a + 1; b < 4; ++b)
-            FLSIM_REQUIRE(!overlaps(outs[a], outs[b], P), "p/m/v/g_out overlap each other");
+    BucketStep B;
+    RC(step_begin(optim, clip, g_out, p, m, v, P, step, &B));
+    static const char name[] = "geometric-median";
     FLSIM_REQUIRE(s && s->partials && s->w && s->d2 && s->obj && s->state,
                   "null geometric-median scratch");
     FLSIM_REQUIRE((((uintptr_t)s->partials | (uintptr_t)s->w | (uintptr_t)s->d2 |
@@ -4090,59 +3904,26 @@ int flsim_geomed_optim_step(const flsim_geomed* r, const flsim_geomed_scratch* s
     FLSIM_REQUIRE(s->n_partials >= n_dist,
                   "geometric-median n_partials = %ld, this step writes %ld", s->n_partials, n_dist);
     // (a buffer of no bytes -- d2 and obj at iters = 0 -- overlaps nothing)
-    const void* const sb[] = {s->partials, s->w, s->d2, s->obj, s->state};
-    const long sn[] = {8 * n_dist, 8L * (iters + 1) * k, 8L * iters * k, 8L * iters,
-                       4L * (k + GEOMED_ST_WORDS)};
-    for (int a = 0; a < 5; ++a) {
-        if (!sn[a]) continue;
-        for (int b = a + 1; b < 5; ++b)
-            FLSIM_REQUIRE(!sn[b] || !overlaps_bytes(sb[a], sn[a], sb[b], sn[b]),
-                          "geometric-median scratch buffers overlap each other");
-        for (const float* o : outs)
-            FLSIM_REQUIRE(!overlaps_bytes(sb[a], sn[a], o, 4 * P),
-                          "geometric-median scratch overlaps p/m/v/g_out");
-        FLSIM_REQUIRE(!clip || !overlaps_bytes(sb[a], sn[a], clip->G, 4 * P),
-                      "geometric-median scratch overlaps clip G");
-    }
-    long n_part = 0;
-    if (clip) {
-        FLSIM_REQUIRE(clip->G && clip->partials && clip->out, "null clip buffer");
-        FLSIM_REQUIRE((((uintptr_t)clip->G | (uintptr_t)clip->partials | (uintptr_t)clip->out) &
-                       15) == 0, "clip G/partials/out must be 16-byte aligned");
-        for (const float* o : outs)
-            FLSIM_REQUIRE(!overlaps(clip->G, o, P), "clip G overlaps p/m/v/g_out");
-    }
+    constexpr int NS = 5;
+    const Span sc[NS] = {{s->partials, 8 * n_dist},
+                         {s->w, 8L * (iters + 1) * k},
+                         {s->d2, 8L * iters * k},
+                         {s->obj, 8L * iters},
+                         {s->state, 4L * (k + GEOMED_ST_WORDS)}};
+    RC(check_scratch(B, name, sc, NS, nullptr));
+    RC(check_clip_buffers(B, nullptr));
     GeomedDistArgs D{};
     GeomedFinArgs F{};
     GeomedApplyArgs A{};
     int distinct = 0;
+    RC(fill_entries(B, r->entries, r->count, k, name, sc, NS, nullptr, &D.T, &distinct));
+    A.T = D.T;
     double alpha[RULE_MAX_ARR];
     for (int j = 0; j < k; ++j) {
-        const float* e = r->entries[j];
-        FLSIM_REQUIRE(((uintptr_t)e & 3) == 0, "entry %d must be 4-byte aligned", j);
-        for (const float* o : outs)
-            FLSIM_REQUIRE(!overlaps(e, o, P), "entry %d overlaps p/m/v/g_out", j);
-        FLSIM_REQUIRE(!clip || !overlaps(e, clip->G, P), "entry %d overlaps clip G", j);
-        for (int a = 0; a < 5; ++a)
-            FLSIM_REQUIRE(!sn[a] || !overlaps_bytes(e, 4 * P, sb[a], sn[a]),
-                          "entry %d overlaps the geometric-median scratch", j);
-        volatile float one = 1.f, c = (float)r->count[j];    // RN(1 / count) in fp32
-        D.ent[j] = A.ent[j] = e;
-        D.cnt[j] = A.cnt[j] = c;
-        D.rcnt[j] = A.rcnt[j] = one / c;
         F.count[j] = r->count[j];
         alpha[j] = geomed_alpha(r->weighted, r->count[j], 0);
-        bool seen = e == nullptr;
-        for (int q = 0; q < j && !seen; ++q) seen = r->entries[q] == e;
-        distinct += !seen;
     }
     geomed_w0(alpha, k, D.w0);
-    const long nblk = (P + 255) / 256;
-    if (clip) {
-        n_part = nblk;
-        FLSIM_REQUIRE(clip->n_partials >= n_part, "clip n_partials = %ld, this step writes %ld",
-                      clip->n_partials, n_part);
-    }
     D.w = s->w;
     D.state = s->state;
     D.partials = s->partials;
@@ -4165,13 +3946,15 @@ int flsim_geomed_optim_step(const flsim_geomed* r, const flsim_geomed_scratch* s
         {
             const ProbeSlot ps = probe_begin();
             const dim3 grid((unsigned)nblocks);
-            switch (kpad) {
-                case 4: launch_geomed_dist<4>(pair == 0, grid, stream, ps, D); break;
-                case 8: launch_geomed_dist<8>(pair == 0, grid, stream, ps, D); break;
-                case 16: launch_geomed_dist<16>(pair == 0, grid, stream, ps, D); break;
-                case 32: launch_geomed_dist<32>(pair == 0, grid, stream, ps, D); break;
-                default: launch_geomed_dist<64>(pair == 0, grid, stream, ps, D); break;
-            }
+            with_kpad<4>(kpad, [&](auto kp) {
+                constexpr int KPAD = decltype(kp)::value;
+                if (pair == 0)
+                    hipExtLaunchKernelGGL((k_geomed_dist<KPAD, true>), grid, dim3(256), 0, stream,
+                                          ps.start, ps.stop, 0, D);
+                else
+                    hipExtLaunchKernelGGL((k_geomed_dist<KPAD, false>), grid, dim3(256), 0, stream,
+                                          ps.start, ps.stop, 0, D);
+            });
             FLSIM_LAUNCH_CHECK();
             // algorithmic HBM bytes: each distinct entry read once
             if (probe_end(ps, K_GEOMED_DIST, 4.0 * (double)P * distinct)) return 2;
@@ -4184,28 +3967,13 @@ int flsim_geomed_optim_step(const flsim_geomed* r, const flsim_geomed_scratch* s
             return 2;
     }
     A.w = s->w + (long)iters * k;
-    A.g_out = g_out;
-    A.G = clip ? clip->G : nullptr;
-    A.partials = clip ? clip->partials : nullptr;
-    A.p = p;
-    A.m = m;
-    A.v = v;
-    A.P = P;
     A.k = k;
-    A.ac = ol.ac;
-    A.oc = ol.oc;
-    const int ok_launch = clip ? (int)OK_GOUT : ol.ok;
-    // algorithmic HBM bytes: the distinct entries read; g_out / G written; p and the kind's state
-    // arrays read + written (not by a launch that only writes g)
-    const int nst_launch = ok_launch == OK_GOUT ? 0 : nstate;
-    const double bytes = 4.0 * (double)P * (distinct + (g_out ? 1 : 0) + (clip ? 1 : 0) +
-                                            (ok_launch == OK_GOUT ? 0 : 2 + 2 * nst_launch));
-    const ProbeSlot ps = probe_begin();
-    launch_geomed_apply(ok_launch, dim3((unsigned)nblk), stream, ps, A);
-    FLSIM_LAUNCH_CHECK();
-    if (probe_end(ps, K_GEOMED_APPLY, bytes)) return 2;
-    if (!clip) return 0;
-    return clip_finish_apply(clip, n_part, ol, p, m, v, P, stream);
+    // the rule's own arrays: the distinct entries read
+    return launch_apply(B, A, K_GEOMED_APPLY, distinct, stream,
+                        [&](auto ok, dim3 grid, const ProbeSlot& ps) {
+                            hipExtLaunchKernelGGL((k_geomed_apply<decltype(ok)::value>), grid,
+                                                  dim3(256), 0, stream, ps.start, ps.stop, 0, A);
+                        });
 }
 
 // host (testing): the text for host pointers.  The bucket means by one fp32 division each; z as
@@ -4292,13 +4060,9 @@ int flsim_attack_entries(const flsim_attack* a, float* b_out, long P, hipStream_
     A.ntiles = (int)attack_tiles(P, kpad);
     const dim3 grid((unsigned)attack_blocks(P, kpad));
     const ProbeSlot ps = probe_begin();
-    switch (kpad) {
-        case 4: launch_attack<4>(a->kind, grid, stream, ps, A); break;
-        case 8: launch_attack<8>(a->kind, grid, stream, ps, A); break;
-        case 16: launch_attack<16>(a->kind, grid, stream, ps, A); break;
-        case 32: launch_attack<32>(a->kind, grid, stream, ps, A); break;
-        default: launch_attack<64>(a->kind, grid, stream, ps, A); break;
-    }
+    with_kpad<4>(kpad, [&](auto kp) {
+        launch_attack<decltype(kp)::value>(a->kind, grid, stream, ps, A);
+    });
     FLSIM_LAUNCH_CHECK();
     // algorithmic HBM bytes: the honest entries read, the Byzantine-holding ones and b_out written
     if (probe_end(ps, K_ATTACK, 4.0 * (double)P * (nread + nwritten + (b_out ? 1 : 0)))) return 2;
@@ -4336,33 +4100,13 @@ int flsim_cclip_optim_step(const flsim_cclip* r, const flsim_cclip_scratch* s,
                            const flsim_clip* clip, float* g_out, float* p, float* m, float* v,
                            long P, long step, const flsim_optim* optim, hipStream_t stream) {
     RC(check_cclip(r));
-    if (optim) RC(check_optim(optim));
-    RC(check_clip(clip));
-    FLSIM_REQUIRE(optim || (g_out && !clip), "null optimizer (only a step that writes g_out alone, "
-                  "unclipped, takes none)");
-    OptLaunch ol{};
-    ol.ok = OK_GOUT;
-    int nstate = 0;
-    if (optim) {
-        nstate = optim_n_state(optim);
-        RC(make_opt_launch(optim, 1.0, step, &ol));
-        FLSIM_REQUIRE(p && (m || nstate < 1) && (v || nstate < 2), "null pointer");
-    } else {
-        p = nullptr;
-    }
-    if (nstate < 2) v = nullptr;
-    if (nstate < 1) m = nullptr;
-    FLSIM_REQUIRE(P > 0 && P < (1L << 31), "P = %ld out of range", P);
-    FLSIM_REQUIRE((((uintptr_t)p | (uintptr_t)m | (uintptr_t)v | (uintptr_t)g_out) & 15) == 0,
-                  "p/m/v/g_out must be 16-byte aligned");
-    const float* const outs[] = {p, m, v, g_out};
-    for (int a = 0; a < 4; ++a)
-        for (int b = a + 1; b < 4; ++b)
-            FLSIM_REQUIRE(!overlaps(outs[a], outs[b], P), "p/m/v/g_out overlap each other");
+    BucketStep B;
+    RC(step_begin(optim, clip, g_out, p, m, v, P, step, &B));
+    static const char name[] = "centered-clipping";
     float* const center = r->center;
     FLSIM_REQUIRE(center, "null centered-clipping center");
     FLSIM_REQUIRE(((uintptr_t)center & 15) == 0, "centered-clipping center must be 16-byte aligned");
-    for (const float* o : outs)
+    for (const float* o : B.outs)
         FLSIM_REQUIRE(!overlaps(center, o, P), "centered-clipping center overlaps p/m/v/g_out");
     FLSIM_REQUIRE(s && s->partials && s->u && s->w && s->d2 && s->s && s->state,
                   "null centered-clipping scratch");
@@ -4376,59 +4120,18 @@ int flsim_cclip_optim_step(const flsim_cclip* r, const flsim_cclip_scratch* s,
     FLSIM_REQUIRE(s->n_partials >= n_dist,
                   "centered-clipping n_partials = %ld, this step writes %ld", s->n_partials, n_dist);
     constexpr int NS = 6;
-    const void* const sb[NS] = {s->partials, s->u, s->w, s->d2, s->s, s->state};
-    const long sn[NS] = {8 * n_dist, 8L * (iters + 1), 8L * (iters + 1) * k, 8L * iters * k,
-                         8L * iters * k, 4L * (k + CCLIP_ST_WORDS)};
-    for (int a = 0; a < NS; ++a) {
-        for (int b = a + 1; b < NS; ++b)
-            FLSIM_REQUIRE(!overlaps_bytes(sb[a], sn[a], sb[b], sn[b]),
-                          "centered-clipping scratch buffers overlap each other");
-        for (const float* o : outs)
-            FLSIM_REQUIRE(!overlaps_bytes(sb[a], sn[a], o, 4 * P),
-                          "centered-clipping scratch overlaps p/m/v/g_out");
-        FLSIM_REQUIRE(!clip || !overlaps_bytes(sb[a], sn[a], clip->G, 4 * P),
-                      "centered-clipping scratch overlaps clip G");
-        FLSIM_REQUIRE(!overlaps_bytes(sb[a], sn[a], center, 4 * P),
-                      "centered-clipping center overlaps the centered-clipping scratch");
-    }
-    long n_part = 0;
-    if (clip) {
-        FLSIM_REQUIRE(clip->G && clip->partials && clip->out, "null clip buffer");
-        FLSIM_REQUIRE((((uintptr_t)clip->G | (uintptr_t)clip->partials | (uintptr_t)clip->out) &
-                       15) == 0, "clip G/partials/out must be 16-byte aligned");
-        for (const float* o : outs)
-            FLSIM_REQUIRE(!overlaps(clip->G, o, P), "clip G overlaps p/m/v/g_out");
-        FLSIM_REQUIRE(!overlaps(clip->G, center, P), "centered-clipping center overlaps clip G");
-    }
+    const Span sc[NS] = {{s->partials, 8 * n_dist},      {s->u, 8L * (iters + 1)},
+                         {s->w, 8L * (iters + 1) * k},   {s->d2, 8L * iters * k},
+                         {s->s, 8L * iters * k},         {s->state, 4L * (k + CCLIP_ST_WORDS)}};
+    RC(check_scratch(B, name, sc, NS, center));
+    RC(check_clip_buffers(B, center));
     CclipDistArgs D{};
     CclipFinArgs F{};
     CclipApplyArgs A{};
     int distinct = 0;
-    for (int j = 0; j < k; ++j) {
-        const float* e = r->entries[j];
-        FLSIM_REQUIRE(((uintptr_t)e & 3) == 0, "entry %d must be 4-byte aligned", j);
-        for (const float* o : outs)
-            FLSIM_REQUIRE(!overlaps(e, o, P), "entry %d overlaps p/m/v/g_out", j);
-        FLSIM_REQUIRE(!clip || !overlaps(e, clip->G, P), "entry %d overlaps clip G", j);
-        for (int a = 0; a < NS; ++a)
-            FLSIM_REQUIRE(!overlaps_bytes(e, 4 * P, sb[a], sn[a]),
-                          "entry %d overlaps the centered-clipping scratch", j);
-        FLSIM_REQUIRE(!overlaps(e, center, P), "entry %d overlaps the centered-clipping center", j);
-        volatile float one = 1.f, c = (float)r->count[j];    // RN(1 / count) in fp32
-        D.ent[j] = A.ent[j] = e;
-        D.cnt[j] = A.cnt[j] = c;
-        D.rcnt[j] = A.rcnt[j] = one / c;
-        F.count[j] = r->count[j];
-        bool seen = e == nullptr;
-        for (int q = 0; q < j && !seen; ++q) seen = r->entries[q] == e;
-        distinct += !seen;
-    }
-    const long nblk = (P + 255) / 256;
-    if (clip) {
-        n_part = nblk;
-        FLSIM_REQUIRE(clip->n_partials >= n_part, "clip n_partials = %ld, this step writes %ld",
-                      clip->n_partials, n_part);
-    }
+    RC(fill_entries(B, r->entries, r->count, k, name, sc, NS, center, &D.T, &distinct));
+    A.T = D.T;
+    for (int j = 0; j < k; ++j) F.count[j] = r->count[j];
     const bool fresh = r->fresh != 0;
     D.center = center;
     D.u = s->u;
@@ -4453,13 +4156,9 @@ int flsim_cclip_optim_step(const flsim_cclip* r, const flsim_cclip_scratch* s,
         {
             const ProbeSlot ps = probe_begin();
             const dim3 grid((unsigned)nblocks);
-            switch (kpad) {
-                case 4: launch_cclip_dist<4>(pair == 0, fresh, grid, stream, ps, D); break;
-                case 8: launch_cclip_dist<8>(pair == 0, fresh, grid, stream, ps, D); break;
-                case 16: launch_cclip_dist<16>(pair == 0, fresh, grid, stream, ps, D); break;
-                case 32: launch_cclip_dist<32>(pair == 0, fresh, grid, stream, ps, D); break;
-                default: launch_cclip_dist<64>(pair == 0, fresh, grid, stream, ps, D); break;
-            }
+            with_kpad<4>(kpad, [&](auto kp) {
+                launch_cclip_dist<decltype(kp)::value>(pair == 0, fresh, grid, stream, ps, D);
+            });
             FLSIM_LAUNCH_CHECK();
             // algorithmic HBM bytes: each distinct entry and (unless fresh) the center read once
             if (probe_end(ps, K_CCLIP_DIST, 4.0 * (double)P * (distinct + (fresh ? 0 : 1))))
@@ -4475,31 +4174,15 @@ int flsim_cclip_optim_step(const flsim_cclip* r, const flsim_cclip_scratch* s,
     A.u = s->u + iters;
     A.w = s->w + (long)iters * k;
     A.center = center;
-    A.g_out = g_out;
-    A.G = clip ? clip->G : nullptr;
-    A.partials = clip ? clip->partials : nullptr;
-    A.p = p;
-    A.m = m;
-    A.v = v;
-    A.P = P;
     A.k = k;
     A.fresh = fresh;
-    A.ac = ol.ac;
-    A.oc = ol.oc;
-    const int ok_launch = clip ? (int)OK_GOUT : ol.ok;
-    // algorithmic HBM bytes: the distinct entries and (unless fresh) the center read; the center,
-    // g_out / G written; p and the kind's state arrays read + written (not by a launch that only
-    // writes g)
-    const int nst_launch = ok_launch == OK_GOUT ? 0 : nstate;
-    const double bytes = 4.0 * (double)P * (distinct + (fresh ? 1 : 2) + (g_out ? 1 : 0) +
-                                            (clip ? 1 : 0) +
-                                            (ok_launch == OK_GOUT ? 0 : 2 + 2 * nst_launch));
-    const ProbeSlot ps = probe_begin();
-    launch_cclip_apply(ok_launch, dim3((unsigned)nblk), stream, ps, A);
-    FLSIM_LAUNCH_CHECK();
-    if (probe_end(ps, K_CCLIP_APPLY, bytes)) return 2;
-    if (!clip) return 0;
-    return clip_finish_apply(clip, n_part, ol, p, m, v, P, stream);
+    // the rule's own arrays: the distinct entries and (unless fresh) the center read, the center
+    // written
+    return launch_apply(B, A, K_CCLIP_APPLY, distinct + (fresh ? 1 : 2), stream,
+                        [&](auto ok, dim3 grid, const ProbeSlot& ps) {
+                            hipExtLaunchKernelGGL((k_cclip_apply<decltype(ok)::value>), grid,
+                                                  dim3(256), 0, stream, ps.start, ps.stop, 0, A);
+                        });
 }
 
 // host (testing): the text for host pointers.  The bucket means by one fp32 division each; z as

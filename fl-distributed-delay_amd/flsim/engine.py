@@ -906,36 +906,76 @@ def aggregate_rule(S, rule, theta, m, v, step, sizes, lr=1e-3, betas=(0.9, 0.999
         float(betas[1]), float(eps), stream_ptr()))
 
 
-class Robust:
-    """A robust rule over bucket / class sums (flsim_robust, include/flsim.h): kind "median" (the
-    coordinate-wise lower median) or "trimmed_mean" (per coordinate the `trim` lowest and highest
-    values dropped, the rest averaged), over the k = len(entries) values entries[j] / counts[j].
-    entries: flat fp32 device tensors of the same length, or None (an all-zero entry); counts: the
-    number of workers summed into each (>= 1).  flsim/robust.py is the rule's text."""
+class _BucketRule:
+    """What the rules over bucket / class sums share: the entries and their counts, checked as
+    every rule checks them (_what and _kmin: the rule's words in the message), and their fields
+    in the rule's C struct.  center and c_scratch: the rules that have one override them."""
+    _what, _kmin = None, 1
+    center = None
 
-    def __init__(self, kind, trim, entries, counts):
+    def _set_entries(self, entries, counts):
         entries, counts = list(entries), [int(c) for c in counts]
         if len(entries) != len(counts):
             raise ValueError(f"{len(counts)} counts for {len(entries)} entries")
         if len(entries) > MAX_ARRAYS:
-            raise ValueError(f"robust rule over k = {len(entries)} entries (1 .. {MAX_ARRAYS})")
-        self.kind, self.trim = kind, int(trim)
+            raise ValueError(f"{self._what} over k = {len(entries)} entries "
+                             f"({self._kmin} .. {MAX_ARRAYS})")
         self.entries, self.counts = entries, counts     # (the rule keeps the tensors alive)
 
     @property
     def k(self):
         return len(self.entries)
 
-    def c_struct(self):
-        r = FlsimRobust()
-        r.kind = ROBUST_KINDS.get(self.kind, -1)
-        r.trim = self.trim
+    def _fill_entries(self, r):
+        """k, entries[] and count[] of the rule's C struct r; returns r."""
         r.k = len(self.entries)
         for j, (e, c) in enumerate(zip(self.entries, self.counts)):
             r.entries[j] = e.data_ptr() if e is not None else None
             # (an int32 field: a count it cannot hold is refused as the library refuses one < 1)
             r.count[j] = c if -2 ** 31 <= c < 2 ** 31 else 0
         return r
+
+    def c_scratch(self, device, P):
+        return None
+
+
+def _bucket_step(fn, rule, theta, m, v, step, P, lr, betas, eps, optim, clip, g_out):
+    """The call of a bucketed rule's entry point `fn` (after the rule and its scratch, where it has
+    one, every one takes clip, g_out, theta, m, v, P, step, optim and the stream)."""
+    if optim is False:
+        o = None
+    else:
+        o = ctypes.byref((as_optim(optim) if optim is not None else
+                          Optim(lr=lr, betas=tuple(betas), eps=eps)).c_struct())
+    if P is None:
+        P = int((theta if theta is not None else g_out).numel())
+    r = rule.c_struct()
+    dev = next((t.device for t in (theta, g_out, rule.center, *rule.entries) if t is not None),
+               None)
+    s = rule.c_scratch(dev, int(P))
+    c = ctypes.byref(clip.c_struct(dev, int(P))) if clip is not None else None
+    check(getattr(lib(), fn)(
+        ctypes.byref(r), *(() if s is None else (ctypes.byref(s),)), c, ptr(g_out), ptr(theta),
+        ptr(m), ptr(v), int(P), int(step), o, stream_ptr()))
+
+
+class Robust(_BucketRule):
+    """A robust rule over bucket / class sums (flsim_robust, include/flsim.h): kind "median" (the
+    coordinate-wise lower median) or "trimmed_mean" (per coordinate the `trim` lowest and highest
+    values dropped, the rest averaged), over the k = len(entries) values entries[j] / counts[j].
+    entries: flat fp32 device tensors of the same length, or None (an all-zero entry); counts: the
+    number of workers summed into each (>= 1).  flsim/robust.py is the rule's text."""
+    _what = "robust rule"
+
+    def __init__(self, kind, trim, entries, counts):
+        self._set_entries(entries, counts)
+        self.kind, self.trim = kind, int(trim)
+
+    def c_struct(self):
+        r = FlsimRobust()
+        r.kind = ROBUST_KINDS.get(self.kind, -1)
+        r.trim = self.trim
+        return self._fill_entries(r)
 
 
 def robust_step(robust, theta, m, v, step, P=None, lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
@@ -945,22 +985,11 @@ def robust_step(robust, theta, m, v, step, P=None, lr=1e-3, betas=(0.9, 0.999), 
     array.  clip (a Clip): the rule's output is clipped to clip.max_norm before the update.  g_out
     (optional): the rule's output is also written there; optim=False with g_out runs the rule
     alone and touches none of theta / m / v (theta may then be None)."""
-    if optim is False:
-        o = None
-    else:
-        o = ctypes.byref((as_optim(optim) if optim is not None else
-                          Optim(lr=lr, betas=tuple(betas), eps=eps)).c_struct())
-    if P is None:
-        P = int((theta if theta is not None else g_out).numel())
-    r = robust.c_struct()
-    dev = next((t.device for t in (theta, g_out, *robust.entries) if t is not None), None)
-    c = ctypes.byref(clip.c_struct(dev, int(P))) if clip is not None else None
-    check(lib().flsim_robust_optim_step(
-        ctypes.byref(r), c, ptr(g_out), ptr(theta), ptr(m), ptr(v), int(P), int(step), o,
-        stream_ptr()))
+    _bucket_step("flsim_robust_optim_step", robust, theta, m, v, step, P, lr, betas, eps, optim,
+                 clip, g_out)
 
 
-class Krum:
+class Krum(_BucketRule):
     """Krum / Multi-Krum over bucket / class sums (flsim_krum, include/flsim.h): of the k =
     len(entries) values entries[j] / counts[j], the mean of the m whose summed squared distance
     to their k - f - 2 nearest neighbours is lowest (m = 1: Krum).  entries, counts as for Robust.
@@ -969,28 +998,17 @@ class Krum:
     with no synchronisation beyond the stream's order; the next step overwrites them.
     flsim/robust.py is the rule's text."""
     _scratch = {}       # (device, P, k) -> buffers, shared by the objects of a run
+    _what, _kmin = "Krum", 3
 
     def __init__(self, f, m, entries, counts):
-        entries, counts = list(entries), [int(c) for c in counts]
-        if len(entries) != len(counts):
-            raise ValueError(f"{len(counts)} counts for {len(entries)} entries")
-        if len(entries) > MAX_ARRAYS:
-            raise ValueError(f"Krum over k = {len(entries)} entries (3 .. {MAX_ARRAYS})")
+        self._set_entries(entries, counts)
         self.f, self.m = int(f), int(m)
-        self.entries, self.counts = entries, counts     # (the rule keeps the tensors alive)
         self.dist = self.score = self.sel = None
-
-    @property
-    def k(self):
-        return len(self.entries)
 
     def c_struct(self):
         r = FlsimKrum()
-        r.f, r.m, r.k = self.f, self.m, len(self.entries)
-        for j, (e, c) in enumerate(zip(self.entries, self.counts)):
-            r.entries[j] = e.data_ptr() if e is not None else None
-            r.count[j] = c if -2 ** 31 <= c < 2 ** 31 else 0
-        return r
+        r.f, r.m = self.f, self.m
+        return self._fill_entries(r)
 
     def c_scratch(self, device, P):
         """flsim_krum_scratch over this device's scratch for a step over P elements."""
@@ -1020,23 +1038,11 @@ def krum_step(krum, theta, m, v, step, P=None, lr=1e-3, betas=(0.9, 0.999), eps=
               optim=None, clip=None, g_out=None):
     """Krum / Multi-Krum + Adam(lr, betas, eps), or the update rule `optim`, in three launches
     (flsim_krum_optim_step); m / v, clip, g_out and optim=False as robust_step."""
-    if optim is False:
-        o = None
-    else:
-        o = ctypes.byref((as_optim(optim) if optim is not None else
-                          Optim(lr=lr, betas=tuple(betas), eps=eps)).c_struct())
-    if P is None:
-        P = int((theta if theta is not None else g_out).numel())
-    r = krum.c_struct()
-    dev = next((t.device for t in (theta, g_out, *krum.entries) if t is not None), None)
-    s = krum.c_scratch(dev, int(P))
-    c = ctypes.byref(clip.c_struct(dev, int(P))) if clip is not None else None
-    check(lib().flsim_krum_optim_step(
-        ctypes.byref(r), ctypes.byref(s), c, ptr(g_out), ptr(theta), ptr(m), ptr(v), int(P),
-        int(step), o, stream_ptr()))
+    _bucket_step("flsim_krum_optim_step", krum, theta, m, v, step, P, lr, betas, eps, optim, clip,
+                 g_out)
 
 
-class GeoMed:
+class GeoMed(_BucketRule):
     """The geometric median over bucket / class sums by smoothed Weiszfeld iterations
     (flsim_geomed, include/flsim.h; "RFA"): of the k = len(entries) values entries[j] /
     counts[j], `iters` iterations from their alpha-weighted mean, alpha = 1 or (weighted) the
@@ -1046,30 +1052,18 @@ class GeoMed:
     synchronisation beyond the stream's order; the next step overwrites them.
     flsim/robust.py is the rule's text."""
     _scratch = {}       # (device, P, k, iters) -> buffers, shared by the objects of a run
+    _what = "geometric median"
 
     def __init__(self, iters, nu, weighted, entries, counts):
-        entries, counts = list(entries), [int(c) for c in counts]
-        if len(entries) != len(counts):
-            raise ValueError(f"{len(counts)} counts for {len(entries)} entries")
-        if len(entries) > MAX_ARRAYS:
-            raise ValueError(f"geometric median over k = {len(entries)} entries "
-                             f"(1 .. {MAX_ARRAYS})")
+        self._set_entries(entries, counts)
         self.iters, self.nu, self.weighted = int(iters), float(nu), bool(weighted)
-        self.entries, self.counts = entries, counts     # (the rule keeps the tensors alive)
         self.w = self.d2 = self.obj = self.dead = None
-
-    @property
-    def k(self):
-        return len(self.entries)
 
     def c_struct(self):
         r = FlsimGeomed()
-        r.iters, r.weighted, r.k = self.iters, int(self.weighted), len(self.entries)
+        r.iters, r.weighted = self.iters, int(self.weighted)
         r.nu = self.nu
-        for j, (e, c) in enumerate(zip(self.entries, self.counts)):
-            r.entries[j] = e.data_ptr() if e is not None else None
-            r.count[j] = c if -2 ** 31 <= c < 2 ** 31 else 0
-        return r
+        return self._fill_entries(r)
 
     def c_scratch(self, device, P):
         """flsim_geomed_scratch over this device's scratch for a step over P elements."""
@@ -1104,23 +1098,11 @@ def geomed_step(geomed, theta, m, v, step, P=None, lr=1e-3, betas=(0.9, 0.999), 
     """The geometric median (RFA) + Adam(lr, betas, eps), or the update rule `optim`, in
     2 * (iters + 1) + 1 launches (flsim_geomed_optim_step); m / v, clip, g_out and optim=False
     as robust_step."""
-    if optim is False:
-        o = None
-    else:
-        o = ctypes.byref((as_optim(optim) if optim is not None else
-                          Optim(lr=lr, betas=tuple(betas), eps=eps)).c_struct())
-    if P is None:
-        P = int((theta if theta is not None else g_out).numel())
-    r = geomed.c_struct()
-    dev = next((t.device for t in (theta, g_out, *geomed.entries) if t is not None), None)
-    s = geomed.c_scratch(dev, int(P))
-    c = ctypes.byref(clip.c_struct(dev, int(P))) if clip is not None else None
-    check(lib().flsim_geomed_optim_step(
-        ctypes.byref(r), ctypes.byref(s), c, ptr(g_out), ptr(theta), ptr(m), ptr(v), int(P),
-        int(step), o, stream_ptr()))
+    _bucket_step("flsim_geomed_optim_step", geomed, theta, m, v, step, P, lr, betas, eps, optim,
+                 clip, g_out)
 
 
-class CClip:
+class CClip(_BucketRule):
     """Centered clipping over bucket / class sums around a carried center (flsim_cclip,
     include/flsim.h; Karimireddy, He and Jaggi 2021): `iters` iterations of v <- v + sum_j lam_j
     min(1, tau / ||x_j - v||) (x_j - v) from v = center over the k = len(entries) values
@@ -1132,32 +1114,20 @@ class CClip:
     and dead ([k] int32) are device tensors, read with no synchronisation beyond the stream's
     order; the next step overwrites them.  flsim/robust.py is the rule's text."""
     _scratch = {}       # (device, P, k, iters) -> buffers, shared by the objects of a run
+    _what = "centered clipping"
 
     def __init__(self, tau, iters, weighted, entries, counts, center, fresh=False):
-        entries, counts = list(entries), [int(c) for c in counts]
-        if len(entries) != len(counts):
-            raise ValueError(f"{len(counts)} counts for {len(entries)} entries")
-        if len(entries) > MAX_ARRAYS:
-            raise ValueError(f"centered clipping over k = {len(entries)} entries "
-                             f"(1 .. {MAX_ARRAYS})")
+        self._set_entries(entries, counts)
         self.tau, self.iters, self.weighted = float(tau), int(iters), bool(weighted)
-        self.entries, self.counts = entries, counts     # (the rule keeps the tensors alive)
         self.center, self.fresh = center, bool(fresh)
         self.u = self.w = self.d2 = self.s = self.dead = None
 
-    @property
-    def k(self):
-        return len(self.entries)
-
     def c_struct(self):
         r = FlsimCclip()
-        r.iters, r.weighted, r.k = self.iters, int(self.weighted), len(self.entries)
+        r.iters, r.weighted = self.iters, int(self.weighted)
         r.fresh, r.tau = int(self.fresh), self.tau
-        for j, (e, c) in enumerate(zip(self.entries, self.counts)):
-            r.entries[j] = e.data_ptr() if e is not None else None
-            r.count[j] = c if -2 ** 31 <= c < 2 ** 31 else 0
         r.center = self.center.data_ptr() if self.center is not None else None
-        return r
+        return self._fill_entries(r)
 
     def c_scratch(self, device, P):
         """flsim_cclip_scratch over this device's scratch for a step over P elements."""
@@ -1194,21 +1164,8 @@ def cclip_step(cclip, theta, m, v, step, P=None, lr=1e-3, betas=(0.9, 0.999), ep
     """Centered clipping + Adam(lr, betas, eps), or the update rule `optim`, in 2 * iters + 1
     launches (flsim_cclip_optim_step); cclip.center then holds the (unclipped) aggregate.  m / v,
     clip, g_out and optim=False as robust_step."""
-    if optim is False:
-        o = None
-    else:
-        o = ctypes.byref((as_optim(optim) if optim is not None else
-                          Optim(lr=lr, betas=tuple(betas), eps=eps)).c_struct())
-    if P is None:
-        P = int((theta if theta is not None else g_out).numel())
-    r = cclip.c_struct()
-    dev = next((t.device for t in (theta, g_out, cclip.center, *cclip.entries) if t is not None),
-               None)
-    s = cclip.c_scratch(dev, int(P))
-    c = ctypes.byref(clip.c_struct(dev, int(P))) if clip is not None else None
-    check(lib().flsim_cclip_optim_step(
-        ctypes.byref(r), ctypes.byref(s), c, ptr(g_out), ptr(theta), ptr(m), ptr(v), int(P),
-        int(step), o, stream_ptr()))
+    _bucket_step("flsim_cclip_optim_step", cclip, theta, m, v, step, P, lr, betas, eps, optim,
+                 clip, g_out)
 
 
 class Attack:
