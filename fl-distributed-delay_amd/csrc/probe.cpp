@@ -21,7 +21,8 @@ static const char* KNAME[K_COUNT] = {
     "krum_dist", "krum_finish", "krum_apply",
     "geomed_dist", "geomed_finish", "geomed_apply",
     "attack_entries",
-    "cclip_dist", "cclip_finish", "cclip_apply"};
+    "cclip_dist", "cclip_finish", "cclip_apply",
+    "nnm_dist", "nnm_finish", "nnm_mix"};
 
 struct Probe {
     bool on = false;

@@ -26,7 +26,9 @@ enum KernelId {
     K_KRUM_DIST, K_KRUM_FIN, K_KRUM_APPLY, K_GEOMED_DIST, K_GEOMED_FIN, K_GEOMED_APPLY,
     // the Byzantine attack on the entries; the centered-clipping step's launches (distances to the
     // iterate, finish, apply)
-    K_ATTACK, K_CCLIP_DIST, K_CCLIP_FIN, K_CCLIP_APPLY, K_COUNT
+    K_ATTACK, K_CCLIP_DIST, K_CCLIP_FIN, K_CCLIP_APPLY,
+    // nearest-neighbour mixing of the entries (Krum's distance launch, finish + selection, the mix)
+    K_NNM_DIST, K_NNM_FIN, K_NNM_MIX, K_COUNT
 };
 
 // Event pair for the launch that follows (nullptr events when the probe is off or full).  The

@@ -44,6 +44,7 @@
 #include "flsim.h"
 #include "geomed.h"
 #include "krum.h"
+#include "nnm.h"
 #include "probe.h"
 #include "robust.h"
 #include "slabstep.h"
@@ -2924,6 +2925,173 @@ static void attack_eval_host(const flsim_attack* a, int kh, float* b_out, long P
 }
 
 // ================================================================================================
+// Nearest-neighbour mixing of the entries before any rule: Krum's distance launch, finish + the
+// neighbour selection, the mix in place (include/flsim.h: flsim_nnm; csrc/nnm.h: the geometry of
+// the mix, the selection and the element code shared with the host)
+// ================================================================================================
+// One block of KRUM_FIN_THREADS.  The first half is k_krum_finish's, statement for statement: pair
+// (i, j), i < j, belongs to one wave, lane l adds the partials of the blocks l, l + 64, ... in
+// index order, a butterfly adds the 64 lanes, a wave takes four pairs at a time; a NaN sum becomes
+// +inf, the value is mirrored, the diagonal is zero -- so for the same partials the two kernels
+// give the same matrix, bit for bit.  Then csrc/nnm.h's selection on the matrix in LDS: thread i
+// takes row i.
+__global__ void __launch_bounds__(KRUM_FIN_THREADS)
+k_nnm_finish(const double* partials, int nblocks, int nb, int k, int f, double* dist,
+             uint64_t* nbr) {
+    __shared__ double sd[RULE_MAX_ARR * RULE_MAX_ARR];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    constexpr int WAVES = KRUM_FIN_THREADS / 64;
+    constexpr int NLD = 12;
+    static_assert(krum_max_blocks(4) <= 64 * NLD && krum_max_blocks(64) <= 64 * NLD, "NLD");
+    auto lane_sum = [&](int idx) -> double {
+        const int i = idx / k, j = idx - i * k;
+        double a = 0.0;
+        if (idx < k * k && i < j) {
+            const double* src = partials + (long)krum_slot(i, j, nb) * nblocks;
+            double x[NLD];
+#pragma unroll
+            for (int u = 0; u < NLD; ++u) x[u] = lane + 64 * u < nblocks ? src[lane + 64 * u] : 0.0;
+#pragma unroll
+            for (int u = 0; u < NLD; ++u) a = lane + 64 * u < nblocks ? a + x[u] : a;
+        }
+        return a;
+    };
+    auto store = [&](int idx, double a) {
+        const int i = idx / k, j = idx - i * k;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
+        if (lane == 0 && idx < k * k && i <= j) {
+            a = a != a ? (double)__builtin_inff() : a;
+            sd[i * k + j] = a;                  // (the diagonal: no partial was added, 0)
+            sd[j * k + i] = a;
+        }
+    };
+    for (int base = wave; base < k * k; base += 4 * WAVES) {
+        double a[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) a[u] = lane_sum(base + u * WAVES);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) store(base + u * WAVES, a[u]);
+    }
+    __syncthreads();
+    for (int idx = threadIdx.x; idx < k * k; idx += KRUM_FIN_THREADS) dist[idx] = sd[idx];
+    nnm_select(sd, nbr, k, f, (int)threadIdx.x, KRUM_FIN_THREADS);
+}
+
+struct NnmMixArgs {
+    float* ent[RULE_MAX_ARR];           // in: bucket sums; out: the mixed means, in place
+    float cnt[RULE_MAX_ARR];            // (float)count[j] and RN(1 / that), as the EntryTable's
+    float rcnt[RULE_MAX_ARR];
+    const uint64_t* nbr;                // [k] the masks k_nnm_finish wrote (device memory)
+    long P;
+    int k, ntiles;
+    float fn;                           // (float)(k - f): the divisor of every neighbour sum
+};
+static_assert(sizeof(NnmMixArgs) <= 4096, "kernel argument block");
+
+// One streaming pass, the shape of k_attack: thread t of the block's 256 owns the elements
+// u * 256 + t, u < U, of a tile (a wave's load or store is one coalesced 256-byte row) and a block
+// grid-strides over the tiles.  All loads of all k entries for a thread's elements are issued
+// before any arithmetic or store; then the bucket means x_j = ent[j][e] / cnt[j] by div_const as
+// k_robust forms them, and for every i < k the mixed value y_i = nnm_mix_elem (csrc/nnm.h): the
+// neighbours of i added in ascending j, fp32, contraction off, one IEEE division -- stored to
+// ent[i].  In place is safe without any ordering between blocks or threads: every element of
+// every entry is read and written by one thread only, and that thread has all k values of the
+// element in registers before its first store.  The per-entry table (addresses, counts, the
+// neighbour masks: loaded from device memory once, by wave 0) is built in LDS and read by
+// broadcast, as in k_attack; the mask of row i and k are made scalar (readfirstlane), so every
+// test of a mask bit is a wave-uniform scalar branch.  x is indexed by the unrolled j alone and the
+// loop over i indexes only LDS: no register array is indexed at run time (scratch stays 0).  A
+// padding entry loads entry 0's address and an element past P loads element 0: both values are
+// dropped, so every load is in bounds, and nothing is stored past P.
+template <int KPAD>
+__global__ void __launch_bounds__(256) k_nnm_mix(NnmMixArgs A) {
+#pragma clang fp contract(off)
+    constexpr int U = nnm_unroll(KPAD), E = nnm_tile_elems(KPAD);
+    constexpr int GRP = KPAD < 8 ? KPAD : 8;
+    __shared__ unsigned long long s_ent[KPAD];  // the address loaded for entry j
+    __shared__ unsigned long long s_nbr[KPAD];  // the neighbours of entry j
+    __shared__ float s_cnt[KPAD], s_rcnt[KPAD];
+    {
+        const int j = threadIdx.x;
+        if (j < KPAD) {
+            const bool in = j < A.k;
+            s_ent[j] = (unsigned long long)(uintptr_t)(in ? A.ent[j] : A.ent[0]);
+            s_nbr[j] = in ? (unsigned long long)A.nbr[j] : 0ull;
+            s_cnt[j] = in ? A.cnt[j] : 1.f;
+            s_rcnt[j] = in ? A.rcnt[j] : 1.f;
+        }
+        __syncthreads();
+    }
+    for (int tl = blockIdx.x; tl < A.ntiles; tl += gridDim.x) {
+        // k is made scalar again in every tile, as k_attack does
+        asm volatile("" ::: "memory");
+        int k = A.k;
+        asm volatile("" : "+v"(k));
+        k = __builtin_amdgcn_readfirstlane(k);
+        const long e0 = (long)tl * E + threadIdx.x;
+        bool inb[U];
+        long off[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            inb[u] = e0 + u * 256 < A.P;
+            off[u] = inb[u] ? e0 + u * 256 : 0;
+        }
+        float x[U][KPAD];
+#pragma unroll
+        for (int j0 = 0; j0 < KPAD; j0 += GRP) {
+            if (j0 < k) {
+#pragma unroll
+                for (int j = j0; j < j0 + GRP; ++j) {
+                    const GeomedGlobalF32 src = (GeomedGlobalF32)s_ent[j];
+#pragma unroll
+                    for (int u = 0; u < U; ++u)
+                        x[u][j] = __builtin_nontemporal_load(src + off[u]);
+                }
+            } else {
+#pragma unroll
+                for (int j = j0; j < j0 + GRP; ++j)
+#pragma unroll
+                    for (int u = 0; u < U; ++u) x[u][j] = 0.f;
+            }
+        }
+#pragma unroll
+        for (int j0 = 0; j0 < KPAD; j0 += GRP) {
+            if (j0 < k) {
+#pragma unroll
+                for (int j = j0; j < j0 + GRP; ++j) {
+                    const float c = s_cnt[j], rc = s_rcnt[j];
+#pragma unroll
+                    for (int u = 0; u < U; ++u) x[u][j] = div_const(x[u][j], c, rc);
+                }
+            }
+        }
+        for (int i = 0; i < k; ++i) {
+            const unsigned long long mi = s_nbr[i];
+            const uint64_t m =
+                ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(mi >> 32)) << 32) |
+                (uint32_t)__builtin_amdgcn_readfirstlane((int)mi);
+            const AttackGlobalF32 dst = (AttackGlobalF32)s_ent[i];
+            float y[U];
+            nnm_mix_elem<KPAD, U>(x, m, k, A.fn, y);
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+                if (inb[u]) dst[off[u]] = y[u];
+        }
+    }
+}
+
+// flsim_nnm's fields, before any pointer is looked at
+static int check_nnm(const flsim_nnm* a) {
+    FLSIM_REQUIRE(a, "null NNM");
+    FLSIM_REQUIRE(a->k >= 1 && a->k <= RULE_MAX_ARR, "NNM over k = %d entries (1 .. %d)", a->k,
+                  RULE_MAX_ARR);
+    FLSIM_REQUIRE(a->f >= 0 && 2 * (long)a->f < a->k,
+                  "Invalid NNM f = %d for k = %d entries: f >= 0 and 2 * f < k", a->f, a->k);
+    return check_counts(a->count, a->k);
+}
+
+// ================================================================================================
 // Centered clipping with a carried center (CClip): distances to the iterate, the scalar step, apply
 // (include/flsim.h: flsim_cclip; csrc/cclip.h: the scalar code shared with the host; the geometry
 // is csrc/geomed.h's)
@@ -4078,6 +4246,142 @@ int flsim_attack_eval_host(const flsim_attack* a, float* b_out, long P) {
         attack_eval_host<FLSIM_ATTACK_IPM>(a, kh, b_out, P);
     else
         attack_eval_host<FLSIM_ATTACK_ALIE>(a, kh, b_out, P);
+    return 0;
+}
+
+// ---- nearest-neighbour mixing of the entries, in place (include/flsim.h) --------------------------
+long flsim_nnm_partials(long P, int k) { return flsim_krum_partials(P, k); }
+
+long flsim_nnm_tile_elems(int k) {
+    if (k < 1 || k > RULE_MAX_ARR) return 0;
+    return nnm_tile_elems(nnm_kpad(k));
+}
+
+// Three launches on `stream`: k_krum_dist -> s->partials (Krum's launch and geometry; it pads to
+// KPAD >= 4 with zero rows, so k = 1 and 2 take it too); k_nnm_finish -> s->dist, s->nbr;
+// k_nnm_mix over the entries in place.
+int flsim_nnm_entries(const flsim_nnm* a, const flsim_nnm_scratch* s, long P, hipStream_t stream) {
+    RC(check_nnm(a));
+    const int k = a->k;
+    for (int j = 0; j < k; ++j) {
+        FLSIM_REQUIRE(a->entries[j], "null entry %d", j);
+        FLSIM_REQUIRE(((uintptr_t)a->entries[j] & 15) == 0, "entry %d must be 16-byte aligned", j);
+    }
+    FLSIM_REQUIRE(P > 0 && P < (1L << 31), "P = %ld out of range", P);
+    FLSIM_REQUIRE(s && s->partials && s->dist && s->nbr, "null NNM scratch");
+    FLSIM_REQUIRE((((uintptr_t)s->partials | (uintptr_t)s->dist | (uintptr_t)s->nbr) & 15) == 0,
+                  "NNM scratch must be 16-byte aligned");
+    const int kpad = krum_kpad(k);
+    const long nblocks = krum_blocks(P, kpad);
+    const long n_dist = nblocks * krum_npb(kpad) * 16;
+    FLSIM_REQUIRE(s->n_partials >= n_dist, "NNM n_partials = %ld, this step writes %ld",
+                  s->n_partials, n_dist);
+    constexpr int NS = 3;
+    const Span sc[NS] = {{s->partials, 8 * n_dist}, {s->dist, 8L * k * k}, {s->nbr, 8L * k}};
+    for (int j = 0; j < k; ++j)
+        for (int q = 0; q < j; ++q)
+            FLSIM_REQUIRE(!overlaps(a->entries[q], a->entries[j], P), "entries %d and %d overlap",
+                          q, j);
+    for (int j = 0; j < k; ++j)
+        for (int b = 0; b < NS; ++b)
+            FLSIM_REQUIRE(!overlaps(a->entries[j], 4 * P, sc[b].ptr, sc[b].bytes),
+                          "entry %d overlaps the NNM scratch", j);
+    for (int b = 0; b < NS; ++b)
+        for (int c = b + 1; c < NS; ++c)
+            FLSIM_REQUIRE(!overlaps(sc[b].ptr, sc[b].bytes, sc[c].ptr, sc[c].bytes),
+                          "NNM scratch buffers overlap each other");
+    KrumDistArgs D{};
+    NnmMixArgs M{};
+    for (int j = 0; j < k; ++j) {
+        volatile float one = 1.f, c = (float)a->count[j];      // RN(1 / count) in fp32
+        D.T.ent[j] = M.ent[j] = a->entries[j];
+        D.T.cnt[j] = M.cnt[j] = c;
+        D.T.rcnt[j] = M.rcnt[j] = one / c;
+    }
+    D.partials = s->partials;
+    D.P = P;
+    D.k = k;
+    D.ntiles = (int)krum_tiles(P, kpad);
+    {
+        const ProbeSlot ps = probe_begin();
+        const dim3 grid((unsigned)nblocks);
+        with_kpad<4>(kpad, [&](auto kp) {
+            constexpr int KPAD = decltype(kp)::value;
+            hipExtLaunchKernelGGL((k_krum_dist<KPAD>), grid, dim3(KrumGeom<KPAD>::NT), 0, stream,
+                                  ps.start, ps.stop, 0, D);
+        });
+        FLSIM_LAUNCH_CHECK();
+        // algorithmic HBM bytes: each entry read once
+        if (probe_end(ps, K_NNM_DIST, 4.0 * (double)P * k)) return 2;
+    }
+    {
+        const ProbeSlot ps = probe_begin();
+        hipExtLaunchKernelGGL(k_nnm_finish, dim3(1), dim3(KRUM_FIN_THREADS), 0, stream, ps.start,
+                              ps.stop, 0, (const double*)s->partials, (int)nblocks, kpad / 4, k,
+                              (int)a->f, s->dist, s->nbr);
+        FLSIM_LAUNCH_CHECK();
+        if (probe_end(ps, K_NNM_FIN, 8.0 * (double)nblocks * (k * (k - 1) / 2) + 8.0 * k * (k + 1)))
+            return 2;
+    }
+    M.nbr = s->nbr;
+    M.P = P;
+    M.k = k;
+    M.fn = (float)(k - a->f);
+    const int mpad = nnm_kpad(k);
+    M.ntiles = (int)nnm_tiles(P, mpad);
+    {
+        const ProbeSlot ps = probe_begin();
+        const dim3 grid((unsigned)nnm_blocks(P, mpad));
+        with_kpad<4>(mpad, [&](auto kp) {
+            hipExtLaunchKernelGGL((k_nnm_mix<decltype(kp)::value>), grid, dim3(256), 0, stream,
+                                  ps.start, ps.stop, 0, M);
+        });
+        FLSIM_LAUNCH_CHECK();
+        // algorithmic HBM bytes: every entry read once and written once
+        if (probe_end(ps, K_NNM_MIX, 8.0 * (double)P * k)) return 2;
+    }
+    return 0;
+}
+
+// host (testing): the text for host pointers.  The bucket means by one fp32 division each, every
+// distance as the fp64 sum of the squared fp64 differences in element order (a pair is computed
+// once and mirrored), NaN -> +inf, a zero diagonal; then csrc/nnm.h's selection and element code.
+// a->entries are read only; out (nullable) is [k * P], row-major.
+int flsim_nnm_eval_host(const flsim_nnm* a, long P, double* dist, uint64_t* nbr, float* out) {
+    RC(check_nnm(a));
+    const int k = a->k;
+    for (int j = 0; j < k; ++j) FLSIM_REQUIRE(a->entries[j], "null entry %d", j);
+    FLSIM_REQUIRE(dist && nbr, "null pointer");
+    FLSIM_REQUIRE(P > 0, "P = %ld out of range", P);
+    auto mean = [&](int j, long e) -> float {
+        volatile float x = a->entries[j][e];
+        volatile float c = (float)a->count[j];
+        return x / c;
+    };
+    for (int i = 0; i < k; ++i) {
+        dist[(long)i * k + i] = 0.0;
+        for (int j = i + 1; j < k; ++j) {
+            double acc = 0.0;
+            for (long e = 0; e < P; ++e) {
+                const double d = (double)mean(i, e) - (double)mean(j, e);
+                acc = __builtin_fma(d, d, acc);
+            }
+            acc = acc != acc ? (double)__builtin_inff() : acc;
+            dist[(long)i * k + j] = acc;
+            dist[(long)j * k + i] = acc;
+        }
+    }
+    nnm_select(dist, nbr, k, (int)a->f, 0, 1);
+    if (!out) return 0;
+    const float fn = (float)(k - a->f);
+    for (long e = 0; e < P; ++e) {
+        float x[1][RULE_MAX_ARR], y[1];
+        for (int j = 0; j < RULE_MAX_ARR; ++j) x[0][j] = j < k ? mean(j, e) : 0.f;
+        for (int i = 0; i < k; ++i) {
+            nnm_mix_elem<RULE_MAX_ARR, 1>(x, nbr[i], k, fn, y);
+            out[(long)i * P + e] = y[0];
+        }
+    }
     return 0;
 }
 

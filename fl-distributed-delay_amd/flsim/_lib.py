@@ -58,6 +58,7 @@ EXPORTS = [
     "flsim_attack_tile_elems", "flsim_attack_entries", "flsim_attack_eval_host",
     "flsim_cclip_partials", "flsim_cclip_tile_elems", "flsim_cclip_optim_step",
     "flsim_cclip_eval_host",
+    "flsim_nnm_partials", "flsim_nnm_tile_elems", "flsim_nnm_entries", "flsim_nnm_eval_host",
 ]
 COMM_ID_BYTES = 128      # FLSIM_COMM_ID_BYTES
 
@@ -158,6 +159,18 @@ class FlsimAttack(ctypes.Structure):
     _fields_ = [("kind", ctypes.c_int32), ("k", ctypes.c_int32), ("strength", ctypes.c_double),
                 ("entries", ctypes.c_void_p * MAX_ARRAYS), ("honest", ctypes.c_int32 * MAX_ARRAYS),
                 ("byz", ctypes.c_int32 * MAX_ARRAYS)]
+
+
+class FlsimNnm(ctypes.Structure):
+    """flsim_nnm (include/flsim.h): nearest-neighbour mixing over k bucket sums and counts."""
+    _fields_ = [("f", ctypes.c_int32), ("k", ctypes.c_int32),
+                ("entries", ctypes.c_void_p * MAX_ARRAYS), ("count", ctypes.c_int32 * MAX_ARRAYS)]
+
+
+class FlsimNnmScratch(ctypes.Structure):
+    """flsim_nnm_scratch (include/flsim.h): the caller's scratch and outputs of a mixing."""
+    _fields_ = [("partials", ctypes.c_void_p), ("n_partials", ctypes.c_long),
+                ("dist", ctypes.c_void_p), ("nbr", ctypes.c_void_p)]
 
 
 # FLSIM_OPT_ADAM / _ADAMW / _SGD / _ADAGRAD / _YOGI
@@ -311,6 +324,12 @@ def lib():
     L.flsim_cclip_optim_step.argtypes = [vp, vp, vp, vp, vp, vp, vp, ctypes.c_long, ctypes.c_long,
                                          vp, vp]
     L.flsim_cclip_eval_host.argtypes = [vp, ctypes.c_long, vp, vp, vp, vp, vp, vp]
+    L.flsim_nnm_partials.restype = ctypes.c_long
+    L.flsim_nnm_partials.argtypes = [ctypes.c_long, ctypes.c_int]
+    L.flsim_nnm_tile_elems.restype = ctypes.c_long
+    L.flsim_nnm_tile_elems.argtypes = [ctypes.c_int]
+    L.flsim_nnm_entries.argtypes = [vp, vp, ctypes.c_long, vp]
+    L.flsim_nnm_eval_host.argtypes = [vp, ctypes.c_long, vp, vp, vp]
     L.flsim_cascade_program.argtypes = [ctypes.c_int, vp, vp, ctypes.c_int, vp, ctypes.c_int, vp]
     L.flsim_cascade_eval_host.argtypes = [vp, vp, vp, vp, ctypes.c_int, vp, ctypes.c_long, vp]
     L.flsim_probe_enable.argtypes = [ctypes.c_int]

@@ -22,7 +22,7 @@ import math
 
 from ._lib import (ATTACK_KINDS, MAX_ARRAYS, OPT_KINDS, ROBUST_KINDS, FlsimAttack, FlsimCclip,
                    FlsimCclipScratch, FlsimClip, FlsimGeomed, FlsimGeomedScratch, FlsimKrum,
-                   FlsimKrumScratch, FlsimOptim,
+                   FlsimKrumScratch, FlsimNnm, FlsimNnmScratch, FlsimOptim,
                    FlsimRobust, FlsimRule, FlsimRuleComp, FlsimRuleWeights, WorkerRec, check, lib,
                    ptr, stream_ptr)
 
@@ -493,6 +493,11 @@ class NetEngine:
         parameters: the crafted vector is mixed into the entries in place; b_out as
         attack_entries."""
         attack_entries(attack, b_out, self.P)
+
+    def nnm_entries(self, nnm):
+        """Nearest-neighbour mixing (an NNM over bucket sums) over this network's P parameters:
+        the entries become their mixed means in place, as nnm_entries."""
+        nnm_entries(nnm, self.P)
 
 
 class PN1Engine(NetEngine):
@@ -1211,6 +1216,78 @@ def attack_entries(attack, b_out=None, P=None):
         P = int(next(e for e in attack.entries if e is not None).numel())
     a = attack.c_struct()
     check(lib().flsim_attack_entries(ctypes.byref(a), ptr(b_out), int(P), stream_ptr()))
+
+
+class NNM:
+    """Nearest-neighbour mixing over bucket sums (flsim_nnm, include/flsim.h; Allouah et al.
+    2023): every entry becomes the mean of the k - f of the k = len(entries) values entries[j] /
+    counts[j] nearest to its own, itself included; a rule then reads the entries with counts 1.
+    entries: flat fp32 device tensors of the same length, all updated in place (no None here);
+    counts: the workers summed into each (>= 1).  The object owns its scratch per (device, P, k),
+    allocated at the first call and shared by the objects of a run; after a call dist ([k, k]
+    fp64) and nbr ([k] int64: bit j of nbr[i] = entry j is a neighbour of i) are device tensors,
+    read with no synchronisation beyond the stream's order; the next call overwrites them.
+    flsim/robust.py (nnm_flat) is the text."""
+    _scratch = {}       # (device, P, k) -> buffers
+
+    def __init__(self, f, entries, counts):
+        entries, counts = list(entries), [int(c) for c in counts]
+        if len(entries) != len(counts):
+            raise ValueError(f"{len(counts)} counts for {len(entries)} entries")
+        if len(entries) > MAX_ARRAYS:
+            raise ValueError(f"NNM over k = {len(entries)} entries (1 .. {MAX_ARRAYS})")
+        self.f = int(f)
+        self.entries, self.counts = entries, counts     # (keeps the tensors alive)
+        self.dist = self.nbr = None
+
+    @property
+    def k(self):
+        return len(self.entries)
+
+    def c_struct(self):
+        a = FlsimNnm()
+        a.f = self.f if -2 ** 31 <= self.f < 2 ** 31 else -1
+        a.k = len(self.entries)
+        for j, (e, c) in enumerate(zip(self.entries, self.counts)):
+            a.entries[j] = e.data_ptr() if e is not None else None
+            # (an int32 field: a count it cannot hold is refused as the library refuses one < 1)
+            a.count[j] = c if -2 ** 31 <= c < 2 ** 31 else -1
+        return a
+
+    def c_scratch(self, device, P):
+        """flsim_nnm_scratch over this device's scratch for a mixing over P elements."""
+        k = len(self.entries)
+        key = (str(device), int(P), k)
+        if key not in NNM._scratch:
+            n = max(int(lib().flsim_nnm_partials(int(P), k)), 2)
+            NNM._scratch[key] = (torch.empty(n, dtype=torch.float64, device=device),
+                                 torch.empty(k * k + 2, dtype=torch.float64, device=device),
+                                 torch.empty(k + 2, dtype=torch.int64, device=device))
+        partials, dist, nbr = NNM._scratch[key]
+        s = FlsimNnmScratch()
+        s.partials = partials.data_ptr()
+        s.n_partials = int(partials.numel())
+        s.dist = dist.data_ptr()
+        s.nbr = nbr.data_ptr()
+        self.partials = partials
+        self.dist = dist[:k * k].view(k, k)
+        self.nbr = nbr[:k]
+        return s
+
+    def neighbours(self):
+        """nbr read back as k ascending lists of entry indices (synchronises)."""
+        return [[j for j in range(self.k) if (int(w) >> j) & 1] for w in self.nbr.tolist()]
+
+
+def nnm_entries(nnm, P=None):
+    """Replace the NNM's entries by their mixed means in place, in three launches
+    (flsim_nnm_entries); nnm.dist and nnm.nbr then hold the distances and the neighbour masks."""
+    ref = next((e for e in nnm.entries if e is not None), None)
+    if P is None:
+        P = int(ref.numel())
+    a = nnm.c_struct()
+    s = nnm.c_scratch(ref.device if ref is not None else "cpu", P)
+    check(lib().flsim_nnm_entries(ctypes.byref(a), ctypes.byref(s), int(P), stream_ptr()))
 
 
 def worker_table(recs, device):

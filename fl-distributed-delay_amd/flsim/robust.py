@@ -11,6 +11,7 @@ NaN where it gives a NaN.
     Agg(lambda ups: krum_rule(ups, f=1))              # the update closest to its neighbours
     Agg(lambda ups: multi_krum_rule(ups, f=1, m=3))   # the mean of the three closest
     Agg(CenteredClip(tau=10.0, iters=1))              # centered clipping; the object keeps its center
+    Agg(NNM(median_rule, f=1))                        # nearest-neighbour mixing, then any rule
 """
 from __future__ import annotations
 
@@ -152,6 +153,85 @@ def krum_flat(entries, counts, f, m=1):
     cols = torch.stack(bucket_means(sums, counts))
     d, score, sel = krum_select(cols, f, m)
     return _krum(cols, f, m), d, score, sel
+
+
+# ---- Nearest-neighbour mixing (NNM; Allouah et al. 2023, "Fixing by Mixing"): a pre-aggregation
+# stage, not a rule.  Every entry is replaced by the mean of its k - f nearest entries, itself
+# included, and any rule then runs over the mixed entries (count 1 each).  The distances are
+# Krum's, over the whole model.  The yardstick of flsim_nnm_entries (include/flsim.h) and of its
+# host twin: dist within 2 (P + 2) 2^-53 relative, nbr equal wherever the text's cut is wider than
+# that, and given equal nbr the mixed entries equal _nnm as numbers.
+def nnm_neighbours(cols, f):                 # cols: [k, numel] fp32, already bucket means
+    k = cols.shape[0]
+    x = cols.double()
+    d = torch.stack([((x[i] - x) ** 2).sum(1) for i in range(k)])      # fp64, exactly symmetric
+    d = torch.where(torch.isnan(d), torch.full_like(d, float("inf")), d)
+    # an entry is always its own nearest neighbour, even one that holds a NaN (whose distance to
+    # itself is NaN -> +inf above): it keeps itself among its neighbours and stays NaN, and the
+    # rule behind treats it as it treats any poisoned entry.  Every other row sees it at +inf,
+    # hence last.
+    d.fill_diagonal_(0.0)
+    nbr = []
+    for i in range(k):
+        order = sorted(range(k), key=lambda j: (d[i, j].item(), j))    # ties: lowest index
+        nbr.append(sorted(order[:k - f]))    # the k - f nearest, in index order; i is among them
+    return d, nbr
+
+
+def _nnm(cols, f):
+    _, nbr = nnm_neighbours(cols, f)
+    out = []
+    for i in range(cols.shape[0]):
+        acc = cols[nbr[i][0]].clone()
+        for j in nbr[i][1:]:                 # sequential fp32 adds, ascending entry index
+            acc += cols[j]
+        out.append(acc / (cols.shape[0] - f))    # one IEEE fp32 division
+    return torch.stack(out)
+
+
+def check_nnm(f, k):
+    """The cases the library refuses (ValueError), and rule()'s IndexError on an empty list."""
+    f = int(f)
+    if k == 0:
+        raise IndexError("empty weight_ups (reference: IndexError in rule, main.py:25)")
+    if f < 0 or 2 * f >= k:
+        raise ValueError(f"Invalid NNM f = {f} for k = {k} entries: f >= 0 and 2 * f < k")
+    return f
+
+
+def nnm_flat(entries, counts, f):
+    """The text over flat bucket SUMS (None = an all-zero entry) with their counts: what
+    flsim_nnm_entries computes.  Returns (mixed [k, P] fp32, dist [k, k] fp64, nbr: k lists)."""
+    ref = next(e for e in entries if e is not None)
+    sums = [torch.zeros_like(ref) if e is None else e for e in entries]
+    f = check_nnm(f, len(sums))
+    cols = torch.stack(bucket_means(sums, counts))
+    d, nbr = nnm_neighbours(cols, f)
+    return _nnm(cols, f), d, nbr
+
+
+class NNM:
+    """Nearest-neighbour mixing in front of any rule, as a rule: NNM(median_rule, f=1)(ups_list).
+    All tensors are flattened together (the distances are over the whole model), the k updates are
+    mixed, un-flattened into k per-parameter lists and handed to `rule`."""
+
+    def __init__(self, rule, f):
+        self.rule, self.f = rule, int(f)
+        if self.f < 0:
+            raise ValueError(f"Invalid NNM f = {self.f}: it must be >= 0")
+
+    def __call__(self, ups_list):
+        f = check_nnm(self.f, len(ups_list))
+        cols = torch.stack([torch.cat([u.reshape(-1) for u in ups]) for ups in ups_list])
+        mixed = _nnm(cols, f)
+        out = []
+        for row in mixed:
+            ups, off = [], 0
+            for u in ups_list[0]:
+                ups.append(row[off:off + u.numel()].view(u.shape))
+                off += u.numel()
+            out.append(ups)
+        return self.rule(out)
 
 
 # ---- the geometric median by smoothed Weiszfeld iterations ("RFA", Pillutla, Kakade and Harchaoui

@@ -40,6 +40,14 @@ omniscient attack on the epoch's fresh bucket entries (flsim/robust.py: attack_f
 robust_rule, ("trimmed_mean", 0) being the undefended mean over buckets).  They compute nothing:
 one launch mixes the crafted vector into the bucket sums before the robust step reads them.
 attack_log() returns every epoch's (kind, strength used, Byzantine workers present).
+
+nnm (None or f >= 0; needs robust_rule) puts nearest-neighbour mixing (NNM, Allouah et al. 2023;
+flsim/robust.py: nnm_flat) in front of the robust rule: after the attack, every entry of the epoch
+(fresh buckets and popped slots alike) is replaced in place by the mean of its k - f nearest
+entries, itself included, and the rule reads the mixed entries with count 1 each.  f is the number
+of Byzantine ENTRIES assumed (2 f < this epoch's k).  With weights "count" the geometric median
+and centered clipping therefore see equal weights.  nnm_log() returns every epoch's neighbour
+masks.
 """
 from __future__ import annotations
 
@@ -51,7 +59,8 @@ import torch
 from .data import DevicePool, make_test_pool
 from .engine import (PN1_SIZES, Clip, Optim, ProgramStager, Rule, engine_class, optim_defaults,
                      padded, split_views, staleness_weight)
-from .robust import CCLIP_KIND, GEOMED_KIND, KRUM_KINDS, alie_z, check_krum, parse_attack, parse_rule
+from .robust import (CCLIP_KIND, GEOMED_KIND, KRUM_KINDS, alie_z, check_krum, check_nnm,
+                     parse_attack, parse_rule)
 from .schedule import Schedule, reference_delays
 
 SEMANTICS = ("reference", "torch1", "independent")
@@ -95,7 +104,7 @@ class FLSimulation:
                  dampening=0.0, nesterov=False, stale_weight=None, stale_normalize="weights",
                  delay_comp=None, clip_grad_norm=None, lr_decay=0.0,
                  initial_accumulator_value=None, robust_rule=None, buckets=8,
-                 keep_entries=False, attack=None, n_byz=0, byz_placement="spread"):
+                 keep_entries=False, attack=None, n_byz=0, byz_placement="spread", nnm=None):
         if semantics not in SEMANTICS:
             raise NotImplementedError(f"semantics {semantics!r} (supported: {SEMANTICS})")
         # a robust rule in place of the mean (None: off; today's code paths exactly): (kind, trim),
@@ -134,6 +143,20 @@ class FLSimulation:
                                       "undefended mean over buckets)")
         if self.n_byz < 0:
             raise ValueError(f"n_byz = {self.n_byz}: it must be >= 0")
+        # nearest-neighbour mixing of the entries before the rule (None: off; today's code paths
+        # exactly): f, the Byzantine entries assumed; checked against every epoch's k
+        if nnm is not None:
+            if isinstance(nnm, bool) or not isinstance(nnm, (int, np.integer)):
+                raise ValueError(f"Invalid NNM f = {nnm!r}: it must be an integer >= 0")
+            if nnm < 0:
+                raise ValueError(f"Invalid NNM f = {nnm}: it must be an integer >= 0")
+            if self.robust is None:
+                raise NotImplementedError("nnm needs robust_rule: the bucketed entries are what "
+                                          "it acts on (robust_rule=('trimmed_mean', 0) is the "
+                                          "mean over the mixed buckets)")
+        self.nnm = None if nnm is None else int(nnm)
+        self.last_mixed = None          # with keep_entries: clones of the mixed entries
+        self.nnm_entries_log = []       # per epoch: the neighbour masks, a cloned device tensor
         if self.n_byz >= 1 and self.attack is None:
             raise ValueError(f"n_byz = {self.n_byz} Byzantine workers without an attack")
         if self.attack is not None and self.n_byz == 0:
@@ -789,6 +812,8 @@ class FLSimulation:
                              "buckets or delay classes are needed")
         if self.keep_entries:
             self.last_entries = ([e[:self.P].clone() for e in entries], list(counts))
+        if self.nnm is not None:
+            counts = self._nnm(entries, counts)
         if self.robust[0] in KRUM_KINDS:
             # Krum / Multi-Krum: f and m against this epoch's k, as the trim is refused below
             from .engine import Krum
@@ -876,6 +901,25 @@ class FLSimulation:
         for j, nb in enumerate(byz):
             counts[j] += nb
         self.attack_entries_log.append((kind, float(strength), present))
+
+    def _nnm(self, entries, counts):
+        """Nearest-neighbour mixing of all the epoch's entries in place (three launches): every
+        slot here is owned by this epoch and goes back to free_slots after the step, so nothing
+        else reads it.  f is checked against this epoch's k, as Krum's.  Returns the counts the
+        rule then reads: 1 each."""
+        from .engine import NNM
+        check_nnm(self.nnm, len(entries))
+        mix = NNM(self.nnm, [e[:self.P] for e in entries], counts)
+        self.engine.nnm_entries(mix)
+        self.nnm_entries_log.append(mix.nbr.detach().clone())   # (a device tensor: no sync)
+        if self.keep_entries:
+            self.last_mixed = [e[:self.P].clone() for e in entries]
+        return [1] * len(entries)
+
+    def nnm_log(self):
+        """Per epoch of a run with nnm (else []) the neighbour masks as cloned device tensors
+        ([k] int64: bit j of word i = entry j is a neighbour of entry i).  Never synchronises."""
+        return list(self.nnm_entries_log)
 
     def attack_log(self):
         """Per epoch of a run under attack (else []) the triple (kind, strength used, Byzantine
@@ -1026,6 +1070,7 @@ class FLSimulation:
                 "robust_rule": None if self.robust is None else list(self.robust),
                 "buckets": self.buckets,
                 "attack": None if self.attack is None else list(self.attack),
+                "nnm": self.nnm,
                 "n_byz": self.n_byz, "byz_placement": self.byz_placement}
 
     def save_checkpoint(self, path):
@@ -1059,7 +1104,9 @@ class FLSimulation:
                      # ... and from before the robust rules: off, the default bucket count
                      ("robust_rule", None), ("buckets", 8),
                      # ... and from before the simulated Byzantine workers: none
-                     ("attack", None), ("n_byz", 0), ("byz_placement", "spread")):
+                     ("attack", None), ("n_byz", 0), ("byz_placement", "spread"),
+                     # ... and from before nearest-neighbour mixing: off
+                     ("nnm", None)):
             cfg.setdefault(k, v)
         delays = cfg["delays"].numpy().astype(np.int32)
         if fmt == "flsim-checkpoint-1":

@@ -30,6 +30,11 @@ Baruch et al. 2019; default X = the paper's z for the epoch's worker counts), mu
 coordinate-wise mean and standard deviation of the honest buckets' means.  --attack_strength is not
 --byz_f, which stays the count Krum tolerates.  'Attack' per epoch logs (kind, strength, Byzantine
 workers present).
+--nnm F (needs --robust_rule) mixes the entries before the rule (nearest-neighbour mixing, Allouah
+et al. 2023): after the attack, every entry is replaced by the mean of its k - F nearest entries,
+itself included, and the rule reads the mixed entries with count 1 each -- so --geomed_weights
+count and --cclip_weights count then see equal weights.  F is the number of Byzantine ENTRIES
+assumed, like --byz_f, and 2F must stay below every epoch's entry count.
 The training loop (main.py:126-188) runs as flsim.sim.FLSimulation: host schedule,
 worker-batched HIP forward/backward, fused rule()+Adam; with
 `torchrun --nproc-per-node N` the computing workers are sharded over N GPUs with one RCCL
@@ -150,6 +155,11 @@ def parse(argv=None):
     p.add_argument('--byz_placement', default='spread', choices=['spread', 'block'],
                    help='--attack: the Byzantine workers are spread evenly over the fast workers, '
                         'or are the first N of them, filling whole buckets (default spread)')
+    p.add_argument('--nnm', type=int, default=None, metavar='F',
+                   help='nearest-neighbour mixing before --robust_rule: every entry becomes the '
+                        'mean of its (entry count - F) nearest entries, itself included; F is the '
+                        "number of Byzantine entries assumed, like --byz_f, 2F < the epoch's "
+                        'entry count (default: off)')
     p.add_argument('--seed', type=int, default=0)
     p.add_argument('--semantics', default='reference', choices=['reference', 'torch1', 'independent'],
                    help='stale entry = S_{t-d} (torch>=2 aliasing), zeros (torch 1.x) or the slow '
@@ -206,6 +216,17 @@ def attack_spec(args):
     return args.attack if args.attack_strength is None else (args.attack, args.attack_strength)
 
 
+def nnm_spec(args):
+    """--nnm as FLSimulation's nnm (None: off)."""
+    if args.nnm is None:
+        return None
+    if args.nnm < 0:
+        raise SystemExit(f"--nnm {args.nnm}: F must be >= 0")
+    if args.robust_rule == 'none':
+        raise SystemExit("--nnm needs --robust_rule: the bucketed entries are what it mixes")
+    return args.nnm
+
+
 def optim_kwargs(args):
     """--lr_decay / --initial_accumulator_value / --eps / --beta1 / --beta2 as FLSimulation's
     arguments; a flag left out resolves to the kind's default (flsim.engine.optim_defaults)."""
@@ -250,7 +271,7 @@ def main(argv=None):
                        delay_comp=args.delay_comp, clip_grad_norm=args.clip_grad_norm,
                        robust_rule=robust_spec(args), buckets=args.buckets,
                        attack=attack_spec(args), n_byz=args.n_byz,
-                       byz_placement=args.byz_placement,
+                       byz_placement=args.byz_placement, nnm=nnm_spec(args),
                        **optim_kwargs(args))
     if buffers:
         sim.engine.load_buffers(buffers)

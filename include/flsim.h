@@ -848,6 +848,91 @@ int flsim_attack_entries(const flsim_attack* a, float* b_out /* nullable, [P] */
 int flsim_attack_eval_host(const flsim_attack* a, float* b_out, long P);
 
 /* ---------------------------------------------------------------------------------------------
+ * Nearest-neighbour mixing (NNM; Allouah, Farhadkhani, Guerraoui, Gupta, Pinot and Stephan 2023,
+ * "Fixing by Mixing"): a pre-aggregation stage in front of any robust rule.  Every entry is
+ * replaced by the mean of its k - f nearest entries, itself included; the rule then reads the
+ * mixed entries with count 1.  An in-place transform of the bucket SUMS, like flsim_attack.  The
+ * text (flsim/robust.py, plain torch):
+ *
+ *   def nnm_neighbours(cols, f):                 # cols: [k, numel] fp32, already bucket means
+ *       k = cols.shape[0]
+ *       x = cols.double()
+ *       d = torch.stack([((x[i] - x) ** 2).sum(1) for i in range(k)])      # fp64, exactly symmetric
+ *       d = torch.where(torch.isnan(d), torch.full_like(d, float("inf")), d)
+ *       d.fill_diagonal_(0.0)                    # an entry is always its own nearest neighbour
+ *       nbr = []
+ *       for i in range(k):
+ *           order = sorted(range(k), key=lambda j: (d[i, j].item(), j))    # ties: lowest index
+ *           nbr.append(sorted(order[:k - f]))    # the k - f nearest, in index order
+ *       return d, nbr
+ *   def _nnm(cols, f):
+ *       _, nbr = nnm_neighbours(cols, f)
+ *       out = []
+ *       for i in range(cols.shape[0]):
+ *           acc = cols[nbr[i][0]].clone()
+ *           for j in nbr[i][1:]:                 # sequential fp32 adds, ascending entry index
+ *               acc += cols[j]
+ *           out.append(acc / (cols.shape[0] - f))    # one IEEE fp32 division
+ *       return torch.stack(out)
+ *
+ * x_j[e] = entries[j][e] / (float)count[j], as flsim_robust forms the bucket means.  The diagonal
+ * is zero even for an entry that holds a NaN: such an entry keeps itself among its neighbours and
+ * stays NaN, and the rule behind treats it as it treats any poisoned entry; every other row sees
+ * it at +inf, hence last.
+ *
+ * Three launches on `stream`; no allocation, no host synchronisation, no atomics; the grids and
+ * the element-to-block maps depend on (P, k) alone.
+ *   1. distances: the launch of flsim_krum_optim_step (same kernel, same geometry, same sums)
+ *      into s->partials; it pads to 4 .. 64 rows with zero rows, so k = 1 and 2 take it too.
+ *      Reads every entry once.
+ *   2. finish, one block: adds the partials in Krum's fixed order (NaN -> +inf, mirrored, zero
+ *      diagonal), writes s->dist, runs the neighbour selection (each row: k - f scans for the
+ *      smallest (value, j) above the last one taken) and writes s->nbr.
+ *   3. mix, element-wise and in place: a thread issues the loads of all k entries for its
+ *      elements before any arithmetic or store, forms every x_j, then every y_i in the text's
+ *      order (ascending j over the bits of nbr[i], sequential fp32 adds, never an fma, one IEEE
+ *      division by (float)(k - f)) and stores y_i to entries[i].  Every element is read and
+ *      written by one thread only, so in place needs no ordering between blocks.  Reads and
+ *      writes k P floats once each; nothing is written past P.  P need not be a multiple of
+ *      anything.
+ * s->partials, s->dist and s->nbr are never read before they are written: their previous contents,
+ * any bytes, do not matter.
+ *
+ * dist is within 2 (P + 2) 2^-53 relative of the text's (Krum's bound, from the same launch; the
+ * same inputs give the same bits on every call, and identical rows give bit-identical sums).  nbr
+ * equals the text's wherever the text's row i has its (k - f)-th and (k - f + 1)-th smallest
+ * distances further apart than that; exact ties are broken by the lower index on both sides.
+ * Given equal nbr, the mixed entries equal _nnm "as numbers" in the sense of
+ * flsim_robust_optim_step.
+ * Checked before any pointer, status 1: k outside [1, FLSIM_MAX_ARRAYS]; f < 0 or 2 f >= k; a
+ * count < 1.  Then: a NULL or misaligned (16 bytes) entry (every entry is read and written: no
+ * NULL "all-zero" entries here); P outside [1, 2^31); a NULL or misaligned (16 bytes) scratch
+ * pointer; n_partials too small; two entries that overlap; an entry that overlaps the scratch;
+ * scratch buffers that overlap each other.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct flsim_nnm {
+    int32_t f, k;                          /* 1 <= k <= FLSIM_MAX_ARRAYS, 0 <= 2f < k */
+    float*  entries[FLSIM_MAX_ARRAYS];     /* in: bucket SUMS; out: the mixed MEANS (count 1), in place */
+    int32_t count[FLSIM_MAX_ARRAYS];       /* >= 1: x_j[e] = entries[j][e] / (float)count[j] */
+} flsim_nnm;
+typedef struct flsim_nnm_scratch {         /* caller-provided, 16-byte aligned, never pre-initialised */
+    double* partials; long n_partials;     /* >= flsim_nnm_partials(P, k) */
+    double* dist;                          /* [k*k] out */
+    uint64_t* nbr;                         /* [k] out: bit j of nbr[i] = entry j is a neighbour of i */
+} flsim_nnm_scratch;
+/* the doubles the distance launch writes: flsim_krum_partials(P, k) (0: P or k out of range) */
+long flsim_nnm_partials(long P, int k);
+/* (tests) the MIX launch's tile: the elements of every entry a block takes at a time (0: k out of
+ * range); the distance launch's tile is flsim_krum_tile_elems(k) */
+long flsim_nnm_tile_elems(int k);
+int flsim_nnm_entries(const flsim_nnm* a, const flsim_nnm_scratch* s, long P, flsim_stream_t stream);
+/* host (testing): dist [k * k], nbr [k] and the mixed entries (out nullable, [k * P] row-major) of
+ * the text for host pointers: the distances summed in element order, then the selection and the
+ * element code the kernels run; a->entries are left unmodified; refuses what the entry point
+ * refuses about a's fields, and a NULL entry */
+int flsim_nnm_eval_host(const flsim_nnm* a, long P, double* dist, uint64_t* nbr, float* out);
+
+/* ---------------------------------------------------------------------------------------------
  * Centered clipping with a carried center ("CClip", Karimireddy, He and Jaggi 2021), fused with
  * the update.  The clipping center c of an epoch is the previous epoch's aggregate (all zero on
  * the first step): every entry is pulled towards the iterate with weight min(1, tau / distance),
