@@ -1804,22 +1804,50 @@ static int check_counts(const int32_t* count, int k) {
     return 0;
 }
 
+// a bucket mean on the host twins: one fp32 division (volatile: one rounding whatever the flags); a
+// null entry is all zero
+static float bucket_mean(const float* const* entries, const int32_t* count, int j, long e) {
+    volatile float x = entries[j] ? entries[j][e] : 0.f;
+    volatile float c = (float)count[j];
+    return x / c;
+}
+
 // ---- the host side of a bucketed step: the stages the four entry points run, in this order ------
 // (after the rule's own hyper-parameter check; a rule's checks of its center and of its scratch
 // pointers come between step_begin and check_scratch)
-struct BucketStep {
-    OptLaunch ol;                       // OK_GOUT without an optimizer
-    int nstate;
-    float *g_out, *p, *m, *v;           // p / m / v: null where the kind does not own them
+// what the entries and the scratch are checked against (check_scratch, fill_entries); a call with
+// no p / m / v / clip (NNM) has P alone: StepBuffers{} and P
+struct StepBuffers {
     const float* outs[4];               // p, m, v, g_out
     const flsim_clip* clip;
     long P, nblk;                       // nblk: the apply launch's blocks = the clip partials
+};
+
+struct BucketStep : StepBuffers {
+    OptLaunch ol;                       // OK_GOUT without an optimizer
+    int nstate;
+    float *g_out, *p, *m, *v;           // p / m / v: null where the kind does not own them
 };
 
 struct Span {                           // a scratch buffer
     const void* ptr;
     long bytes;
 };
+
+// a bucketed call's scratch pointers, before check_scratch: sc[0] is the partials, n_partials
+// doubles of which this step writes n_dist (a null scratch struct: the caller passes an empty one)
+static int check_scratch_pointers(const char* name, const Span* sc, int ns, long n_partials,
+                                  long n_dist) {
+    uintptr_t all = 0;
+    for (int a = 0; a < ns; ++a) {
+        FLSIM_REQUIRE(sc[a].ptr, "null %s scratch", name);
+        all |= (uintptr_t)sc[a].ptr;
+    }
+    FLSIM_REQUIRE((all & 15) == 0, "%s scratch must be 16-byte aligned", name);
+    FLSIM_REQUIRE(n_partials >= n_dist, "%s n_partials = %ld, this step writes %ld", name,
+                  n_partials, n_dist);
+    return 0;
+}
 
 // the optimizer's and the clip's hyper-parameters (before any pointer), then p / m / v / g_out / P
 static int step_begin(const flsim_optim* optim, const flsim_clip* clip, float* g_out, float* p,
@@ -1862,7 +1890,7 @@ static int step_begin(const flsim_optim* optim, const flsim_clip* clip, float* g
 
 // the rule's scratch buffers against each other, the outputs, clip G and the rule's center
 // (nullable); `name` is the rule's in the messages; a buffer of no bytes overlaps nothing
-static int check_scratch(const BucketStep& B, const char* name, const Span* sc, int ns,
+static int check_scratch(const StepBuffers& B, const char* name, const Span* sc, int ns,
                          const float* center) {
     for (int a = 0; a < ns; ++a) {
         if (!sc[a].bytes) continue;
@@ -1882,7 +1910,7 @@ static int check_scratch(const BucketStep& B, const char* name, const Span* sc, 
 }
 
 // the clip buffers (center: centered clipping's, nullable)
-static int check_clip_buffers(const BucketStep& B, const float* center) {
+static int check_clip_buffers(const StepBuffers& B, const float* center) {
     const flsim_clip* clip = B.clip;
     if (!clip) return 0;
     FLSIM_REQUIRE(clip->G && clip->partials && clip->out, "null clip buffer");
@@ -1897,7 +1925,7 @@ static int check_clip_buffers(const BucketStep& B, const float* center) {
 // the entries: their alignment and their overlap with the outputs, clip G, the scratch (sc
 // nullable) and the center (nullable); fills T; *distinct: the entry arrays read (not NULL, each
 // counted once).  Then the size of the clip partials, the last check before the first launch.
-static int fill_entries(const BucketStep& B, const float* const* entries, const int32_t* count,
+static int fill_entries(const StepBuffers& B, const float* const* entries, const int32_t* count,
                         int k, const char* name, const Span* sc, int ns, const float* center,
                         EntryTable* T, int* distinct) {
     *distinct = 0;
@@ -2008,9 +2036,7 @@ static void robust_eval_host(const flsim_robust* r, long P, float* g_out) {
                 key[j] = ROBUST_PAD;
                 continue;
             }
-            volatile float x = r->entries[j] ? r->entries[j][e] : 0.f;
-            volatile float c = (float)r->count[j];
-            key[j] = robust_key(x / c);
+            key[j] = robust_key(bucket_mean(r->entries, r->count, j, e));
         }
         float g = robust_select<KPAD>(key, r->kind, r->trim, r->k);
         if (r->kind != FLSIM_ROBUST_MEDIAN) {
@@ -2179,20 +2205,18 @@ __global__ void __launch_bounds__(KrumGeom<KPAD>::NT) k_krum_dist(KrumDistArgs A
     }
 }
 
-// One block of KRUM_FIN_THREADS = 16 waves.  Pair (i, j), i < j, belongs to one wave: lane l adds
-// the partials of the blocks l, l + 64, ... in index order (coalesced: the partials are slot-major)
-// and a butterfly adds the 64 lanes, as k_clip_finish and block_sum_f64 do -- a fixed order for a
-// given (P, k).  A wave takes four pairs at a time and issues all their loads before any add.  A NaN
-// sum becomes +inf, the value is mirrored, the diagonal is zero.  Then csrc/krum.h's score /
-// selection code on the matrix in LDS.
+// The pairwise-distance stage's matrix, for one block of KRUM_FIN_THREADS = 16 waves (k_krum_finish,
+// k_nnm_finish: the two rules read one matrix, bit for bit, because this is its only text).  Pair
+// (i, j), i < j, belongs to one wave: lane l adds the partials of the blocks l, l + 64, ... in index
+// order (coalesced: the partials are slot-major) and a butterfly adds the 64 lanes, as k_clip_finish
+// and block_sum_f64 do -- a fixed order for a given (P, k).  A wave takes four pairs at a time and
+// issues all their loads before any add.  A NaN sum becomes +inf, the value is mirrored, the
+// diagonal is zero.  The matrix is left in sd ([k * k] of the caller's LDS, visible to the whole
+// block on return) and stored to dist.
 constexpr int KRUM_FIN_THREADS = 1024;
 
-__global__ void __launch_bounds__(KRUM_FIN_THREADS)
-k_krum_finish(const double* partials, int nblocks, int nb, int k, int f, int m, double* dist,
-              double* score, int32_t* sel) {
-    __shared__ double sd[RULE_MAX_ARR * RULE_MAX_ARR];
-    __shared__ double ss[RULE_MAX_ARR];
-    __shared__ int32_t sr[RULE_MAX_ARR];
+__device__ __forceinline__ void pair_matrix(const double* partials, int nblocks, int nb, int k,
+                                            double* sd, double* dist) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     constexpr int WAVES = KRUM_FIN_THREADS / 64;
     // every load of a pair is issued before the first add (the grid's cap bounds them: 12 a lane)
@@ -2230,9 +2254,81 @@ k_krum_finish(const double* partials, int nblocks, int nb, int k, int f, int m, 
     }
     __syncthreads();
     for (int idx = threadIdx.x; idx < k * k; idx += KRUM_FIN_THREADS) dist[idx] = sd[idx];
+}
+
+// pair_matrix, then csrc/krum.h's score / selection code on the matrix in LDS
+__global__ void __launch_bounds__(KRUM_FIN_THREADS)
+k_krum_finish(const double* partials, int nblocks, int nb, int k, int f, int m, double* dist,
+              double* score, int32_t* sel) {
+    __shared__ double sd[RULE_MAX_ARR * RULE_MAX_ARR];
+    __shared__ double ss[RULE_MAX_ARR];
+    __shared__ int32_t sr[RULE_MAX_ARR];
+    pair_matrix(partials, nblocks, nb, k, sd, dist);
     krum_score_select(sd, ss, sr, sel, k, f, m, (int)threadIdx.x, KRUM_FIN_THREADS,
                       [] { __syncthreads(); });
     if ((int)threadIdx.x < k) score[threadIdx.x] = ss[threadIdx.x];
+}
+
+// the doubles k_krum_dist writes for (P, k): one run of NPB * 16 a block
+static long pair_partials(long P, int k) {
+    const int kpad = krum_kpad(k);
+    return krum_blocks(P, kpad) * krum_npb(kpad) * 16;
+}
+
+// The pairwise-distance stage on `stream`: k_krum_dist over the table -> partials (probe id
+// kid_dist; algorithmic HBM bytes: the `arrays` distinct entries read once), then the consumer's
+// finish launch, finish(probe slot, partials, nblocks, nb), which is to call pair_matrix (probe id
+// kid_fin; bytes: the pairs' partials read, dist and a [k] result written, and fin_bytes of its own).
+template <class F>
+static int launch_pair_dist(const EntryTable& T, double* partials, long P, int k, int kid_dist,
+                            int arrays, int kid_fin, double fin_bytes, hipStream_t stream,
+                            F&& finish) {
+    const int kpad = krum_kpad(k);
+    const long nblocks = krum_blocks(P, kpad);
+    KrumDistArgs D{};
+    D.T = T;
+    D.partials = partials;
+    D.P = P;
+    D.k = k;
+    D.ntiles = (int)krum_tiles(P, kpad);
+    {
+        const ProbeSlot ps = probe_begin();
+        const dim3 grid((unsigned)nblocks);
+        with_kpad<4>(kpad, [&](auto kp) {
+            constexpr int KPAD = decltype(kp)::value;
+            hipExtLaunchKernelGGL((k_krum_dist<KPAD>), grid, dim3(KrumGeom<KPAD>::NT), 0, stream,
+                                  ps.start, ps.stop, 0, D);
+        });
+        FLSIM_LAUNCH_CHECK();
+        if (probe_end(ps, kid_dist, 4.0 * (double)P * arrays)) return 2;
+    }
+    const ProbeSlot ps = probe_begin();
+    finish(ps, (const double*)partials, (int)nblocks, kpad / 4);
+    FLSIM_LAUNCH_CHECK();
+    if (probe_end(ps, kid_fin, 8.0 * (double)nblocks * (k * (k - 1) / 2) + 8.0 * k * (k + 1) +
+                                   fin_bytes))
+        return 2;
+    return 0;
+}
+
+// the stage's host twin: every distance as the fp64 sum of the squared fp64 differences of the
+// means in element order (one fma each; a pair is computed once and mirrored), NaN -> +inf, a zero
+// diagonal
+template <class M>
+static void pair_dist_host(M&& mean, int k, long P, double* dist) {
+    for (int i = 0; i < k; ++i) {
+        dist[(long)i * k + i] = 0.0;
+        for (int j = i + 1; j < k; ++j) {
+            double a = 0.0;
+            for (long e = 0; e < P; ++e) {
+                const double d = (double)mean(i, e) - (double)mean(j, e);
+                a = __builtin_fma(d, d, a);
+            }
+            a = a != a ? (double)__builtin_inff() : a;
+            dist[(long)i * k + j] = a;
+            dist[(long)j * k + i] = a;
+        }
+    }
 }
 
 struct KrumApplyArgs {
@@ -2539,28 +2635,20 @@ struct GeomedFinArgs {
     int nblocks, k, pair, iters, weighted;
 };
 
-// One block of 16 waves.  Entry j's sum belongs to one wave: lane l adds the partials of the
-// blocks l, l + 64, ... in index order (coalesced: the partials are slot-major) and a butterfly
-// adds the 64 lanes, as k_krum_finish does -- a fixed order for a given (P, k).  Pair 0 also ORs
-// the blocks' masks, writes the dead flags and the control words, and w^(0) over the live entries
-// (the host's, bit for bit, when none is dead); with a dead entry its distances are worthless (z was
-// a NaN) and it stops there: "redo".  Then csrc/geomed.h's scalar code of one iteration on the
-// sums in LDS, and d2, obj and the next w.
+// The distance-to-iterate stage's two reductions, for one block of GEOMED_FIN_THREADS = 16 waves
+// (k_geomed_finish, k_cclip_finish).  Both take the kernel's own argument struct (its partials,
+// nblocks and k) by reference: with the three passed by value the compiler loads the arguments
+// earlier and both kernels need 4 - 6 more SGPRs (profiles/pair_stage/README.md).
 constexpr int GEOMED_FIN_THREADS = 1024;
 
-__global__ void __launch_bounds__(GEOMED_FIN_THREADS) k_geomed_finish(GeomedFinArgs A) {
-    __shared__ double sd[RULE_MAX_ARR], sa[RULE_MAX_ARR], sw[RULE_MAX_ARR], sterm[RULE_MAX_ARR];
-    __shared__ double ssum[2];
-    __shared__ int32_t sdead[RULE_MAX_ARR];
-    __shared__ unsigned long long smask[GEOMED_FIN_THREADS / 64];
-    __shared__ int32_t sgo;
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, k = A.k;
-    int it = 0;
-    if (A.pair > 0) {
-        it = A.pair - A.state[k + GEOMED_ST_REDO];
-        if (it >= A.iters) return;
-    }
-    for (int j = wave; j < k; j += GEOMED_FIN_THREADS / 64) {
+// A.partials [k + 1][nblocks] -> sd[j], j < k.  Entry j's sum belongs to one wave: lane l adds the
+// partials of the blocks l, l + 64, ... in index order (coalesced: the partials are slot-major) and
+// a butterfly adds the 64 lanes, as pair_matrix does -- a fixed order for a given (P, k).  No
+// barrier: the caller's next one publishes sd.
+template <class Args>
+__device__ __forceinline__ void entry_sums(const Args& A, double* sd) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int j = wave; j < A.k; j += GEOMED_FIN_THREADS / 64) {
         const double* src = A.partials + (long)j * A.nblocks;
         double a = 0.0;
 #pragma unroll 8
@@ -2569,19 +2657,50 @@ __global__ void __launch_bounds__(GEOMED_FIN_THREADS) k_geomed_finish(GeomedFinA
         for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
         if (lane == 0) sd[j] = a;
     }
-    if (A.pair == 0) {
-        const unsigned long long* src =
-            reinterpret_cast<const unsigned long long*>(A.partials) + (long)k * A.nblocks;
-        unsigned long long mk = 0;
-        for (int b = t; b < A.nblocks; b += GEOMED_FIN_THREADS) mk |= src[b];
+}
+
+// pair 0: the OR of the blocks' NaN masks (row k of the partials) through smask[16]; thread t < k
+// returns entry t's dead bit (t >= k: 0).  One barrier inside.
+template <class Args>
+__device__ __forceinline__ int32_t dead_mask(const Args& A, unsigned long long* smask) {
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, k = A.k;
+    const unsigned long long* src =
+        reinterpret_cast<const unsigned long long*>(A.partials) + (long)k * A.nblocks;
+    unsigned long long mk = 0;
+    for (int b = t; b < A.nblocks; b += GEOMED_FIN_THREADS) mk |= src[b];
 #pragma unroll
-        for (int o = 32; o > 0; o >>= 1) mk |= __shfl_xor(mk, o, 64);
-        if (lane == 0) smask[wave] = mk;
-        __syncthreads();
+    for (int o = 32; o > 0; o >>= 1) mk |= __shfl_xor(mk, o, 64);
+    if (lane == 0) smask[wave] = mk;
+    __syncthreads();
+    int32_t dead = 0;
+    if (t < k) {
+        unsigned long long all = 0;
+        for (int w = 0; w < GEOMED_FIN_THREADS / 64; ++w) all |= smask[w];
+        dead = (int32_t)((all >> t) & 1);
+    }
+    return dead;
+}
+
+// entry_sums; pair 0 also takes dead_mask, writes the dead flags and the control words, and w^(0)
+// over the live entries (the host's, bit for bit, when none is dead); with a dead entry its
+// distances are worthless (z was a NaN) and it stops there: "redo".  Then csrc/geomed.h's scalar
+// code of one iteration on the sums in LDS, and d2, obj and the next w.
+__global__ void __launch_bounds__(GEOMED_FIN_THREADS) k_geomed_finish(GeomedFinArgs A) {
+    __shared__ double sd[RULE_MAX_ARR], sa[RULE_MAX_ARR], sw[RULE_MAX_ARR], sterm[RULE_MAX_ARR];
+    __shared__ double ssum[2];
+    __shared__ int32_t sdead[RULE_MAX_ARR];
+    __shared__ unsigned long long smask[GEOMED_FIN_THREADS / 64];
+    __shared__ int32_t sgo;
+    const int t = threadIdx.x, k = A.k;
+    int it = 0;
+    if (A.pair > 0) {
+        it = A.pair - A.state[k + GEOMED_ST_REDO];
+        if (it >= A.iters) return;
+    }
+    entry_sums(A, sd);
+    if (A.pair == 0) {
+        const int32_t dead = dead_mask(A, smask);
         if (t < k) {
-            unsigned long long all = 0;
-            for (int w = 0; w < GEOMED_FIN_THREADS / 64; ++w) all |= smask[w];
-            const int32_t dead = (int32_t)((all >> t) & 1);
             sdead[t] = dead;
             A.state[t] = dead;
             sa[t] = geomed_alpha(A.weighted, A.count[t], dead);
@@ -2710,6 +2829,55 @@ static int check_geomed(const flsim_geomed* r) {
     FLSIM_REQUIRE(r->weighted == 0 || r->weighted == 1,
                   "Invalid weighted = %d: 0 (uniform) or 1 (count)", r->weighted);
     return check_counts(r->count, r->k);
+}
+
+// ---- the distance-to-iterate stage's host twin (geometric median, centered clipping) -------------
+// z as _wsum forms it: the center's term first (center nullable: none), then the entries' in index
+// order, one fp64 multiply and one add per term, zero weights skipped
+template <class M>
+static double wsum_host(M&& mean, const double* wt, int k, long e, const float* center = nullptr,
+                        double uw = 0.0) {
+    double z = 0.0;
+    bool have = false;
+    if (center && geomed_nonzero(uw)) {
+        volatile double t = (double)center[e] * uw;
+        z = t;
+        have = true;
+    }
+    for (int j = 0; j < k; ++j) {
+        if (!geomed_nonzero(wt[j])) continue;
+        volatile double t = (double)mean(j, e) * wt[j];
+        z = have ? z + t : (double)t;
+        have = true;
+    }
+    return z;
+}
+
+// dead[j]: entry j holds a mean that is not finite
+template <class M>
+static void dead_scan_host(M&& mean, int k, long P, int32_t* dead) {
+    for (int j = 0; j < k; ++j) {
+        dead[j] = 0;
+        for (long e = 0; e < P && !dead[j]; ++e) {
+            const float y = mean(j, e);
+            dead[j] = !(__builtin_fabsf(y) < __builtin_inff());
+        }
+    }
+}
+
+// d[j] = the fp64 sum of ((double)x_j - z(e))^2 over the live entries, in element order (one fma
+// each, as the kernels')
+template <class M, class Z>
+static void d2_host(M&& mean, Z&& z_of, const int32_t* dead, int k, long P, double* d) {
+    for (int j = 0; j < k; ++j) d[j] = 0.0;
+    for (long e = 0; e < P; ++e) {
+        const double z = z_of(e);
+        for (int j = 0; j < k; ++j) {
+            if (dead[j]) continue;
+            const double df = (double)mean(j, e) - z;
+            d[j] = __builtin_fma(df, df, d[j]);
+        }
+    }
 }
 
 // ================================================================================================
@@ -2929,52 +3097,13 @@ static void attack_eval_host(const flsim_attack* a, int kh, float* b_out, long P
 // neighbour selection, the mix in place (include/flsim.h: flsim_nnm; csrc/nnm.h: the geometry of
 // the mix, the selection and the element code shared with the host)
 // ================================================================================================
-// One block of KRUM_FIN_THREADS.  The first half is k_krum_finish's, statement for statement: pair
-// (i, j), i < j, belongs to one wave, lane l adds the partials of the blocks l, l + 64, ... in
-// index order, a butterfly adds the 64 lanes, a wave takes four pairs at a time; a NaN sum becomes
-// +inf, the value is mirrored, the diagonal is zero -- so for the same partials the two kernels
-// give the same matrix, bit for bit.  Then csrc/nnm.h's selection on the matrix in LDS: thread i
-// takes row i.
+// One block of KRUM_FIN_THREADS: pair_matrix (the pairwise-distance stage, Krum's matrix), then
+// csrc/nnm.h's selection on the matrix in LDS: thread i takes row i.
 __global__ void __launch_bounds__(KRUM_FIN_THREADS)
 k_nnm_finish(const double* partials, int nblocks, int nb, int k, int f, double* dist,
              uint64_t* nbr) {
     __shared__ double sd[RULE_MAX_ARR * RULE_MAX_ARR];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    constexpr int WAVES = KRUM_FIN_THREADS / 64;
-    constexpr int NLD = 12;
-    static_assert(krum_max_blocks(4) <= 64 * NLD && krum_max_blocks(64) <= 64 * NLD, "NLD");
-    auto lane_sum = [&](int idx) -> double {
-        const int i = idx / k, j = idx - i * k;
-        double a = 0.0;
-        if (idx < k * k && i < j) {
-            const double* src = partials + (long)krum_slot(i, j, nb) * nblocks;
-            double x[NLD];
-#pragma unroll
-            for (int u = 0; u < NLD; ++u) x[u] = lane + 64 * u < nblocks ? src[lane + 64 * u] : 0.0;
-#pragma unroll
-            for (int u = 0; u < NLD; ++u) a = lane + 64 * u < nblocks ? a + x[u] : a;
-        }
-        return a;
-    };
-    auto store = [&](int idx, double a) {
-        const int i = idx / k, j = idx - i * k;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
-        if (lane == 0 && idx < k * k && i <= j) {
-            a = a != a ? (double)__builtin_inff() : a;
-            sd[i * k + j] = a;                  // (the diagonal: no partial was added, 0)
-            sd[j * k + i] = a;
-        }
-    };
-    for (int base = wave; base < k * k; base += 4 * WAVES) {
-        double a[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) a[u] = lane_sum(base + u * WAVES);
-#pragma unroll
-        for (int u = 0; u < 4; ++u) store(base + u * WAVES, a[u]);
-    }
-    __syncthreads();
-    for (int idx = threadIdx.x; idx < k * k; idx += KRUM_FIN_THREADS) dist[idx] = sd[idx];
+    pair_matrix(partials, nblocks, nb, k, sd, dist);
     nnm_select(sd, nbr, k, f, (int)threadIdx.x, KRUM_FIN_THREADS);
 }
 
@@ -3289,41 +3418,21 @@ struct CclipFinArgs {
     int nblocks, k, pair, weighted;
 };
 
-// One block of 16 waves, the sums as k_geomed_finish takes them (entry j's sum belongs to one wave:
-// lane l adds the partials of the blocks l, l + 64, ... in index order, a butterfly adds the 64
-// lanes -- a fixed order for a given (P, k)).  Pair 0 also ORs the blocks' masks, writes the dead
-// flags and the control words, and u[0] = 1, w[0] = 0.  Then csrc/cclip.h's scalar code of one
-// iteration on the sums in LDS, and d2[r], s[r], u[r + 1] and w[r + 1].
+// One block of 16 waves: entry_sums; pair 0 also takes dead_mask, writes the dead flags and the
+// control words, and u[0] = 1, w[0] = 0.  Then csrc/cclip.h's scalar code of one iteration on the
+// sums in LDS, and d2[r], s[r], u[r + 1] and w[r + 1].
 __global__ void __launch_bounds__(GEOMED_FIN_THREADS) k_cclip_finish(CclipFinArgs A) {
     __shared__ double sd[RULE_MAX_ARR], sa[RULE_MAX_ARR], sw[RULE_MAX_ARR], ss[RULE_MAX_ARR];
     __shared__ double sterm[RULE_MAX_ARR], swn[RULE_MAX_ARR];
     __shared__ double ssum[CCLIP_SUM_WORDS];
     __shared__ int32_t sdead[RULE_MAX_ARR];
     __shared__ unsigned long long smask[GEOMED_FIN_THREADS / 64];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, k = A.k, r = A.pair;
-    for (int j = wave; j < k; j += GEOMED_FIN_THREADS / 64) {
-        const double* src = A.partials + (long)j * A.nblocks;
-        double a = 0.0;
-#pragma unroll 8
-        for (int b = lane; b < A.nblocks; b += 64) a += src[b];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
-        if (lane == 0) sd[j] = a;
-    }
+    const int t = threadIdx.x, k = A.k, r = A.pair;
+    entry_sums(A, sd);
     double u = 1.0;
     if (r == 0) {
-        const unsigned long long* src =
-            reinterpret_cast<const unsigned long long*>(A.partials) + (long)k * A.nblocks;
-        unsigned long long mk = 0;
-        for (int b = t; b < A.nblocks; b += GEOMED_FIN_THREADS) mk |= src[b];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) mk |= __shfl_xor(mk, o, 64);
-        if (lane == 0) smask[wave] = mk;
-        __syncthreads();
+        const int32_t dead = dead_mask(A, smask);
         if (t < k) {
-            unsigned long long all = 0;
-            for (int w = 0; w < GEOMED_FIN_THREADS / 64; ++w) all |= smask[w];
-            const int32_t dead = (int32_t)((all >> t) & 1);
             sdead[t] = dead;
             A.state[t] = dead;
             sa[t] = geomed_alpha(A.weighted, A.count[t], dead);
@@ -3922,8 +4031,7 @@ int flsim_robust_eval_host(const flsim_robust* r, long P, float* g_out) {
 // ---- Krum / Multi-Krum over bucket means + the update (include/flsim.h) --------------------------
 long flsim_krum_partials(long P, int k) {
     if (k < 1 || k > RULE_MAX_ARR || P < 1 || P >= (1L << 31)) return 0;
-    const int kpad = krum_kpad(k);
-    return krum_blocks(P, kpad) * krum_npb(kpad) * 16;
+    return pair_partials(P, k);
 }
 
 long flsim_krum_tile_elems(int k) {
@@ -3941,52 +4049,28 @@ int flsim_krum_optim_step(const flsim_krum* r, const flsim_krum_scratch* s, cons
     BucketStep B;
     RC(step_begin(optim, clip, g_out, p, m, v, P, step, &B));
     static const char name[] = "Krum";
-    FLSIM_REQUIRE(s && s->partials && s->dist && s->score && s->sel, "null Krum scratch");
-    FLSIM_REQUIRE((((uintptr_t)s->partials | (uintptr_t)s->dist | (uintptr_t)s->score |
-                    (uintptr_t)s->sel) & 15) == 0, "Krum scratch must be 16-byte aligned");
-    const int kpad = krum_kpad(r->k);
-    const long nblocks = krum_blocks(P, kpad);
-    const long n_dist = nblocks * krum_npb(kpad) * 16;
-    FLSIM_REQUIRE(s->n_partials >= n_dist, "Krum n_partials = %ld, this step writes %ld",
-                  s->n_partials, n_dist);
+    const flsim_krum_scratch none{};
+    if (!s) s = &none;
+    const long n_dist = pair_partials(P, r->k);
     constexpr int NS = 4;
     const Span sc[NS] = {{s->partials, 8 * n_dist},
                          {s->dist, 8L * r->k * r->k},
                          {s->score, 8L * r->k},
                          {s->sel, 4L * r->m}};
+    RC(check_scratch_pointers(name, sc, NS, s->n_partials, n_dist));
     RC(check_scratch(B, name, sc, NS, nullptr));
     RC(check_clip_buffers(B, nullptr));
-    KrumDistArgs D{};
     KrumApplyArgs A{};
     int distinct = 0;
-    RC(fill_entries(B, r->entries, r->count, r->k, name, sc, NS, nullptr, &D.T, &distinct));
-    A.T = D.T;
-    D.partials = s->partials;
-    D.P = P;
-    D.k = r->k;
-    D.ntiles = (int)krum_tiles(P, kpad);
-    {
-        const ProbeSlot ps = probe_begin();
-        const dim3 grid((unsigned)nblocks);
-        with_kpad<4>(kpad, [&](auto kp) {
-            constexpr int KPAD = decltype(kp)::value;
-            hipExtLaunchKernelGGL((k_krum_dist<KPAD>), grid, dim3(KrumGeom<KPAD>::NT), 0, stream,
-                                  ps.start, ps.stop, 0, D);
-        });
-        FLSIM_LAUNCH_CHECK();
-        // algorithmic HBM bytes: each distinct entry read once
-        if (probe_end(ps, K_KRUM_DIST, 4.0 * (double)P * distinct)) return 2;
-    }
-    {
-        const ProbeSlot ps = probe_begin();
-        hipExtLaunchKernelGGL(k_krum_finish, dim3(1), dim3(KRUM_FIN_THREADS), 0, stream, ps.start,
-                              ps.stop, 0, (const double*)s->partials, (int)nblocks, kpad / 4,
-                              (int)r->k, (int)r->f, (int)r->m, s->dist, s->score, s->sel);
-        FLSIM_LAUNCH_CHECK();
-        if (probe_end(ps, K_KRUM_FIN, 8.0 * (double)nblocks * (r->k * (r->k - 1) / 2) +
-                                          8.0 * r->k * (r->k + 1) + 4.0 * r->m))
-            return 2;
-    }
+    RC(fill_entries(B, r->entries, r->count, r->k, name, sc, NS, nullptr, &A.T, &distinct));
+    // the finish launch's own bytes: sel written
+    RC(launch_pair_dist(A.T, s->partials, P, r->k, K_KRUM_DIST, distinct, K_KRUM_FIN, 4.0 * r->m,
+                        stream, [&](const ProbeSlot& ps, const double* part, int nblocks, int nb) {
+                            hipExtLaunchKernelGGL(k_krum_finish, dim3(1), dim3(KRUM_FIN_THREADS), 0,
+                                                  stream, ps.start, ps.stop, 0, part, nblocks, nb,
+                                                  (int)r->k, (int)r->f, (int)r->m, s->dist,
+                                                  s->score, s->sel);
+                        }));
     A.sel = s->sel;
     A.nsel = r->m;
     A.fm = (float)r->m;
@@ -4008,24 +4092,8 @@ int flsim_krum_eval_host(const flsim_krum* r, long P, double* dist, double* scor
     FLSIM_REQUIRE(dist && score && sel, "null pointer");
     FLSIM_REQUIRE(P > 0, "P = %ld out of range", P);
     const int k = r->k;
-    auto mean = [&](int j, long e) -> float {
-        volatile float x = r->entries[j] ? r->entries[j][e] : 0.f;
-        volatile float c = (float)r->count[j];
-        return x / c;
-    };
-    for (int i = 0; i < k; ++i) {
-        dist[(long)i * k + i] = 0.0;
-        for (int j = i + 1; j < k; ++j) {
-            double a = 0.0;
-            for (long e = 0; e < P; ++e) {
-                const double d = (double)mean(i, e) - (double)mean(j, e);
-                a = __builtin_fma(d, d, a);
-            }
-            a = a != a ? (double)__builtin_inff() : a;
-            dist[(long)i * k + j] = a;
-            dist[(long)j * k + i] = a;
-        }
-    }
+    auto mean = [&](int j, long e) { return bucket_mean(r->entries, r->count, j, e); };
+    pair_dist_host(mean, k, P, dist);
     int32_t rank[RULE_MAX_ARR];
     krum_score_select(dist, score, rank, sel, k, (int)r->f, (int)r->m, 0, 1, [] {});
     if (!g_out) return 0;
@@ -4060,17 +4128,12 @@ int flsim_geomed_optim_step(const flsim_geomed* r, const flsim_geomed_scratch* s
     BucketStep B;
     RC(step_begin(optim, clip, g_out, p, m, v, P, step, &B));
     static const char name[] = "geometric-median";
-    FLSIM_REQUIRE(s && s->partials && s->w && s->d2 && s->obj && s->state,
-                  "null geometric-median scratch");
-    FLSIM_REQUIRE((((uintptr_t)s->partials | (uintptr_t)s->w | (uintptr_t)s->d2 |
-                    (uintptr_t)s->obj | (uintptr_t)s->state) & 15) == 0,
-                  "geometric-median scratch must be 16-byte aligned");
+    const flsim_geomed_scratch none{};
+    if (!s) s = &none;
     const int k = r->k, iters = r->iters;
     const int kpad = geomed_kpad(k);
     const long nblocks = geomed_blocks(P, kpad);
     const long n_dist = nblocks * (k + 1);
-    FLSIM_REQUIRE(s->n_partials >= n_dist,
-                  "geometric-median n_partials = %ld, this step writes %ld", s->n_partials, n_dist);
     // (a buffer of no bytes -- d2 and obj at iters = 0 -- overlaps nothing)
     constexpr int NS = 5;
     const Span sc[NS] = {{s->partials, 8 * n_dist},
@@ -4078,6 +4141,7 @@ int flsim_geomed_optim_step(const flsim_geomed* r, const flsim_geomed_scratch* s
                          {s->d2, 8L * iters * k},
                          {s->obj, 8L * iters},
                          {s->state, 4L * (k + GEOMED_ST_WORDS)}};
+    RC(check_scratch_pointers(name, sc, NS, s->n_partials, n_dist));
     RC(check_scratch(B, name, sc, NS, nullptr));
     RC(check_clip_buffers(B, nullptr));
     GeomedDistArgs D{};
@@ -4153,44 +4217,16 @@ int flsim_geomed_eval_host(const flsim_geomed* r, long P, double* w, double* d2,
     const int k = r->k, iters = r->iters;
     FLSIM_REQUIRE(w && (iters == 0 || (d2 && obj)), "null pointer");
     FLSIM_REQUIRE(P > 0, "P = %ld out of range", P);
-    auto mean = [&](int j, long e) -> float {
-        volatile float x = r->entries[j] ? r->entries[j][e] : 0.f;
-        volatile float c = (float)r->count[j];
-        return x / c;
-    };
-    auto wsum = [&](const double* wt, long e) -> double {
-        double z = 0.0;
-        bool have = false;
-        for (int j = 0; j < k; ++j) {
-            if (!geomed_nonzero(wt[j])) continue;
-            volatile double t = (double)mean(j, e) * wt[j];
-            z = have ? z + t : (double)t;
-            have = true;
-        }
-        return z;
-    };
+    auto mean = [&](int j, long e) { return bucket_mean(r->entries, r->count, j, e); };
+    auto wsum = [&](const double* wt, long e) { return wsum_host(mean, wt, k, e); };
     int32_t dead[RULE_MAX_ARR];
     double a[RULE_MAX_ARR], term[RULE_MAX_ARR], sums[2];
-    for (int j = 0; j < k; ++j) {
-        dead[j] = 0;
-        for (long e = 0; e < P && !dead[j]; ++e) {
-            const float y = mean(j, e);
-            dead[j] = !(__builtin_fabsf(y) < __builtin_inff());
-        }
-        a[j] = geomed_alpha(r->weighted, r->count[j], dead[j]);
-    }
+    dead_scan_host(mean, k, P, dead);
+    for (int j = 0; j < k; ++j) a[j] = geomed_alpha(r->weighted, r->count[j], dead[j]);
     geomed_w0(a, k, w);
     for (int it = 0; it < iters; ++it) {
         double* d = d2 + (long)it * k;
-        for (int j = 0; j < k; ++j) d[j] = 0.0;
-        for (long e = 0; e < P; ++e) {
-            const double z = wsum(w + (long)it * k, e);
-            for (int j = 0; j < k; ++j) {
-                if (dead[j]) continue;
-                const double df = (double)mean(j, e) - z;
-                d[j] = __builtin_fma(df, df, d[j]);
-            }
-        }
+        d2_host(mean, [&](long e) { return wsum(w + (long)it * k, e); }, dead, k, P, d);
         geomed_iterate(d, a, dead, k, r->nu, term, sums, w + (long)(it + 1) * k, 0, 1, [] {});
         obj[it] = sums[0];
     }
@@ -4250,7 +4286,7 @@ int flsim_attack_eval_host(const flsim_attack* a, float* b_out, long P) {
 }
 
 // ---- nearest-neighbour mixing of the entries, in place (include/flsim.h) --------------------------
-long flsim_nnm_partials(long P, int k) { return flsim_krum_partials(P, k); }
+long flsim_nnm_partials(long P, int k) { return flsim_krum_partials(P, k); }   // (pair_partials)
 
 long flsim_nnm_tile_elems(int k) {
     if (k < 1 || k > RULE_MAX_ARR) return 0;
@@ -4268,61 +4304,36 @@ int flsim_nnm_entries(const flsim_nnm* a, const flsim_nnm_scratch* s, long P, hi
         FLSIM_REQUIRE(((uintptr_t)a->entries[j] & 15) == 0, "entry %d must be 16-byte aligned", j);
     }
     FLSIM_REQUIRE(P > 0 && P < (1L << 31), "P = %ld out of range", P);
-    FLSIM_REQUIRE(s && s->partials && s->dist && s->nbr, "null NNM scratch");
-    FLSIM_REQUIRE((((uintptr_t)s->partials | (uintptr_t)s->dist | (uintptr_t)s->nbr) & 15) == 0,
-                  "NNM scratch must be 16-byte aligned");
-    const int kpad = krum_kpad(k);
-    const long nblocks = krum_blocks(P, kpad);
-    const long n_dist = nblocks * krum_npb(kpad) * 16;
-    FLSIM_REQUIRE(s->n_partials >= n_dist, "NNM n_partials = %ld, this step writes %ld",
-                  s->n_partials, n_dist);
+    static const char name[] = "NNM";
+    const flsim_nnm_scratch none{};
+    if (!s) s = &none;
+    const long n_dist = pair_partials(P, k);
     constexpr int NS = 3;
     const Span sc[NS] = {{s->partials, 8 * n_dist}, {s->dist, 8L * k * k}, {s->nbr, 8L * k}};
+    RC(check_scratch_pointers(name, sc, NS, s->n_partials, n_dist));
     for (int j = 0; j < k; ++j)
         for (int q = 0; q < j; ++q)
             FLSIM_REQUIRE(!overlaps(a->entries[q], a->entries[j], P), "entries %d and %d overlap",
                           q, j);
-    for (int j = 0; j < k; ++j)
-        for (int b = 0; b < NS; ++b)
-            FLSIM_REQUIRE(!overlaps(a->entries[j], 4 * P, sc[b].ptr, sc[b].bytes),
-                          "entry %d overlaps the NNM scratch", j);
-    for (int b = 0; b < NS; ++b)
-        for (int c = b + 1; c < NS; ++c)
-            FLSIM_REQUIRE(!overlaps(sc[b].ptr, sc[b].bytes, sc[c].ptr, sc[c].bytes),
-                          "NNM scratch buffers overlap each other");
-    KrumDistArgs D{};
+    // no p / m / v / clip here: the entries against the scratch, then the scratch against itself
+    StepBuffers B{};
+    B.P = P;
+    EntryTable T{};
     NnmMixArgs M{};
+    int distinct = 0;                   // k: no entry is null, none overlaps another
+    RC(fill_entries(B, a->entries, a->count, k, name, sc, NS, nullptr, &T, &distinct));
+    RC(check_scratch(B, name, sc, NS, nullptr));
     for (int j = 0; j < k; ++j) {
-        volatile float one = 1.f, c = (float)a->count[j];      // RN(1 / count) in fp32
-        D.T.ent[j] = M.ent[j] = a->entries[j];
-        D.T.cnt[j] = M.cnt[j] = c;
-        D.T.rcnt[j] = M.rcnt[j] = one / c;
+        M.ent[j] = a->entries[j];
+        M.cnt[j] = T.cnt[j];
+        M.rcnt[j] = T.rcnt[j];
     }
-    D.partials = s->partials;
-    D.P = P;
-    D.k = k;
-    D.ntiles = (int)krum_tiles(P, kpad);
-    {
-        const ProbeSlot ps = probe_begin();
-        const dim3 grid((unsigned)nblocks);
-        with_kpad<4>(kpad, [&](auto kp) {
-            constexpr int KPAD = decltype(kp)::value;
-            hipExtLaunchKernelGGL((k_krum_dist<KPAD>), grid, dim3(KrumGeom<KPAD>::NT), 0, stream,
-                                  ps.start, ps.stop, 0, D);
-        });
-        FLSIM_LAUNCH_CHECK();
-        // algorithmic HBM bytes: each entry read once
-        if (probe_end(ps, K_NNM_DIST, 4.0 * (double)P * k)) return 2;
-    }
-    {
-        const ProbeSlot ps = probe_begin();
-        hipExtLaunchKernelGGL(k_nnm_finish, dim3(1), dim3(KRUM_FIN_THREADS), 0, stream, ps.start,
-                              ps.stop, 0, (const double*)s->partials, (int)nblocks, kpad / 4, k,
-                              (int)a->f, s->dist, s->nbr);
-        FLSIM_LAUNCH_CHECK();
-        if (probe_end(ps, K_NNM_FIN, 8.0 * (double)nblocks * (k * (k - 1) / 2) + 8.0 * k * (k + 1)))
-            return 2;
-    }
+    RC(launch_pair_dist(T, s->partials, P, k, K_NNM_DIST, distinct, K_NNM_FIN, 0.0, stream,
+                        [&](const ProbeSlot& ps, const double* part, int nblocks, int nb) {
+                            hipExtLaunchKernelGGL(k_nnm_finish, dim3(1), dim3(KRUM_FIN_THREADS), 0,
+                                                  stream, ps.start, ps.stop, 0, part, nblocks, nb,
+                                                  k, (int)a->f, s->dist, s->nbr);
+                        }));
     M.nbr = s->nbr;
     M.P = P;
     M.k = k;
@@ -4353,24 +4364,8 @@ int flsim_nnm_eval_host(const flsim_nnm* a, long P, double* dist, uint64_t* nbr,
     for (int j = 0; j < k; ++j) FLSIM_REQUIRE(a->entries[j], "null entry %d", j);
     FLSIM_REQUIRE(dist && nbr, "null pointer");
     FLSIM_REQUIRE(P > 0, "P = %ld out of range", P);
-    auto mean = [&](int j, long e) -> float {
-        volatile float x = a->entries[j][e];
-        volatile float c = (float)a->count[j];
-        return x / c;
-    };
-    for (int i = 0; i < k; ++i) {
-        dist[(long)i * k + i] = 0.0;
-        for (int j = i + 1; j < k; ++j) {
-            double acc = 0.0;
-            for (long e = 0; e < P; ++e) {
-                const double d = (double)mean(i, e) - (double)mean(j, e);
-                acc = __builtin_fma(d, d, acc);
-            }
-            acc = acc != acc ? (double)__builtin_inff() : acc;
-            dist[(long)i * k + j] = acc;
-            dist[(long)j * k + i] = acc;
-        }
-    }
+    auto mean = [&](int j, long e) { return bucket_mean(a->entries, a->count, j, e); };
+    pair_dist_host(mean, k, P, dist);
     nnm_select(dist, nbr, k, (int)a->f, 0, 1);
     if (!out) return 0;
     const float fn = (float)(k - a->f);
@@ -4412,21 +4407,17 @@ int flsim_cclip_optim_step(const flsim_cclip* r, const flsim_cclip_scratch* s,
     FLSIM_REQUIRE(((uintptr_t)center & 15) == 0, "centered-clipping center must be 16-byte aligned");
     for (const float* o : B.outs)
         FLSIM_REQUIRE(!overlaps(center, o, P), "centered-clipping center overlaps p/m/v/g_out");
-    FLSIM_REQUIRE(s && s->partials && s->u && s->w && s->d2 && s->s && s->state,
-                  "null centered-clipping scratch");
-    FLSIM_REQUIRE((((uintptr_t)s->partials | (uintptr_t)s->u | (uintptr_t)s->w | (uintptr_t)s->d2 |
-                    (uintptr_t)s->s | (uintptr_t)s->state) & 15) == 0,
-                  "centered-clipping scratch must be 16-byte aligned");
+    const flsim_cclip_scratch none{};
+    if (!s) s = &none;
     const int k = r->k, iters = r->iters;
     const int kpad = geomed_kpad(k);
     const long nblocks = geomed_blocks(P, kpad);
     const long n_dist = nblocks * (k + 1);
-    FLSIM_REQUIRE(s->n_partials >= n_dist,
-                  "centered-clipping n_partials = %ld, this step writes %ld", s->n_partials, n_dist);
     constexpr int NS = 6;
     const Span sc[NS] = {{s->partials, 8 * n_dist},      {s->u, 8L * (iters + 1)},
                          {s->w, 8L * (iters + 1) * k},   {s->d2, 8L * iters * k},
                          {s->s, 8L * iters * k},         {s->state, 4L * (k + CCLIP_ST_WORDS)}};
+    RC(check_scratch_pointers(name, sc, NS, s->n_partials, n_dist));
     RC(check_scratch(B, name, sc, NS, center));
     RC(check_clip_buffers(B, center));
     CclipDistArgs D{};
@@ -4501,50 +4492,21 @@ int flsim_cclip_eval_host(const flsim_cclip* r, long P, double* u, double* w, do
     FLSIM_REQUIRE(u && w && d2 && s, "null pointer");
     FLSIM_REQUIRE(fresh || r->center, "null centered-clipping center");
     FLSIM_REQUIRE(P > 0, "P = %ld out of range", P);
-    auto mean = [&](int j, long e) -> float {
-        volatile float x = r->entries[j] ? r->entries[j][e] : 0.f;
-        volatile float c = (float)r->count[j];
-        return x / c;
-    };
-    auto wsum = [&](double uw, const double* wt, long e) -> double {
-        double z = 0.0;
-        bool have = false;
-        if (!fresh && geomed_nonzero(uw)) {
-            volatile double t = (double)r->center[e] * uw;
-            z = t;
-            have = true;
-        }
-        for (int j = 0; j < k; ++j) {
-            if (!geomed_nonzero(wt[j])) continue;
-            volatile double t = (double)mean(j, e) * wt[j];
-            z = have ? z + t : (double)t;
-            have = true;
-        }
-        return z;
+    auto mean = [&](int j, long e) { return bucket_mean(r->entries, r->count, j, e); };
+    auto wsum = [&](double uw, const double* wt, long e) {
+        return wsum_host(mean, wt, k, e, fresh ? nullptr : r->center, uw);
     };
     int32_t dead[RULE_MAX_ARR];
     double a[RULE_MAX_ARR], term[RULE_MAX_ARR], sums[CCLIP_SUM_WORDS];
+    dead_scan_host(mean, k, P, dead);
     for (int j = 0; j < k; ++j) {
-        dead[j] = 0;
-        for (long e = 0; e < P && !dead[j]; ++e) {
-            const float y = mean(j, e);
-            dead[j] = !(__builtin_fabsf(y) < __builtin_inff());
-        }
         a[j] = geomed_alpha(r->weighted, r->count[j], dead[j]);
         w[j] = 0.0;
     }
     u[0] = 1.0;
     for (int it = 0; it < iters; ++it) {
         double* d = d2 + (long)it * k;
-        for (int j = 0; j < k; ++j) d[j] = 0.0;
-        for (long e = 0; e < P; ++e) {
-            const double z = wsum(u[it], w + (long)it * k, e);
-            for (int j = 0; j < k; ++j) {
-                if (dead[j]) continue;
-                const double df = (double)mean(j, e) - z;
-                d[j] = __builtin_fma(df, df, d[j]);
-            }
-        }
+        d2_host(mean, [&](long e) { return wsum(u[it], w + (long)it * k, e); }, dead, k, P, d);
         cclip_iterate(d, a, dead, k, r->tau, u[it], w + (long)it * k, s + (long)it * k, term, sums,
                       w + (long)(it + 1) * k, 0, 1, [] {});
         u[it + 1] = sums[CCLIP_SUM_U];

@@ -912,10 +912,17 @@ def aggregate_rule(S, rule, theta, m, v, step, sizes, lr=1e-3, betas=(0.9, 0.999
 
 
 class _BucketRule:
-    """What the rules over bucket / class sums share: the entries and their counts, checked as
-    every rule checks them (_what and _kmin: the rule's words in the message), and their fields
-    in the rule's C struct.  center and c_scratch: the rules that have one override them."""
+    """What the objects over bucket / class sums share (the four rules, Attack, NNM): the entries
+    and their counts, checked as every rule checks them (_what and _kmin: the object's words in
+    the message), their fields in the C struct, and the scratch of those that have one.  center:
+    the rule that has one overrides it.
+
+    A class with scratch names its C struct (_scratch_struct) and the library function that sizes
+    the partials (_partials), and describes the other buffers in _scratch_rows; c_scratch allocates
+    them per key in the class's own _scratch dictionary, as (partials, *rows)."""
     _what, _kmin = None, 1
+    _bad_count = 0      # what a count the int32 field cannot hold becomes: the library refuses it
+    _scratch_struct = _partials = None
     center = None
 
     def _set_entries(self, entries, counts):
@@ -931,17 +938,44 @@ class _BucketRule:
     def k(self):
         return len(self.entries)
 
-    def _fill_entries(self, r):
-        """k, entries[] and count[] of the rule's C struct r; returns r."""
+    def _fill_entries(self, r, **counts):
+        """k, entries[] and the count fields of the C struct r (count = self.counts unless other
+        fields are named); returns r."""
         r.k = len(self.entries)
-        for j, (e, c) in enumerate(zip(self.entries, self.counts)):
+        for j, e in enumerate(self.entries):
             r.entries[j] = e.data_ptr() if e is not None else None
-            # (an int32 field: a count it cannot hold is refused as the library refuses one < 1)
-            r.count[j] = c if -2 ** 31 <= c < 2 ** 31 else 0
+        for field, cs in (counts or {"count": self.counts}).items():
+            for j, c in enumerate(cs):
+                # (an int32 field: a count it cannot hold becomes one the library refuses)
+                getattr(r, field)[j] = c if -2 ** 31 <= c < 2 ** 31 else self._bad_count
         return r
 
+    def _scratch_rows(self, k):
+        """-> (the key's tail after (device, P, k), rows); a row is (the struct's field, the
+        object's attribute, dtype, elements allocated, the shape of the view exposed)."""
+        raise NotImplementedError
+
     def c_scratch(self, device, P):
-        return None
+        """The class's scratch struct over this device's scratch for a call over P elements (None
+        for a class that has none); the views of its rows become the object's attributes."""
+        if self._scratch_struct is None:
+            return None
+        k = len(self.entries)
+        tail, rows = self._scratch_rows(k)
+        cache, key = type(self)._scratch, (str(device), int(P), k) + tail
+        if key not in cache:
+            n = max(int(getattr(lib(), self._partials)(int(P), k)), 2)
+            cache[key] = (torch.empty(n, dtype=torch.float64, device=device),
+                          *(torch.empty(alloc, dtype=dt, device=device)
+                            for _, _, dt, alloc, _ in rows))
+        s = self._scratch_struct()
+        self.partials = cache[key][0]
+        s.partials = self.partials.data_ptr()
+        s.n_partials = int(self.partials.numel())
+        for (field, attr, _, _, shape), buf in zip(rows, cache[key][1:]):
+            setattr(s, field, buf.data_ptr())
+            setattr(self, attr, buf[:math.prod(shape)].view(shape))
+        return s
 
 
 def _bucket_step(fn, rule, theta, m, v, step, P, lr, betas, eps, optim, clip, g_out):
@@ -1004,6 +1038,7 @@ class Krum(_BucketRule):
     flsim/robust.py is the rule's text."""
     _scratch = {}       # (device, P, k) -> buffers, shared by the objects of a run
     _what, _kmin = "Krum", 3
+    _scratch_struct, _partials = FlsimKrumScratch, "flsim_krum_partials"
 
     def __init__(self, f, m, entries, counts):
         self._set_entries(entries, counts)
@@ -1015,28 +1050,11 @@ class Krum(_BucketRule):
         r.f, r.m = self.f, self.m
         return self._fill_entries(r)
 
-    def c_scratch(self, device, P):
-        """flsim_krum_scratch over this device's scratch for a step over P elements."""
-        k = len(self.entries)
-        key = (str(device), int(P), k)
-        if key not in Krum._scratch:
-            n = max(int(lib().flsim_krum_partials(int(P), k)), 2)
-            Krum._scratch[key] = (torch.empty(n, dtype=torch.float64, device=device),
-                                  torch.empty(k * k + 2, dtype=torch.float64, device=device),
-                                  torch.empty(k + 2, dtype=torch.float64, device=device),
-                                  torch.empty(MAX_ARRAYS, dtype=torch.int32, device=device))
-        partials, dist, score, sel = Krum._scratch[key]
-        s = FlsimKrumScratch()
-        s.partials = partials.data_ptr()
-        s.n_partials = int(partials.numel())
-        s.dist = dist.data_ptr()
-        s.score = score.data_ptr()
-        s.sel = sel.data_ptr()
-        self.partials = partials
-        self.dist = dist[:k * k].view(k, k)
-        self.score = score[:k]
-        self.sel = sel[:max(min(self.m, MAX_ARRAYS), 0)]
-        return s
+    def _scratch_rows(self, k):
+        f64 = torch.float64
+        return (), (("dist", "dist", f64, k * k + 2, (k, k)),
+                    ("score", "score", f64, k + 2, (k,)),
+                    ("sel", "sel", torch.int32, MAX_ARRAYS, (max(min(self.m, MAX_ARRAYS), 0),)))
 
 
 def krum_step(krum, theta, m, v, step, P=None, lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
@@ -1058,6 +1076,7 @@ class GeoMed(_BucketRule):
     flsim/robust.py is the rule's text."""
     _scratch = {}       # (device, P, k, iters) -> buffers, shared by the objects of a run
     _what = "geometric median"
+    _scratch_struct, _partials = FlsimGeomedScratch, "flsim_geomed_partials"
 
     def __init__(self, iters, nu, weighted, entries, counts):
         self._set_entries(entries, counts)
@@ -1070,32 +1089,12 @@ class GeoMed(_BucketRule):
         r.nu = self.nu
         return self._fill_entries(r)
 
-    def c_scratch(self, device, P):
-        """flsim_geomed_scratch over this device's scratch for a step over P elements."""
-        k = len(self.entries)
-        it = max(min(self.iters, 32), 0)
-        key = (str(device), int(P), k, it)
-        if key not in GeoMed._scratch:
-            n = max(int(lib().flsim_geomed_partials(int(P), k)), 2)
-            GeoMed._scratch[key] = (torch.empty(n, dtype=torch.float64, device=device),
-                                    torch.empty((it + 1) * k + 2, dtype=torch.float64, device=device),
-                                    torch.empty(it * k + 2, dtype=torch.float64, device=device),
-                                    torch.empty(it + 2, dtype=torch.float64, device=device),
-                                    torch.empty(k + 4 + 4, dtype=torch.int32, device=device))
-        partials, w, d2, obj, state = GeoMed._scratch[key]
-        s = FlsimGeomedScratch()
-        s.partials = partials.data_ptr()
-        s.n_partials = int(partials.numel())
-        s.w = w.data_ptr()
-        s.d2 = d2.data_ptr()
-        s.obj = obj.data_ptr()
-        s.state = state.data_ptr()
-        self.partials = partials
-        self.w = w[:(it + 1) * k].view(it + 1, k)
-        self.d2 = d2[:it * k].view(it, k)
-        self.obj = obj[:it]
-        self.dead = state[:k]
-        return s
+    def _scratch_rows(self, k):
+        it, f64 = max(min(self.iters, 32), 0), torch.float64
+        return (it,), (("w", "w", f64, (it + 1) * k + 2, (it + 1, k)),
+                       ("d2", "d2", f64, it * k + 2, (it, k)),
+                       ("obj", "obj", f64, it + 2, (it,)),
+                       ("state", "dead", torch.int32, k + 4 + 4, (k,)))
 
 
 def geomed_step(geomed, theta, m, v, step, P=None, lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
@@ -1120,6 +1119,7 @@ class CClip(_BucketRule):
     order; the next step overwrites them.  flsim/robust.py is the rule's text."""
     _scratch = {}       # (device, P, k, iters) -> buffers, shared by the objects of a run
     _what = "centered clipping"
+    _scratch_struct, _partials = FlsimCclipScratch, "flsim_cclip_partials"
 
     def __init__(self, tau, iters, weighted, entries, counts, center, fresh=False):
         self._set_entries(entries, counts)
@@ -1134,34 +1134,13 @@ class CClip(_BucketRule):
         r.center = self.center.data_ptr() if self.center is not None else None
         return self._fill_entries(r)
 
-    def c_scratch(self, device, P):
-        """flsim_cclip_scratch over this device's scratch for a step over P elements."""
-        k = len(self.entries)
-        it = max(min(self.iters, 32), 1)
-        key = (str(device), int(P), k, it)
-        if key not in CClip._scratch:
-            n = max(int(lib().flsim_cclip_partials(int(P), k)), 2)
-            f64 = dict(dtype=torch.float64, device=device)
-            CClip._scratch[key] = (torch.empty(n, **f64), torch.empty(it + 1 + 2, **f64),
-                                   torch.empty((it + 1) * k + 2, **f64),
-                                   torch.empty(it * k + 2, **f64), torch.empty(it * k + 2, **f64),
-                                   torch.empty(k + 4 + 4, dtype=torch.int32, device=device))
-        partials, u, w, d2, sc, state = CClip._scratch[key]
-        s = FlsimCclipScratch()
-        s.partials = partials.data_ptr()
-        s.n_partials = int(partials.numel())
-        s.u = u.data_ptr()
-        s.w = w.data_ptr()
-        s.d2 = d2.data_ptr()
-        s.s = sc.data_ptr()
-        s.state = state.data_ptr()
-        self.partials = partials
-        self.u = u[:it + 1]
-        self.w = w[:(it + 1) * k].view(it + 1, k)
-        self.d2 = d2[:it * k].view(it, k)
-        self.s = sc[:it * k].view(it, k)
-        self.dead = state[:k]
-        return s
+    def _scratch_rows(self, k):
+        it, f64 = max(min(self.iters, 32), 1), torch.float64
+        return (it,), (("u", "u", f64, it + 1 + 2, (it + 1,)),
+                       ("w", "w", f64, (it + 1) * k + 2, (it + 1, k)),
+                       ("d2", "d2", f64, it * k + 2, (it, k)),
+                       ("s", "s", f64, it * k + 2, (it, k)),
+                       ("state", "dead", torch.int32, k + 4 + 4, (k,)))
 
 
 def cclip_step(cclip, theta, m, v, step, P=None, lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
@@ -1173,40 +1152,29 @@ def cclip_step(cclip, theta, m, v, step, P=None, lr=1e-3, betas=(0.9, 0.999), ep
                  clip, g_out)
 
 
-class Attack:
+class Attack(_BucketRule):
     """Simulated Byzantine workers over bucket sums (flsim_attack, include/flsim.h): kind "ipm"
     (every Byzantine worker sends -strength * mu) or "alie" (mu - strength * sigma), mu and sigma
     the coordinate-wise mean and population standard deviation of entries[j] / honest[j] over the
     entries with honest[j] >= 1.  entries: flat fp32 device tensors of the same length, updated in
     place where byz[j] >= 1 (never read where honest[j] == 0); honest, byz: the workers of either
     side summed into each.  flsim/robust.py (attack_flat) is the text."""
+    _what, _bad_count = "attack", -1
 
     def __init__(self, kind, strength, entries, honest, byz):
-        entries = list(entries)
-        honest, byz = [int(c) for c in honest], [int(c) for c in byz]
+        entries, honest, byz = list(entries), list(honest), [int(c) for c in byz]
         if len(entries) != len(honest) or len(entries) != len(byz):
             raise ValueError(f"{len(honest)} honest and {len(byz)} Byzantine counts for "
                              f"{len(entries)} entries")
-        if len(entries) > MAX_ARRAYS:
-            raise ValueError(f"attack over k = {len(entries)} entries (1 .. {MAX_ARRAYS})")
+        self._set_entries(entries, honest)      # (its counts are the honest side's)
         self.kind, self.strength = kind, float(strength)
-        self.entries, self.honest, self.byz = entries, honest, byz   # (keeps the tensors alive)
-
-    @property
-    def k(self):
-        return len(self.entries)
+        self.honest, self.byz = self.counts, byz
 
     def c_struct(self):
         a = FlsimAttack()
         a.kind = ATTACK_KINDS.get(self.kind, -1)
-        a.k = len(self.entries)
         a.strength = self.strength
-        for j, (e, h, b) in enumerate(zip(self.entries, self.honest, self.byz)):
-            a.entries[j] = e.data_ptr() if e is not None else None
-            # (int32 fields: a count they cannot hold is refused as the library refuses one < 0)
-            a.honest[j] = h if -2 ** 31 <= h < 2 ** 31 else -1
-            a.byz[j] = b if -2 ** 31 <= b < 2 ** 31 else -1
-        return a
+        return self._fill_entries(a, honest=self.honest, byz=self.byz)
 
 
 def attack_entries(attack, b_out=None, P=None):
@@ -1218,7 +1186,7 @@ def attack_entries(attack, b_out=None, P=None):
     check(lib().flsim_attack_entries(ctypes.byref(a), ptr(b_out), int(P), stream_ptr()))
 
 
-class NNM:
+class NNM(_BucketRule):
     """Nearest-neighbour mixing over bucket sums (flsim_nnm, include/flsim.h; Allouah et al.
     2023): every entry becomes the mean of the k - f of the k = len(entries) values entries[j] /
     counts[j] nearest to its own, itself included; a rule then reads the entries with counts 1.
@@ -1229,50 +1197,22 @@ class NNM:
     read with no synchronisation beyond the stream's order; the next call overwrites them.
     flsim/robust.py (nnm_flat) is the text."""
     _scratch = {}       # (device, P, k) -> buffers
+    _what, _bad_count = "NNM", -1
+    _scratch_struct, _partials = FlsimNnmScratch, "flsim_nnm_partials"
 
     def __init__(self, f, entries, counts):
-        entries, counts = list(entries), [int(c) for c in counts]
-        if len(entries) != len(counts):
-            raise ValueError(f"{len(counts)} counts for {len(entries)} entries")
-        if len(entries) > MAX_ARRAYS:
-            raise ValueError(f"NNM over k = {len(entries)} entries (1 .. {MAX_ARRAYS})")
+        self._set_entries(entries, counts)
         self.f = int(f)
-        self.entries, self.counts = entries, counts     # (keeps the tensors alive)
         self.dist = self.nbr = None
-
-    @property
-    def k(self):
-        return len(self.entries)
 
     def c_struct(self):
         a = FlsimNnm()
         a.f = self.f if -2 ** 31 <= self.f < 2 ** 31 else -1
-        a.k = len(self.entries)
-        for j, (e, c) in enumerate(zip(self.entries, self.counts)):
-            a.entries[j] = e.data_ptr() if e is not None else None
-            # (an int32 field: a count it cannot hold is refused as the library refuses one < 1)
-            a.count[j] = c if -2 ** 31 <= c < 2 ** 31 else -1
-        return a
+        return self._fill_entries(a)
 
-    def c_scratch(self, device, P):
-        """flsim_nnm_scratch over this device's scratch for a mixing over P elements."""
-        k = len(self.entries)
-        key = (str(device), int(P), k)
-        if key not in NNM._scratch:
-            n = max(int(lib().flsim_nnm_partials(int(P), k)), 2)
-            NNM._scratch[key] = (torch.empty(n, dtype=torch.float64, device=device),
-                                 torch.empty(k * k + 2, dtype=torch.float64, device=device),
-                                 torch.empty(k + 2, dtype=torch.int64, device=device))
-        partials, dist, nbr = NNM._scratch[key]
-        s = FlsimNnmScratch()
-        s.partials = partials.data_ptr()
-        s.n_partials = int(partials.numel())
-        s.dist = dist.data_ptr()
-        s.nbr = nbr.data_ptr()
-        self.partials = partials
-        self.dist = dist[:k * k].view(k, k)
-        self.nbr = nbr[:k]
-        return s
+    def _scratch_rows(self, k):
+        return (), (("dist", "dist", torch.float64, k * k + 2, (k, k)),
+                    ("nbr", "nbr", torch.int64, k + 2, (k,)))
 
     def neighbours(self):
         """nbr read back as k ascending lists of entry indices (synchronises)."""

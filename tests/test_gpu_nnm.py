@@ -176,6 +176,35 @@ def test_device_equals_the_host_twin(k):
     assert (np.abs(d - hd) <= 2 * M.dist_bound(P) * hd).all()
 
 
+@pytest.mark.parametrize("k", (3, 4, 5, 9, 64))
+def test_krum_and_nnm_share_the_matrix(k):
+    """Krum (f = 0, m = 1, the rule alone) and NNM (f = 0) over the same entries and counts, both
+    scratches starting from QNAN: dist is the same matrix, bit for bit.  KPAD 4, 4, 8, 16 and 64;
+    P of one element, one tile + 1 and 3 tiles + 5; then entry 1 holding a NaN (a +inf row and
+    column on both sides).  NNM mixes in place, so each side gets its own copies."""
+    from flsim.engine import Krum, krum_step
+    E = M.krum_tile(k)
+    cases = [(P, False) for P in (1, E + 1, 3 * E + 5)] + [(3 * E + 5, True)]
+    for P, poison in cases:
+        ents, counts = M.inputs(k, P)
+        if poison:
+            ents[1][P // 2] = np.nan
+        dev = [torch.from_numpy(e).to(DEV) for e in ents]
+        kr = Krum(0, 1, dev, counts)
+        kr.c_scratch(dev[0].device, P)
+        for t in Krum._scratch[(str(dev[0].device), P, k)]:
+            t.view(torch.int32).fill_(M.QNAN)
+        krum_step(kr, None, None, None, 1, optim=False, g_out=torch.empty(P, device=DEV))
+        torch.cuda.synchronize()
+        dk = kr.dist.cpu().numpy()
+        _, dn, _ = _run(ents, counts, 0)
+        assert np.array_equal(dk.view(np.uint64), dn.view(np.uint64)), (k, P, poison)
+        off = np.arange(k) != 1
+        hit = np.isinf(dk[1, off]) & np.isinf(dk[off, 1])
+        assert hit.all() if poison else not np.isinf(dk).any()
+        assert np.isfinite(dk[off][:, off]).all() and dk[1, 1] == 0
+
+
 def test_refusals_on_device_pointers():
     """Overlapping entries, a misaligned entry, a bad f, a None entry: ValueError, and nothing is
     launched (the buffer keeps its bits)."""

@@ -7,7 +7,7 @@
 //
 //   cd fl-distributed-delay_amd && hipcc -O1 -g -std=c++17 --offload-arch=gfx950 \
 //       -ffp-contract=off -Xarch_host -fsanitize=address,undefined \
-//       -Xarch_host -fno-sanitize-recover=undefined -I../include -Icsrc -x hip \
+//       -Xarch_host -fno-sanitize-recover=undefined -I../include -I../tools -Icsrc -x hip \
 //       csrc/server.hip csrc/probe.cpp ../tools/attack_host_check.cpp \
 //       -fsanitize=address,undefined -o /tmp/attack_host_check && /tmp/attack_host_check
 //
@@ -16,59 +16,10 @@
 // over random honest / mixed / fully Byzantine splits, and is compared, as numbers, with the text
 // restated here in plain C: fp64 divisions, sequential sums in index order, sqrt, one fp64 -> fp32
 // rounding, then a separate fp32 multiply and add.
-#include <math.h>
-#include <stdarg.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
 
 #include <vector>
 
-#include "flsim.h"
-
-// the library's error slot lives with the network engines (csrc/pn1_net.hip), which this program
-// does not link: the same few lines
-namespace flsim {
-static thread_local char g_err[512];
-void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-}
-const char* last_error() { return g_err; }
-}  // namespace flsim
-extern "C" const char* flsim_last_error(void) { return flsim::last_error(); }
-
-static uint32_t bits(float x) {
-    uint32_t u;
-    memcpy(&u, &x, 4);
-    return u;
-}
-// equal as numbers: both NaN, both zero, or the same bits
-static bool same(float a, float b) {
-    return (a != a && b != b) || (a == 0.f && b == 0.f) || bits(a) == bits(b);
-}
-
-static int fails = 0;
-#define EXPECT(cond)                                                       \
-    do {                                                                   \
-        if (!(cond)) {                                                     \
-            printf("FAIL %s:%d %s [%s]\n", __FILE__, __LINE__, #cond, flsim_last_error()); \
-            ++fails;                                                       \
-        }                                                                  \
-    } while (0)
-
-static uint64_t rng_state = 0x9E3779B97F4A7C15ull;
-static double uniform() {
-    rng_state = rng_state * 6364136223846793005ull + 1442695040888963407ull;
-    return (double)(rng_state >> 11) / (double)(1ull << 53);
-}
-static float normal() {
-    const double u = uniform() + 1e-300, v = uniform();
-    return (float)(sqrt(-2.0 * log(u)) * cos(6.283185307179586 * v));
-}
+#include "host_check.h"
 
 // the text's attack_vector for one element in plain C
 static float text_b(const std::vector<float>& x, const std::vector<int>& honest, int kind,
@@ -142,7 +93,7 @@ static void twin_case(int k, long P, int kind, double strength, float bad, bool 
     for (long e = 0; e < P; ++e) {
         for (int j = 0; j < k; ++j) x[j] = before[j][e];
         const float bt = text_b(x, honest, kind, strength);
-        if (with_b) ok &= same(b[e], bt);
+        if (with_b) ok &= same_number(b[e], bt);
         for (int j = 0; j < k; ++j) {
             if (byz[j] == 0) {
                 ok &= bits(ent[j][e]) == bits(before[j][e]);
@@ -150,7 +101,7 @@ static void twin_case(int k, long P, int kind, double strength, float bad, bool 
             }
             volatile float t = bt * (float)byz[j];
             volatile float want = honest[j] ? before[j][e] + t : (float)t;
-            ok &= same(ent[j][e], want);
+            ok &= same_number(ent[j][e], want);
         }
     }
     EXPECT(ok);

@@ -6,42 +6,16 @@
 //
 //   cd fl-distributed-delay_amd && hipcc -O1 -g -std=c++17 --offload-arch=gfx950 \
 //       -ffp-contract=off -Xarch_host -fsanitize=address,undefined \
-//       -Xarch_host -fno-sanitize-recover=undefined -I../include -Icsrc -x hip \
+//       -Xarch_host -fno-sanitize-recover=undefined -I../include -I../tools -Icsrc -x hip \
 //       csrc/server.hip csrc/probe.cpp ../tools/crule_host_check.cpp -fsanitize=address,undefined \
 //       -o /tmp/crule_host_check && /tmp/crule_host_check
 //
 // The twin runs on exactly-sized caller buffers (ASan sees any over-read of a snapshot) and is
 // compared with the five-rounding text restated here in plain C.
-#include <math.h>
-#include <stdarg.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
 
 #include <vector>
 
-#include "flsim.h"
-
-// the library's error slot lives with the network engines (csrc/pn1_net.hip), which this program
-// does not link: the same few lines
-namespace flsim {
-static thread_local char g_err[512];
-void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-}
-const char* last_error() { return g_err; }
-}  // namespace flsim
-extern "C" const char* flsim_last_error(void) { return flsim::last_error(); }
-
-static uint32_t bits(float x) {
-    uint32_t u;
-    memcpy(&u, &x, 4);
-    return u;
-}
+#include "host_check.h"
 
 // the text, one rounding per line (volatile: no contraction whatever the flags)
 static float compensate_text(float x, float now, float src, float lam) {
@@ -51,15 +25,6 @@ static float compensate_text(float x, float now, float src, float lam) {
     volatile float hd = h * d;
     return x + hd;
 }
-
-static int fails = 0;
-#define EXPECT(cond)                                                       \
-    do {                                                                   \
-        if (!(cond)) {                                                     \
-            printf("FAIL %s:%d %s [%s]\n", __FILE__, __LINE__, #cond, flsim_last_error()); \
-            ++fails;                                                       \
-        }                                                                  \
-    } while (0)
 
 int main() {
     // ---- the host twin ------------------------------------------------------------------------

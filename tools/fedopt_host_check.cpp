@@ -6,7 +6,7 @@
 //
 //   cd fl-distributed-delay_amd && hipcc -O1 -g -std=c++17 --offload-arch=gfx950 \
 //       -ffp-contract=off -Xarch_host -fsanitize=address,undefined \
-//       -Xarch_host -fno-sanitize-recover=undefined -I../include -Icsrc -x hip \
+//       -Xarch_host -fno-sanitize-recover=undefined -I../include -I../tools -Icsrc -x hip \
 //       csrc/server.hip csrc/probe.cpp ../tools/fedopt_host_check.cpp \
 //       -fsanitize=address,undefined -o /tmp/fedopt_host_check && /tmp/fedopt_host_check
 //
@@ -16,49 +16,13 @@
 // restated on the host from those launch constants (what opt_update<OK_ADAGRAD / OK_YOGI> does,
 // fmaf and sqrtf being correctly rounded here) against the rule text evaluated from the
 // hyper-parameters as torch evaluates it, on exactly sized heap buffers.
-#include <math.h>
-#include <stdarg.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
 
 #include <vector>
 
-#include "flsim.h"
+#include "host_check.h"
 #include "slabstep.h"
 
-// the library's error slot lives with the network engines (csrc/pn1_net.hip), which this program
-// does not link: the same few lines
-namespace flsim {
-static thread_local char g_err[512];
-void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-}
-const char* last_error() { return g_err; }
-}  // namespace flsim
-extern "C" const char* flsim_last_error(void) { return flsim::last_error(); }
-
 using namespace flsim;
-
-static uint32_t bits(float x) {
-    uint32_t u;
-    memcpy(&u, &x, 4);
-    return u;
-}
-static bool same(float a, float b) { return bits(a) == bits(b) || (a != a && b != b); }
-
-static int fails = 0;
-#define EXPECT(cond)                                                       \
-    do {                                                                   \
-        if (!(cond)) {                                                     \
-            printf("FAIL %s:%d %s [%s]\n", __FILE__, __LINE__, #cond, flsim_last_error()); \
-            ++fails;                                                       \
-        }                                                                  \
-    } while (0)
 
 static flsim_optim optim(int kind) {
     flsim_optim o{};
@@ -276,7 +240,7 @@ int main() {
             for (long e = 0; e < n; ++e) {
                 adagrad_launch(ol, g[e], pa[e], sa[e]);
                 adagrad_text(o, step, g[e], pb[e], sb[e]);
-                diff += !same(pa[e], pb[e]) || !same(sa[e], sb[e]);
+                diff += !same_bits(pa[e], pb[e]) || !same_bits(sa[e], sb[e]);
                 moved += bits(pa[e]) != bits(p0[e]);
             }
             EXPECT(diff == 0);
@@ -296,7 +260,7 @@ int main() {
                 if (wd == 0.0) signs[d > 0.f ? 2 : (d < 0.f ? 0 : 1)]++;
                 yogi_launch(ol, g[e], pa[e], ma[e], va[e]);
                 yogi_text(o, g[e], pb[e], mb[e], vb[e]);
-                diff += !same(pa[e], pb[e]) || !same(ma[e], mb[e]) || !same(va[e], vb[e]);
+                diff += !same_bits(pa[e], pb[e]) || !same_bits(ma[e], mb[e]) || !same_bits(va[e], vb[e]);
                 nans += va[e] != va[e];
             }
             EXPECT(diff == 0);

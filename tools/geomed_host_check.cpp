@@ -7,7 +7,7 @@
 //
 //   cd fl-distributed-delay_amd && hipcc -O1 -g -std=c++17 --offload-arch=gfx950 \
 //       -ffp-contract=off -Xarch_host -fsanitize=address,undefined \
-//       -Xarch_host -fno-sanitize-recover=undefined -I../include -Icsrc -x hip \
+//       -Xarch_host -fno-sanitize-recover=undefined -I../include -I../tools -Icsrc -x hip \
 //       csrc/server.hip csrc/probe.cpp ../tools/geomed_host_check.cpp \
 //       -fsanitize=address,undefined -o /tmp/geomed_host_check && /tmp/geomed_host_check
 //
@@ -16,63 +16,10 @@
 // summation order: one fp32 division per value, z by one fp64 multiply and one add per term in
 // index order (zero weights skipped), fp64 sums of (x - z)^2 by one fma per element, sqrt, the
 // sequential sums and the divisions.
-#include <math.h>
-#include <stdarg.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
 
 #include <vector>
 
-#include "flsim.h"
-
-// the library's error slot lives with the network engines (csrc/pn1_net.hip), which this program
-// does not link: the same few lines
-namespace flsim {
-static thread_local char g_err[512];
-void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-}
-const char* last_error() { return g_err; }
-}  // namespace flsim
-extern "C" const char* flsim_last_error(void) { return flsim::last_error(); }
-
-static uint32_t bits(float x) {
-    uint32_t u;
-    memcpy(&u, &x, 4);
-    return u;
-}
-static uint64_t bits(double x) {
-    uint64_t u;
-    memcpy(&u, &x, 8);
-    return u;
-}
-// equal bit for bit, or both NaN
-static bool same(double a, double b) { return (a != a && b != b) || bits(a) == bits(b); }
-static bool same(float a, float b) { return (a != a && b != b) || bits(a) == bits(b); }
-
-static int fails = 0;
-#define EXPECT(cond)                                                       \
-    do {                                                                   \
-        if (!(cond)) {                                                     \
-            printf("FAIL %s:%d %s [%s]\n", __FILE__, __LINE__, #cond, flsim_last_error()); \
-            ++fails;                                                       \
-        }                                                                  \
-    } while (0)
-
-static uint64_t rng_state = 0x9E3779B97F4A7C15ull;
-static double uniform() {
-    rng_state = rng_state * 6364136223846793005ull + 1442695040888963407ull;
-    return (double)(rng_state >> 11) / (double)(1ull << 53);
-}
-static float normal() {
-    const double u = uniform() + 1e-300, v = uniform();
-    return (float)(sqrt(-2.0 * log(u)) * cos(6.283185307179586 * v));
-}
+#include "host_check.h"
 
 // the text in plain C; x: the bucket means [k][P]
 static void text(const std::vector<std::vector<float>>& x, const std::vector<double>& alpha, long P,
@@ -171,10 +118,10 @@ static void twin_case(int k, long P, int iters, int weighted, double nu, int nul
     std::vector<float> gt;
     text(x, alpha, P, iters, nu, wt, dt, ot, gt);
     bool ok = true;
-    for (size_t i = 0; i < w.size(); ++i) ok &= same(w[i], wt[i]);
-    for (size_t i = 0; i < d2.size(); ++i) ok &= same(d2[i], dt[i]);
-    for (size_t i = 0; i < obj.size(); ++i) ok &= same(obj[i], ot[i]);
-    for (long e = 0; e < P; ++e) ok &= same(g[e], gt[e]);
+    for (size_t i = 0; i < w.size(); ++i) ok &= same_bits(w[i], wt[i]);
+    for (size_t i = 0; i < d2.size(); ++i) ok &= same_bits(d2[i], dt[i]);
+    for (size_t i = 0; i < obj.size(); ++i) ok &= same_bits(obj[i], ot[i]);
+    for (long e = 0; e < P; ++e) ok &= same_bits(g[e], gt[e]);
     EXPECT(ok);
     if (dead >= 0) {
         for (int it = 0; it <= iters; ++it) EXPECT(w[(size_t)it * k + dead] == 0.0);

@@ -7,7 +7,7 @@
 //
 //   cd fl-distributed-delay_amd && hipcc -O1 -g -std=c++17 --offload-arch=gfx950 \
 //       -ffp-contract=off -Xarch_host -fsanitize=address,undefined \
-//       -Xarch_host -fno-sanitize-recover=undefined -I../include -Icsrc -x hip \
+//       -Xarch_host -fno-sanitize-recover=undefined -I../include -I../tools -Icsrc -x hip \
 //       csrc/server.hip csrc/probe.cpp ../tools/krum_host_check.cpp \
 //       -fsanitize=address,undefined -o /tmp/krum_host_check && /tmp/krum_host_check
 //
@@ -16,46 +16,11 @@
 // fp64 sums of squared fp64 differences, NaN -> +inf, a stable sort of each row's off-diagonal
 // distances and sequential fp64 adds of the first k - f - 2, the m lowest (score, index), sequential
 // fp32 adds of the selected means in index order and one division.
-#include <math.h>
-#include <stdarg.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
 
 #include <algorithm>
 #include <vector>
 
-#include "flsim.h"
-
-// the library's error slot lives with the network engines (csrc/pn1_net.hip), which this program
-// does not link: the same few lines
-namespace flsim {
-static thread_local char g_err[512];
-void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-}
-const char* last_error() { return g_err; }
-}  // namespace flsim
-extern "C" const char* flsim_last_error(void) { return flsim::last_error(); }
-
-static uint32_t bits(float x) {
-    uint32_t u;
-    memcpy(&u, &x, 4);
-    return u;
-}
-
-static int fails = 0;
-#define EXPECT(cond)                                                       \
-    do {                                                                   \
-        if (!(cond)) {                                                     \
-            printf("FAIL %s:%d %s [%s]\n", __FILE__, __LINE__, #cond, flsim_last_error()); \
-            ++fails;                                                       \
-        }                                                                  \
-    } while (0)
+#include "host_check.h"
 
 // |got - ref| <= rel * ref, or both +inf
 static bool close_to(double got, double ref, double rel) {

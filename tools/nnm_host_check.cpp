@@ -7,7 +7,7 @@
 //
 //   cd fl-distributed-delay_amd && hipcc -O1 -g -std=c++17 --offload-arch=gfx950 \
 //       -ffp-contract=off -Xarch_host -fsanitize=address,undefined \
-//       -Xarch_host -fno-sanitize-recover=undefined -I../include -Icsrc -x hip \
+//       -Xarch_host -fno-sanitize-recover=undefined -I../include -I../tools -Icsrc -x hip \
 //       csrc/server.hip csrc/probe.cpp ../tools/nnm_host_check.cpp \
 //       -fsanitize=address,undefined -o /tmp/nnm_host_check && /tmp/nnm_host_check
 //
@@ -16,65 +16,12 @@
 // is compared with the text restated here in plain C: the distances the twin's own way (fp64 fma
 // in element order; both are checked symmetric with a zero diagonal), the neighbours by sorting
 // (distance, index) pairs, the mixed values by sequential fp32 adds and one division.
-#include <math.h>
-#include <stdarg.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
 
 #include <algorithm>
 #include <utility>
 #include <vector>
 
-#include "flsim.h"
-
-// the library's error slot lives with the network engines (csrc/pn1_net.hip), which this program
-// does not link: the same few lines
-namespace flsim {
-static thread_local char g_err[512];
-void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-}
-const char* last_error() { return g_err; }
-}  // namespace flsim
-extern "C" const char* flsim_last_error(void) { return flsim::last_error(); }
-
-static uint32_t bits(float x) {
-    uint32_t u;
-    memcpy(&u, &x, 4);
-    return u;
-}
-// equal as numbers: both NaN, both zero, or the same bits
-static bool same(float a, float b) {
-    return (a != a && b != b) || (a == 0.f && b == 0.f) || bits(a) == bits(b);
-}
-
-static int fails = 0;
-#define EXPECT(cond)                                                       \
-    do {                                                                   \
-        if (!(cond)) {                                                     \
-            printf("FAIL %s:%d %s [%s]\n", __FILE__, __LINE__, #cond, flsim_last_error()); \
-            ++fails;                                                       \
-        }                                                                  \
-    } while (0)
-
-static uint64_t rng_state = 0x9E3779B97F4A7C15ull;
-static double uniform() {
-    rng_state = rng_state * 6364136223846793005ull + 1442695040888963407ull;
-    return (double)(rng_state >> 11) / (double)(1ull << 53);
-}
-static float normal() {
-    const double u = uniform() + 1e-300, v = uniform();
-    return (float)(sqrt(-2.0 * log(u)) * cos(6.283185307179586 * v));
-}
-
-static bool refused(int rc, const char* what) {
-    return rc == 1 && strstr(flsim_last_error(), what) != nullptr;
-}
+#include "host_check.h"
 
 int main() {
     long cases = 0;
@@ -146,7 +93,7 @@ int main() {
                         }
                     volatile float fn = (float)(k - f);
                     volatile float y = acc / fn;
-                    EXPECT(same(out[(long)i * P + e], y));
+                    EXPECT(same_number(out[(long)i * P + e], y));
                 }
                 ++cases;
             }

@@ -6,7 +6,7 @@
 //
 //   cd fl-distributed-delay_amd && hipcc -O1 -g -std=c++17 --offload-arch=gfx950 \
 //       -ffp-contract=off -Xarch_host -fsanitize=address,undefined \
-//       -Xarch_host -fno-sanitize-recover=undefined -I../include -Icsrc -x hip \
+//       -Xarch_host -fno-sanitize-recover=undefined -I../include -I../tools -Icsrc -x hip \
 //       csrc/server.hip csrc/probe.cpp ../tools/robust_host_check.cpp \
 //       -fsanitize=address,undefined -o /tmp/robust_host_check && /tmp/robust_host_check
 //
@@ -14,37 +14,11 @@
 // in 1 .. 64 and is compared with the text restated here in plain C: one fp32 division per value,
 // a stable sort that puts NaN last, the lower median, or sequential fp32 adds in ascending order
 // and one division.
-#include <math.h>
-#include <stdarg.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
 
 #include <algorithm>
 #include <vector>
 
-#include "flsim.h"
-
-// the library's error slot lives with the network engines (csrc/pn1_net.hip), which this program
-// does not link: the same few lines
-namespace flsim {
-static thread_local char g_err[512];
-void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-}
-const char* last_error() { return g_err; }
-}  // namespace flsim
-extern "C" const char* flsim_last_error(void) { return flsim::last_error(); }
-
-static uint32_t bits(float x) {
-    uint32_t u;
-    memcpy(&u, &x, 4);
-    return u;
-}
+#include "host_check.h"
 
 // the text for one element (volatile: one rounding per operation whatever the flags)
 static float text(std::vector<float> x, int kind, int trim) {
@@ -58,22 +32,6 @@ static float text(std::vector<float> x, int kind, int trim) {
     volatile float n = (float)(k - 2 * trim);
     return acc / n;
 }
-
-// equal as numbers: the same bits, or both zero, or both NaN
-static bool same(float got, float ref) {
-    if (ref != ref) return got != got;
-    if (ref == 0.f) return got == 0.f;
-    return bits(got) == bits(ref);
-}
-
-static int fails = 0;
-#define EXPECT(cond)                                                       \
-    do {                                                                   \
-        if (!(cond)) {                                                     \
-            printf("FAIL %s:%d %s [%s]\n", __FILE__, __LINE__, #cond, flsim_last_error()); \
-            ++fails;                                                       \
-        }                                                                  \
-    } while (0)
 
 int main() {
     // ---- the host twin, every k in 1 .. 64 ----------------------------------------------------------
@@ -116,7 +74,7 @@ int main() {
                         x[j] = s / c;
                     }
                     const float ref = text(x, kind, trim);
-                    if (!same(out[e], ref)) {
+                    if (!same_number(out[e], ref)) {
                         printf("FAIL k=%d kind=%d trim=%d e=%ld got %a want %a\n", k, kind, trim, e,
                                (double)out[e], (double)ref);
                         ++fails;

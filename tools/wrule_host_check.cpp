@@ -5,38 +5,17 @@
 //
 //   cd fl-distributed-delay_amd && hipcc -O1 -g -std=c++17 --offload-arch=gfx950 \
 //       -ffp-contract=off -Xarch_host -fsanitize=address,undefined \
-//       -Xarch_host -fno-sanitize-recover=undefined -I../include -Icsrc -x hip \
+//       -Xarch_host -fno-sanitize-recover=undefined -I../include -I../tools -Icsrc -x hip \
 //       csrc/server.hip csrc/probe.cpp ../tools/wrule_host_check.cpp -fsanitize=address,undefined \
 //       -o /tmp/wrule_host_check && /tmp/wrule_host_check
 //
 // It also answers the division question of DESIGN 6: div_const's arithmetic (q0 = a * RN(1/b),
 // one fma correction) restated on the host against the IEEE quotient, over adversarial numerators
 // for integer and non-integer divisors.  It prints the count of differing words per divisor.
-#include <math.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
 
 #include <vector>
 
-#include <stdarg.h>
-
-#include "flsim.h"
-
-// the library's error slot lives with the network engines (csrc/pn1_net.hip), which this program
-// does not link: the same few lines
-namespace flsim {
-static thread_local char g_err[512];
-void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-}
-const char* last_error() { return g_err; }
-}  // namespace flsim
-extern "C" const char* flsim_last_error(void) { return flsim::last_error(); }
+#include "host_check.h"
 
 static float div_const_host(float a, float b, float rb) {
     const float q0 = a * rb;
@@ -45,21 +24,6 @@ static float div_const_host(float a, float b, float rb) {
     const float aq = fabsf(q0);
     return (aq >= 0x1p-124f && aq <= 0x1p+124f) ? q : a / b;
 }
-
-static uint32_t bits(float x) {
-    uint32_t u;
-    memcpy(&u, &x, 4);
-    return u;
-}
-
-static int fails = 0;
-#define EXPECT(cond)                                                       \
-    do {                                                                   \
-        if (!(cond)) {                                                     \
-            printf("FAIL %s:%d %s [%s]\n", __FILE__, __LINE__, #cond, flsim_last_error()); \
-            ++fails;                                                       \
-        }                                                                  \
-    } while (0)
 
 int main() {
     // ---- the host twin on exactly-sized caller buffers (ASan sees any over-read) --------------
