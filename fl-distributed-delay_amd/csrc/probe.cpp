@@ -22,7 +22,8 @@ static const char* KNAME[K_COUNT] = {
     "geomed_dist", "geomed_finish", "geomed_apply",
     "attack_entries",
     "cclip_dist", "cclip_finish", "cclip_apply",
-    "nnm_dist", "nnm_finish", "nnm_mix"};
+    "nnm_dist", "nnm_finish", "nnm_mix",
+    "bulyan_dist", "bulyan_finish", "bulyan_apply"};
 
 struct Probe {
     bool on = false;

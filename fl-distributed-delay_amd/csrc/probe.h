@@ -28,7 +28,9 @@ enum KernelId {
     // iterate, finish, apply)
     K_ATTACK, K_CCLIP_DIST, K_CCLIP_FIN, K_CCLIP_APPLY,
     // nearest-neighbour mixing of the entries (Krum's distance launch, finish + selection, the mix)
-    K_NNM_DIST, K_NNM_FIN, K_NNM_MIX, K_COUNT
+    K_NNM_DIST, K_NNM_FIN, K_NNM_MIX,
+    // the Bulyan step's three launches (Krum's distance launch, finish + the rounds, apply)
+    K_BULYAN_DIST, K_BULYAN_FIN, K_BULYAN_APPLY, K_COUNT
 };
 
 // Event pair for the launch that follows (nullptr events when the probe is off or full).  The

@@ -39,6 +39,7 @@
 #include <type_traits>
 
 #include "attack.h"
+#include "bulyan.h"
 #include "cclip.h"
 #include "common.h"
 #include "flsim.h"
@@ -2393,6 +2394,99 @@ static int check_krum(const flsim_krum* r) {
 }
 
 // ================================================================================================
+// Bulyan: Krum's distance launch, the repeated selection, the window around the median over the
+// selected entries (include/flsim.h: flsim_bulyan; csrc/bulyan.h: the selection and the window /
+// sum code shared with the host)
+// ================================================================================================
+// pair_matrix (the pairwise-distance stage, Krum's matrix), then csrc/bulyan.h's selection on the
+// matrix in LDS; order, the winning scores and the ascending selection go out at the end
+__global__ void __launch_bounds__(KRUM_FIN_THREADS)
+k_bulyan_finish(const double* partials, int nblocks, int nb, int k, int f, double* dist,
+                double* score, int32_t* order, int32_t* sel) {
+    __shared__ double sd[RULE_MAX_ARR * RULE_MAX_ARR];
+    __shared__ double ss[RULE_MAX_ARR], sw[RULE_MAX_ARR];
+    __shared__ int32_t so[RULE_MAX_ARR], sl[RULE_MAX_ARR];
+    __shared__ uint8_t sn[RULE_MAX_ARR * RULE_MAX_ARR];
+    pair_matrix(partials, nblocks, nb, k, sd, dist);
+    bulyan_order(sd, sn, ss, sw, so, sl, k, f, (int)threadIdx.x, KRUM_FIN_THREADS,
+                 [] { __syncthreads(); });
+    __syncthreads();
+    if ((int)threadIdx.x < k - 2 * f) {
+        score[threadIdx.x] = sw[threadIdx.x];
+        order[threadIdx.x] = so[threadIdx.x];
+        sel[threadIdx.x] = sl[threadIdx.x];
+    }
+}
+
+struct BulyanApplyArgs {
+    EntryTable T;
+    ApplyOut O;
+    const int32_t* sel;                 // [theta] the selection k_bulyan_finish wrote (device memory)
+    int theta, beta;
+    float fbeta;                        // (float)beta: the divisor of the window's sum
+};
+static_assert(sizeof(BulyanApplyArgs) <= 4096, "kernel argument block");
+
+// One thread owns one element, as k_robust.  The selection is read from device memory; it is
+// launch-uniform (readfirstlane: the entry pointer, its count and the reciprocal come from the
+// kernel arguments by scalar loads), as k_krum_apply reads it.  Only the theta selected entries are
+// loaded, non-temporally, all of them before any arithmetic; then p / m / v; then the divisions,
+// the keys, the network over KPAD = the padded theta, csrc/bulyan.h's window and sum, one IEEE
+// division by (float)beta and the update of kind OK, or OK_GOUT as k_robust.
+template <int KPAD, int OK>
+__global__ void __launch_bounds__(256) k_bulyan_apply(BulyanApplyArgs A) {
+    ApplyElem<OK> el;
+    if (!el.begin(A.O)) return;
+    const long e = el.e;
+    float x[KPAD];
+#pragma unroll
+    for (int t = 0; t < KPAD; ++t) {
+        x[t] = 0.f;
+        if (t < A.theta) {
+            const int j = __builtin_amdgcn_readfirstlane(A.sel[t]) & (RULE_MAX_ARR - 1);
+            const float* src = A.T.ent[j];
+            if (src && el.live) x[t] = __builtin_nontemporal_load(src + e);
+        }
+    }
+    el.load_state(A.O);
+    uint32_t key[KPAD];
+#pragma unroll
+    for (int t = 0; t < KPAD; ++t) {
+        key[t] = ROBUST_PAD;
+        if (t < A.theta) {
+            const int j = __builtin_amdgcn_readfirstlane(A.sel[t]) & (RULE_MAX_ARR - 1);
+            key[t] = robust_key(div_const(x[t], A.T.cnt[j], A.T.rcnt[j]));
+        }
+    }
+    const float g = bulyan_window_sum<KPAD>(key, A.theta, A.beta);
+    el.finish(A.O, __fdiv_rn(g, A.fbeta));
+}
+
+// flsim_bulyan's hyper-parameters; before any pointer check, like check_optim
+static int check_bulyan(const flsim_bulyan* r) {
+    FLSIM_REQUIRE(r, "null Bulyan rule");
+    FLSIM_REQUIRE(r->k >= 3 && r->k <= RULE_MAX_ARR, "Bulyan over k = %d entries (3 .. %d)", r->k,
+                  RULE_MAX_ARR);
+    FLSIM_REQUIRE(r->f >= 0 && r->f <= RULE_MAX_ARR && r->k >= 4 * r->f + 3,
+                  "Invalid f = %d for k = %d entries: f >= 0 and k >= 4 * f + 3", r->f, r->k);
+    return check_counts(r->count, r->k);
+}
+
+// the host twin's elements: the same divisions, keys, network, window and sum as k_bulyan_apply
+template <int KPAD>
+static void bulyan_eval_host(const flsim_bulyan* r, const int32_t* sel, long P, float* g_out) {
+    const int theta = r->k - 2 * r->f, beta = theta - 2 * r->f;
+    for (long e = 0; e < P; ++e) {
+        uint32_t key[KPAD];
+        for (int t = 0; t < KPAD; ++t)
+            key[t] = t < theta ? robust_key(bucket_mean(r->entries, r->count, sel[t], e))
+                               : ROBUST_PAD;
+        volatile float s = bulyan_window_sum<KPAD>(key, theta, beta), n = (float)beta;
+        g_out[e] = s / n;
+    }
+}
+
+// ================================================================================================
 // Geometric median (RFA, smoothed Weiszfeld): distances to the iterate, the scalar step, apply
 // (include/flsim.h: flsim_geomed; csrc/geomed.h: the geometry and the scalar code shared with the
 // host)
@@ -4103,6 +4197,81 @@ int flsim_krum_eval_host(const flsim_krum* r, long P, double* dist, double* scor
         volatile float fm = (float)r->m;
         g_out[e] = acc / fm;
     }
+    return 0;
+}
+
+// ---- Bulyan over bucket means + the update (include/flsim.h) -------------------------------------
+long flsim_bulyan_partials(long P, int k) { return flsim_krum_partials(P, k); }   // (pair_partials)
+
+// Three launches: k_krum_dist -> s->partials (Krum's launch and geometry); k_bulyan_finish ->
+// s->dist, s->score, s->order, s->sel; k_bulyan_apply in the optimizer's kind (optim == NULL:
+// OK_GOUT writing g_out alone; clip: OK_GOUT writing clip->G and the per-block partials, then
+// k_clip_finish and k_clip_apply).
+int flsim_bulyan_optim_step(const flsim_bulyan* r, const flsim_bulyan_scratch* s,
+                            const flsim_clip* clip, float* g_out, float* p, float* m, float* v,
+                            long P, long step, const flsim_optim* optim, hipStream_t stream) {
+    RC(check_bulyan(r));
+    BucketStep B;
+    RC(step_begin(optim, clip, g_out, p, m, v, P, step, &B));
+    static const char name[] = "Bulyan";
+    const flsim_bulyan_scratch none{};
+    if (!s) s = &none;
+    const int theta = r->k - 2 * r->f, beta = theta - 2 * r->f;
+    const long n_dist = pair_partials(P, r->k);
+    constexpr int NS = 5;
+    const Span sc[NS] = {{s->partials, 8 * n_dist},
+                         {s->dist, 8L * r->k * r->k},
+                         {s->score, 8L * theta},
+                         {s->order, 4L * theta},
+                         {s->sel, 4L * theta}};
+    RC(check_scratch_pointers(name, sc, NS, s->n_partials, n_dist));
+    RC(check_scratch(B, name, sc, NS, nullptr));
+    RC(check_clip_buffers(B, nullptr));
+    BulyanApplyArgs A{};
+    int distinct = 0;
+    RC(fill_entries(B, r->entries, r->count, r->k, name, sc, NS, nullptr, &A.T, &distinct));
+    // the finish launch's own bytes: order and sel written
+    RC(launch_pair_dist(A.T, s->partials, P, r->k, K_BULYAN_DIST, distinct, K_BULYAN_FIN,
+                        8.0 * theta, stream,
+                        [&](const ProbeSlot& ps, const double* part, int nblocks, int nb) {
+                            hipExtLaunchKernelGGL(k_bulyan_finish, dim3(1), dim3(KRUM_FIN_THREADS),
+                                                  0, stream, ps.start, ps.stop, 0, part, nblocks,
+                                                  nb, (int)r->k, (int)r->f, s->dist, s->score,
+                                                  s->order, s->sel);
+                        }));
+    A.sel = s->sel;
+    A.theta = theta;
+    A.beta = beta;
+    A.fbeta = (float)beta;
+    const int kpad = robust_kpad(theta);
+    // the rule's own arrays: the theta selected entries read
+    return launch_apply(B, A, K_BULYAN_APPLY, theta, stream,
+                        [&](auto ok, dim3 grid, const ProbeSlot& ps) {
+                            with_kpad<4>(kpad, [&](auto kp) {
+                                hipExtLaunchKernelGGL(
+                                    (k_bulyan_apply<decltype(kp)::value, decltype(ok)::value>),
+                                    grid, dim3(256), 0, stream, ps.start, ps.stop, 0, A);
+                            });
+                        });
+}
+
+// host (testing): the text for host pointers.  The distances as flsim_krum_eval_host forms them,
+// then csrc/bulyan.h's selection and, per element, its window and sum over the selected means.
+int flsim_bulyan_eval_host(const flsim_bulyan* r, long P, double* dist, double* score,
+                           int32_t* order, int32_t* sel, float* g_out) {
+    RC(check_bulyan(r));
+    FLSIM_REQUIRE(dist && score && order && sel, "null pointer");
+    FLSIM_REQUIRE(P > 0, "P = %ld out of range", P);
+    const int k = r->k, theta = k - 2 * r->f;
+    auto mean = [&](int j, long e) { return bucket_mean(r->entries, r->count, j, e); };
+    pair_dist_host(mean, k, P, dist);
+    uint8_t nbr[RULE_MAX_ARR * RULE_MAX_ARR];
+    double work[RULE_MAX_ARR];
+    bulyan_order(dist, nbr, work, score, order, sel, k, (int)r->f, 0, 1, [] {});
+    if (!g_out) return 0;
+    with_kpad<4>(robust_kpad(theta), [&](auto kp) {
+        bulyan_eval_host<decltype(kp)::value>(r, sel, P, g_out);
+    });
     return 0;
 }
 

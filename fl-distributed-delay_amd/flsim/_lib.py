@@ -53,6 +53,7 @@ EXPORTS = [
     "flsim_robust_optim_step", "flsim_robust_eval_host",
     "flsim_krum_partials", "flsim_krum_tile_elems", "flsim_krum_optim_step",
     "flsim_krum_eval_host",
+    "flsim_bulyan_partials", "flsim_bulyan_optim_step", "flsim_bulyan_eval_host",
     "flsim_geomed_partials", "flsim_geomed_tile_elems", "flsim_geomed_optim_step",
     "flsim_geomed_eval_host",
     "flsim_attack_tile_elems", "flsim_attack_entries", "flsim_attack_eval_host",
@@ -117,6 +118,19 @@ class FlsimKrumScratch(ctypes.Structure):
     """flsim_krum_scratch (include/flsim.h): the caller's scratch and outputs of a Krum step."""
     _fields_ = [("partials", ctypes.c_void_p), ("n_partials", ctypes.c_long),
                 ("dist", ctypes.c_void_p), ("score", ctypes.c_void_p), ("sel", ctypes.c_void_p)]
+
+
+class FlsimBulyan(ctypes.Structure):
+    """flsim_bulyan (include/flsim.h): Bulyan over k bucket / class sums and counts."""
+    _fields_ = [("f", ctypes.c_int32), ("k", ctypes.c_int32),
+                ("entries", ctypes.c_void_p * MAX_ARRAYS), ("count", ctypes.c_int32 * MAX_ARRAYS)]
+
+
+class FlsimBulyanScratch(ctypes.Structure):
+    """flsim_bulyan_scratch (include/flsim.h): the caller's scratch and outputs of a Bulyan step."""
+    _fields_ = [("partials", ctypes.c_void_p), ("n_partials", ctypes.c_long),
+                ("dist", ctypes.c_void_p), ("score", ctypes.c_void_p), ("order", ctypes.c_void_p),
+                ("sel", ctypes.c_void_p)]
 
 
 class FlsimGeomed(ctypes.Structure):
@@ -306,6 +320,11 @@ def lib():
     L.flsim_krum_optim_step.argtypes = [vp, vp, vp, vp, vp, vp, vp, ctypes.c_long, ctypes.c_long,
                                         vp, vp]
     L.flsim_krum_eval_host.argtypes = [vp, ctypes.c_long, vp, vp, vp, vp]
+    L.flsim_bulyan_partials.restype = ctypes.c_long
+    L.flsim_bulyan_partials.argtypes = [ctypes.c_long, ctypes.c_int]
+    L.flsim_bulyan_optim_step.argtypes = [vp, vp, vp, vp, vp, vp, vp, ctypes.c_long, ctypes.c_long,
+                                          vp, vp]
+    L.flsim_bulyan_eval_host.argtypes = [vp, ctypes.c_long, vp, vp, vp, vp, vp]
     L.flsim_geomed_partials.restype = ctypes.c_long
     L.flsim_geomed_partials.argtypes = [ctypes.c_long, ctypes.c_int]
     L.flsim_geomed_tile_elems.restype = ctypes.c_long

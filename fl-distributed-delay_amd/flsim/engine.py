@@ -20,7 +20,8 @@ import torch
 
 import math
 
-from ._lib import (ATTACK_KINDS, MAX_ARRAYS, OPT_KINDS, ROBUST_KINDS, FlsimAttack, FlsimCclip,
+from ._lib import (ATTACK_KINDS, MAX_ARRAYS, OPT_KINDS, ROBUST_KINDS, FlsimAttack, FlsimBulyan,
+                   FlsimBulyanScratch, FlsimCclip,
                    FlsimCclipScratch, FlsimClip, FlsimGeomed, FlsimGeomedScratch, FlsimKrum,
                    FlsimKrumScratch, FlsimNnm, FlsimNnmScratch, FlsimOptim,
                    FlsimRobust, FlsimRule, FlsimRuleComp, FlsimRuleWeights, WorkerRec, check, lib,
@@ -472,6 +473,13 @@ class NetEngine:
         this network's P parameters; clip (a Clip) and g_out as krum_step."""
         krum_step(krum, theta, m, v, step, self.P, lr, betas, eps, optim=optim, clip=clip,
                   g_out=g_out)
+
+    def bulyan_step(self, bulyan, theta, m, v, step, lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
+                    optim=None, clip=None, g_out=None):
+        """Bulyan (a Bulyan over bucket sums) + Adam (or the update rule `optim`) over this
+        network's P parameters; clip (a Clip) and g_out as bulyan_step."""
+        bulyan_step(bulyan, theta, m, v, step, self.P, lr, betas, eps, optim=optim, clip=clip,
+                    g_out=g_out)
 
     def geomed_step(self, geomed, theta, m, v, step, lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
                     optim=None, clip=None, g_out=None):
@@ -1063,6 +1071,46 @@ def krum_step(krum, theta, m, v, step, P=None, lr=1e-3, betas=(0.9, 0.999), eps=
     (flsim_krum_optim_step); m / v, clip, g_out and optim=False as robust_step."""
     _bucket_step("flsim_krum_optim_step", krum, theta, m, v, step, P, lr, betas, eps, optim, clip,
                  g_out)
+
+
+class Bulyan(_BucketRule):
+    """Bulyan over bucket / class sums (flsim_bulyan, include/flsim.h): of the k = len(entries)
+    values entries[j] / counts[j], Krum's selection is repeated until theta = k - 2f are chosen,
+    then per coordinate the mean of the beta = k - 4f values closest to the median of the chosen
+    ones (k >= 4f + 3).  entries, counts as for Robust.  The object owns its scratch per (device,
+    P, k), allocated at the first step; after a step dist ([k, k] fp64), score ([theta] fp64:
+    the winning scores in round order), order ([theta] int32: the winners in round order) and sel
+    ([theta] int32, ascending) are device tensors, read with no synchronisation beyond the
+    stream's order; the next step overwrites them.  flsim/robust.py is the rule's text."""
+    _scratch = {}       # (device, P, k) -> buffers, shared by the objects of a run
+    _what, _kmin = "Bulyan", 3
+    _scratch_struct, _partials = FlsimBulyanScratch, "flsim_bulyan_partials"
+
+    def __init__(self, f, entries, counts):
+        self._set_entries(entries, counts)
+        self.f = int(f)
+        self.dist = self.score = self.order = self.sel = None
+
+    def c_struct(self):
+        r = FlsimBulyan()
+        r.f = self.f if -2 ** 31 <= self.f < 2 ** 31 else -1
+        return self._fill_entries(r)
+
+    def _scratch_rows(self, k):
+        f64, i32 = torch.float64, torch.int32
+        theta = max(min(k - 2 * self.f, MAX_ARRAYS), 0)     # (an f the library refuses: no views)
+        return (), (("dist", "dist", f64, k * k + 2, (k, k)),
+                    ("score", "score", f64, MAX_ARRAYS, (theta,)),
+                    ("order", "order", i32, MAX_ARRAYS, (theta,)),
+                    ("sel", "sel", i32, MAX_ARRAYS, (theta,)))
+
+
+def bulyan_step(bulyan, theta, m, v, step, P=None, lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
+                optim=None, clip=None, g_out=None):
+    """Bulyan + Adam(lr, betas, eps), or the update rule `optim`, in three launches
+    (flsim_bulyan_optim_step); m / v, clip, g_out and optim=False as robust_step."""
+    _bucket_step("flsim_bulyan_optim_step", bulyan, theta, m, v, step, P, lr, betas, eps, optim,
+                 clip, g_out)
 
 
 class GeoMed(_BucketRule):

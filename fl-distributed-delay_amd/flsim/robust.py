@@ -10,6 +10,7 @@ NaN where it gives a NaN.
     Agg(lambda ups: trimmed_mean_rule(ups, trim=1))   # drop the lowest and the highest, average
     Agg(lambda ups: krum_rule(ups, f=1))              # the update closest to its neighbours
     Agg(lambda ups: multi_krum_rule(ups, f=1, m=3))   # the mean of the three closest
+    Agg(lambda ups: bulyan_rule(ups, f=1))            # Krum repeated, then a mean around the median
     Agg(CenteredClip(tau=10.0, iters=1))              # centered clipping; the object keeps its center
     Agg(NNM(median_rule, f=1))                        # nearest-neighbour mixing, then any rule
 """
@@ -153,6 +154,117 @@ def krum_flat(entries, counts, f, m=1):
     cols = torch.stack(bucket_means(sums, counts))
     d, score, sel = krum_select(cols, f, m)
     return _krum(cols, f, m), d, score, sel
+
+
+# ---- Bulyan (El Mhamdi, Guerraoui and Rouault 2018): Krum's selection repeated until theta =
+# k - 2f entries are chosen, then per coordinate the mean of the beta = theta - 2f values closest to
+# the median of the chosen ones.  The yardstick of flsim_bulyan_optim_step (include/flsim.h) and of
+# its host twin, stage by stage at the device's own outputs: dist within 2 (P + 2) 2^-53 relative;
+# order, the winning scores (bit for bit) and sel equal to bulyan_order on that dist; g equal to
+# _bulyan_coord over that sel as numbers.
+BULYAN_KIND = "bulyan"
+
+
+def bulyan_order(d, f):
+    """d: [k, k] fp64 distance matrix, symmetric, zero diagonal, no NaN (NaN -> +inf), as
+    krum_select / pair_matrix form it.  theta = k - 2f rounds; in a round with r entries left, the
+    score of a remaining i is the sum of its n = max(r - f - 2, 1) smallest distances to the OTHER
+    remaining entries, added in ascending (value, index) order, sequential fp64 adds; the lowest
+    (score, index) wins and is removed.  r == 1 (only when f == 0): the one left wins, score 0.0.
+    -> (order: theta indices in round order, win: theta fp64 winning scores)."""
+    k = d.shape[0]
+    left = list(range(k))
+    order, win = [], []
+    for _ in range(k - 2 * f):
+        r = len(left)
+        if r == 1:
+            order.append(left[0])
+            win.append(torch.tensor(0.0, dtype=torch.float64))
+            break
+        n = max(r - f - 2, 1)
+        sc = {}
+        for i in left:
+            row = sorted((d[i, j].item(), j) for j in left if j != i)[:n]
+            acc = torch.tensor(row[0][0], dtype=torch.float64)
+            for v, _ in row[1:]:
+                acc = acc + v
+            sc[i] = acc
+        w = min(left, key=lambda i: (sc[i].item(), i))
+        order.append(w)
+        win.append(sc[w])
+        left.remove(w)
+    return order, torch.stack(win)
+
+
+def _bulyan_coord(s_cols, f):
+    """s_cols: [theta, numel] fp32, the selected bucket means.  Per coordinate: sort ascending (NaN
+    last), med = s[(theta-1)//2]; the window starts as {median} and grows beta - 1 times by the
+    closer of its two outer neighbours: right iff a right neighbour exists and (no left neighbour
+    or (s[hi+1] - med) < (med - s[lo-1]) in fp32; a false compare, ties and NaN included, goes
+    left).  g = the window's values added in ascending order, sequential fp32 adds, / float(beta)."""
+    th = s_cols.shape[0]
+    beta = th - 2 * f
+    s = s_cols.sort(0).values
+    mi = (th - 1) // 2
+    med = s[mi]
+    n = s.shape[1]
+    lo = torch.full((n,), mi)
+    hi = torch.full((n,), mi)
+    for _ in range(beta - 1):
+        lok, rok = lo > 0, hi < th - 1
+        dl = med - s.gather(0, (lo - 1).clamp(min=0)[None])[0]
+        dr = s.gather(0, (hi + 1).clamp(max=th - 1)[None])[0] - med
+        right = rok & (~lok | (dr < dl))
+        hi = torch.where(right, hi + 1, hi)
+        lo = torch.where(right, lo, lo - 1)
+    acc = torch.zeros(n)
+    started = torch.zeros(n, dtype=torch.bool)
+    for p in range(th):
+        inw = (p >= lo) & (p <= hi)
+        acc = torch.where(inw, torch.where(started, acc + s[p], s[p]), acc)
+        started |= inw
+    return acc / beta
+
+
+def check_bulyan(f, k):
+    """The cases the library refuses (ValueError), and rule()'s IndexError on an empty list."""
+    f = int(f)
+    if k == 0:
+        raise IndexError("empty weight_ups (reference: IndexError in rule, main.py:25)")
+    if f < 0 or k < 4 * f + 3:
+        raise ValueError(f"Invalid f = {f} for k = {k} entries: f >= 0 and k >= 4 * f + 3")
+    return f
+
+
+def _bulyan(cols, f):
+    """cols [k, numel] fp32 (bucket means) -> (g, dist, order, win, sel)."""
+    d, _, _ = krum_select(cols, 0, 1)        # (the distances alone: Krum's f and m play no part)
+    order, win = bulyan_order(d, f)
+    sel = sorted(order)
+    return _bulyan_coord(cols[sel], f), d, order, win, sel
+
+
+def bulyan_flat(entries, counts, f):
+    """The text over flat bucket SUMS (None = an all-zero entry) with their counts: what
+    flsim_bulyan_optim_step computes.  Returns (g, dist, order, win, sel), sel = sorted(order)."""
+    ref = next(e for e in entries if e is not None)
+    sums = [torch.zeros_like(ref) if e is None else e for e in entries]
+    f = check_bulyan(f, len(sums))
+    return _bulyan(torch.stack(bucket_means(sums, counts)), f)
+
+
+def bulyan_rule(ups_list, f):
+    """rule() with Bulyan: Krum's selection repeated until len(ups_list) - 2f updates are chosen,
+    then per coordinate the mean of the len(ups_list) - 4f values closest to the median of the
+    chosen ones, over all tensors flattened together (the distances are over the whole model)."""
+    f = check_bulyan(f, len(ups_list))
+    cols = torch.stack([torch.cat([u.reshape(-1) for u in ups]) for ups in ups_list])
+    g = _bulyan(cols, f)[0]
+    out, off = [], 0
+    for u in ups_list[0]:
+        out.append(g[off:off + u.numel()].view(u.shape))
+        off += u.numel()
+    return out
 
 
 # ---- Nearest-neighbour mixing (NNM; Allouah et al. 2023, "Fixing by Mixing"): a pre-aggregation
@@ -501,7 +613,8 @@ class CenteredClip:
 def parse_rule(spec):
     """FLSimulation's robust_rule argument -> (kind, trim): None, "median", "trimmed_mean" (trim
     0), or ("trimmed_mean", trim); or ("krum", f) -> ("krum", f, 1) and ("multi_krum", f, m) as
-    it stands (f has no default: the bare strings are refused); or "geomed", ("geomed", iters),
+    it stands (f has no default: the bare strings are refused); or ("bulyan", f) as it stands
+    (the bare string is refused, like Krum's); or "geomed", ("geomed", iters),
     ("geomed", iters, nu), ("geomed", iters, nu, "uniform" | "count") -> ("geomed", iters, nu,
     weights), defaults 3, 1e-6, "uniform"; or ("cclip", tau), ("cclip", tau, iters), ("cclip", tau,
     iters, "uniform" | "count") -> ("cclip", tau, iters, weights), defaults 1, "uniform" (tau has
@@ -540,6 +653,13 @@ def parse_rule(spec):
         if f < 0 or m < 1:
             raise ValueError(f"robust_rule {spec!r}: f must be >= 0 and m >= 1")
         return kind, f, m
+    if kind == BULYAN_KIND:
+        if len(spec) != 2:
+            raise ValueError(f"robust_rule {spec!r} (supported: ('bulyan', f))")
+        f = int(spec[1])
+        if f < 0:
+            raise ValueError(f"robust_rule {spec!r}: f must be >= 0")
+        return kind, f
     if kind not in KINDS or len(spec) > 2:
         raise ValueError(f"robust_rule {spec!r} (supported: None, 'median', ('trimmed_mean', trim), "
                          "('krum', f), ('multi_krum', f, m))")

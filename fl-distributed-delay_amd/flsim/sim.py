@@ -59,8 +59,8 @@ import torch
 from .data import DevicePool, make_test_pool
 from .engine import (PN1_SIZES, Clip, Optim, ProgramStager, Rule, engine_class, optim_defaults,
                      padded, split_views, staleness_weight)
-from .robust import (CCLIP_KIND, GEOMED_KIND, KRUM_KINDS, alie_z, check_krum, check_nnm,
-                     parse_attack, parse_rule)
+from .robust import (BULYAN_KIND, CCLIP_KIND, GEOMED_KIND, KRUM_KINDS, alie_z, check_bulyan,
+                     check_krum, check_nnm, parse_attack, parse_rule)
 from .schedule import Schedule, reference_delays
 
 SEMANTICS = ("reference", "torch1", "independent")
@@ -108,13 +108,13 @@ class FLSimulation:
         if semantics not in SEMANTICS:
             raise NotImplementedError(f"semantics {semantics!r} (supported: {SEMANTICS})")
         # a robust rule in place of the mean (None: off; today's code paths exactly): (kind, trim),
-        # ("krum" | "multi_krum", f, m), ("geomed", iters, nu, weights), or ("cclip", tau, iters,
-        # weights)
+        # ("krum" | "multi_krum", f, m), ("bulyan", f), ("geomed", iters, nu, weights), or ("cclip",
+        # tau, iters, weights)
         self.robust = parse_rule(robust_rule)
         self.buckets = int(buckets)
         self.keep_entries = bool(keep_entries)
         self.last_entries = None
-        self.last_selected = None       # Krum / Multi-Krum with keep_entries: the entries chosen
+        self.last_selected = None       # Krum family with keep_entries: the entries chosen
         self.sel_log = []               # per epoch: list of ints (read back) or a device tensor
         self.last_geomed = None         # the geometric median with keep_entries: the epoch's GeoMed
         self.geomed_entries = []        # per epoch: (obj, final w), device tensors or read back
@@ -826,6 +826,18 @@ class FLSimulation:
             self.sel_log.append(krum.sel.detach().clone())      # (a device tensor: no sync)
             if self.keep_entries:           # (reads the device selection back: synchronises)
                 self.last_selected = [int(j) for j in krum.sel.tolist()]
+        elif self.robust[0] == BULYAN_KIND:
+            # Bulyan: f against this epoch's k, as Krum's
+            from .engine import Bulyan
+            _, f = self.robust
+            check_bulyan(f, len(entries))
+            self.step += 1
+            bul = Bulyan(f, [e[:self.P] for e in entries], counts)
+            eng.bulyan_step(bul, self.theta, self.m, self.v, self.step, optim=self.optim,
+                            clip=self.clip)
+            self.sel_log.append(bul.sel.detach().clone())       # (a device tensor: no sync)
+            if self.keep_entries:           # (reads the device selection back: synchronises)
+                self.last_selected = [int(j) for j in bul.sel.tolist()]
         elif self.robust[0] == CCLIP_KIND:
             # centered clipping around the last epoch's aggregate (the first step: around zero,
             # the center's memory is then not read)
@@ -939,7 +951,7 @@ class FLSimulation:
         return list(self.norm_log)
 
     def selections(self):
-        """The entries Krum / Multi-Krum selected in every epoch (else []), as lists of ints:
+        """The entries Krum, Multi-Krum or Bulyan selected in every epoch (else []), as lists of ints:
         indices into the epoch's entries, the fresh buckets first, then the popped slots.
         Synchronises on the first call after new epochs."""
         self.sel_log = [x if isinstance(x, list) else [int(j) for j in x.tolist()]

@@ -15,6 +15,9 @@ coordinate-wise median or trimmed mean over B bucket means of the fast workers a
 delay-class entries (needs --semantics independent).  --robust_rule {krum,multi_krum} with
 --byz_f F (and --krum_m M) picks the entry closest to its k - F - 2 nearest neighbours, or averages
 the M such entries (Blanchard et al. 2017), and logs the chosen entries as 'Krum Selected'.
+--robust_rule bulyan with --byz_f F repeats Krum's selection until k - 2F entries are chosen and
+takes, per coordinate, the mean of the k - 4F values closest to their median (El Mhamdi et al.
+2018; the epoch's entry count k >= 4F + 3), and logs the chosen entries as 'Bulyan Selected'.
 --robust_rule geomed with --geomed_iters R, --geomed_nu NU and --geomed_weights {uniform,count}
 takes the geometric median of the entries by R smoothed Weiszfeld iterations (RFA, Pillutla et
 al. 2022; no Byzantine count needed) and logs the objective at every iterate as 'GeoMed Objective'.
@@ -108,10 +111,11 @@ def parse(argv=None):
                    help='clip the aggregated gradient to this global 2-norm before the update, '
                         'as torch.nn.utils.clip_grad_norm_ (default: off; inf only logs the norm)')
     p.add_argument('--robust_rule', default='none',
-                   choices=['none', 'median', 'trimmed_mean', 'krum', 'multi_krum', 'geomed',
-                            'cclip'],
+                   choices=['none', 'median', 'trimmed_mean', 'krum', 'multi_krum', 'bulyan',
+                            'geomed', 'cclip'],
                    help='aggregate with the coordinate-wise median or trimmed mean, with Krum / '
-                        'Multi-Krum, with the geometric median (RFA) or with centered clipping, '
+                        'Multi-Krum, with Bulyan, with the geometric median (RFA) or with centered '
+                        'clipping, '
                         'over bucket means instead of the mean (needs --semantics independent; '
                         'default: none)')
     p.add_argument('--cclip_tau', type=float, default=None, metavar='T',
@@ -131,8 +135,9 @@ def parse(argv=None):
                    help="--robust_rule geomed: weigh every entry alike, or by its workers' count "
                         '(default uniform)')
     p.add_argument('--byz_f', type=int, default=None, metavar='F',
-                   help="--robust_rule krum / multi_krum: the Byzantine entries tolerated, the "
-                        "epoch's entry count >= 2F + 3 (required: no default)")
+                   help="--robust_rule krum / multi_krum / bulyan: the Byzantine entries tolerated, "
+                        "the epoch's entry count >= 2F + 3 (bulyan: >= 4F + 3) (required: no "
+                        "default)")
     p.add_argument('--krum_m', type=int, default=1, metavar='M',
                    help='--robust_rule multi_krum: entries averaged, 1 <= M <= the entry count - F '
                         '(default 1)')
@@ -200,6 +205,10 @@ def robust_spec(args):
             raise SystemExit(f"--robust_rule {args.robust_rule} needs --byz_f F")
         return ('krum', args.byz_f) if args.robust_rule == 'krum' else \
             ('multi_krum', args.byz_f, args.krum_m)
+    if args.robust_rule == 'bulyan':
+        if args.byz_f is None:
+            raise SystemExit("--robust_rule bulyan needs --byz_f F")
+        return ('bulyan', args.byz_f)
     if args.robust_rule == 'geomed':
         return ('geomed', args.geomed_iters, args.geomed_nu, args.geomed_weights)
     if args.robust_rule == 'cclip':
@@ -297,6 +306,8 @@ def main(argv=None):
             emit("Grad Norm", sim.grad_norms()[-1], t)
         if args.robust_rule in ('krum', 'multi_krum'):
             emit("Krum Selected", sim.selections()[-1], t)
+        if args.robust_rule == 'bulyan':
+            emit("Bulyan Selected", sim.selections()[-1], t)
         if args.attack != 'none':
             emit("Attack", list(sim.attack_log()[-1]), t)
         if rank == 0 and (t % 10 == 0 or t == args.n_epochs - 1):

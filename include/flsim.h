@@ -705,6 +705,74 @@ int flsim_krum_eval_host(const flsim_krum* r, long P, double* dist, double* scor
                          float* g_out);
 
 /* ---------------------------------------------------------------------------------------------
+ * Bulyan (El Mhamdi, Guerraoui and Rouault 2018) over bucket means, fused with the update: Krum's
+ * selection repeated until theta = k - 2f entries are chosen, then per coordinate the mean of the
+ * beta = theta - 2f = k - 4f values closest to the median of the chosen ones.  The text
+ * (flsim/robust.py, plain torch; d is krum_select's matrix):
+ *
+ *   def bulyan_order(d, f):
+ *       k = d.shape[0]; left = list(range(k)); order, win = [], []
+ *       for _ in range(k - 2 * f):
+ *           r = len(left)
+ *           if r == 1:                                # (only when f == 0)
+ *               order.append(left[0]); win.append(0.0); break
+ *           n = max(r - f - 2, 1); sc = {}
+ *           for i in left:                            # ascending (value, index), sequential fp64 adds
+ *               row = sorted((d[i, j].item(), j) for j in left if j != i)[:n]
+ *               sc[i] = sum of row's values in that order
+ *           w = min(left, key=lambda i: (sc[i], i))   # ties: lowest index
+ *           order.append(w); win.append(sc[w]); left.remove(w)
+ *       return order, win
+ *   def _bulyan_coord(s_cols, f):                     # [theta, numel] fp32, the selected means
+ *       sort ascending (NaN last); med = s[(theta - 1) // 2]; the window starts as {median} and
+ *       grows beta - 1 times by the closer of its two outer neighbours: right iff a right
+ *       neighbour exists and (no left neighbour or (s[hi + 1] - med) < (med - s[lo - 1]) in fp32;
+ *       a false compare, ties and NaN included, goes left); g = the window's values added in
+ *       ascending order, sequential fp32 adds, / float(beta)
+ *
+ * Per element x_j = entries[j][e] / (float)count[j] as for flsim_robust; a NULL entry is all zero.
+ * Three launches on `stream`, no host synchronisation, no atomics: the distance launch of
+ * flsim_krum_optim_step (same kernel, same geometry, same sums) into s->partials; a one-block launch
+ * adds the partials in Krum's fixed order, writes s->dist (the matrix flsim_krum_optim_step and
+ * flsim_nnm_entries write, bit for bit), ranks every row's neighbours once and runs the theta
+ * rounds, writing s->score (the winning scores in round order), s->order and s->sel; the apply
+ * launch reads sel on the device, loads the theta selected entries only, sorts them per element,
+ * forms g as the text does and runs the update of `optim` (every kind).
+ *   dist: within 2 (P + 2) 2^-53 relative of the text; order, score and sel equal, score bit for
+ *   bit, the text's bulyan_order applied to the device's own dist; g equals _bulyan_coord over the
+ *   device's own sel as numbers (the same 32 bits wherever the text's value is neither zero nor
+ *   NaN, a zero where it gives a zero, a NaN where it gives a NaN).
+ * g_out, optim == NULL and clip as for flsim_krum_optim_step.  The library never allocates: the
+ * caller provides the scratch, and nothing depends on what it held before.
+ * Checked before any pointer, status 1: k outside [3, FLSIM_MAX_ARRAYS]; f < 0 or k < 4f + 3; a
+ * count < 1; what flsim_optim and flsim_clip are refused for.  Then: what flsim_krum_optim_step
+ * refuses about p / m / v / g_out / P / clip and the entries; a NULL or misaligned (16 bytes)
+ * scratch pointer; n_partials too small; an entry overlapping the scratch.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct flsim_bulyan {
+    int32_t f, k;                               /* k >= 4f+3, f >= 0, k <= FLSIM_MAX_ARRAYS */
+    const float* entries[FLSIM_MAX_ARRAYS];     /* bucket / class SUMS; NULL = all zero */
+    int32_t count[FLSIM_MAX_ARRAYS];            /* >= 1 */
+} flsim_bulyan;
+typedef struct flsim_bulyan_scratch {           /* caller-provided; the library never allocates */
+    double* partials; long n_partials;          /* >= flsim_bulyan_partials(P, k) */
+    double* dist;                               /* [k*k]   out: the distance matrix */
+    double* score;                              /* [theta] out: the winning scores, round order */
+    int32_t* order;                             /* [theta] out: the winners, round order */
+    int32_t* sel;                               /* [theta] out: the winners, ascending */
+} flsim_bulyan_scratch;
+/* the doubles the distance launch writes: flsim_krum_partials(P, k) (0: P or k out of range) */
+long flsim_bulyan_partials(long P, int k);
+int flsim_bulyan_optim_step(const flsim_bulyan* r, const flsim_bulyan_scratch* s,
+                            const flsim_clip* clip, float* g_out, float* p, float* m, float* v,
+                            long P, long step, const flsim_optim* optim, flsim_stream_t stream);
+/* host (testing): dist [k*k], score, order, sel [theta] and g (g_out nullable) of the text for host
+ * pointers: the distances summed in element order, then the selection code the finish kernel runs
+ * and the window / sum code the apply kernel runs; refuses what the entry point refuses about r */
+int flsim_bulyan_eval_host(const flsim_bulyan* r, long P, double* dist, double* score,
+                           int32_t* order, int32_t* sel, float* g_out);
+
+/* ---------------------------------------------------------------------------------------------
  * Geometric median over bucket means by smoothed Weiszfeld iterations ("RFA", Pillutla, Kakade and
  * Harchaoui 2022), fused with the update.  Breakdown point 1/2, no Byzantine count from the user;
  * where Krum selects, it re-weights the entries continuously by 1 / distance to the iterate.  The
