@@ -39,6 +39,7 @@
 #include <type_traits>
 
 #include "attack.h"
+#include "attack_opt.h"
 #include "bulyan.h"
 #include "cclip.h"
 #include "common.h"
@@ -2983,7 +2984,10 @@ struct AttackArgs {
     int32_t honest[RULE_MAX_ARR];       // > 0: the entry is read
     int32_t byz[RULE_MAX_ARR];          // > 0: the entry is written
     float* b_out;                       // nullable
-    double strength;
+    union {
+        double strength;
+        const double* coef;             // the optimised attacks' mix: gamma * strength, which
+    };                                  // k_attack_opt_finish wrote (device memory)
     long P;
     int k, kh, ntiles;
 };
@@ -3081,9 +3085,17 @@ __global__ void __launch_bounds__(256) k_attack(AttackArgs A) {
             }
         }
         float b[U];
+        if constexpr (KIND >= ATTACK_CRAFT_OPT) {
+            const double coef = A.coef[0];          // launch-uniform: one scalar load
 #pragma unroll
-        for (int u = 0; u < U; ++u)
-            b[u] = attack_craft<KPAD, KIND>(x[u], s_hon, hm, k, (double)A.kh, A.strength);
+            for (int u = 0; u < U; ++u)
+                b[u] = attack_opt_craft<KPAD, KIND - ATTACK_CRAFT_OPT>(x[u], s_hon, hm, k,
+                                                                       (double)A.kh, coef);
+        } else {
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+                b[u] = attack_craft<KPAD, KIND>(x[u], s_hon, hm, k, (double)A.kh, A.strength);
+        }
         if (A.b_out) {
 #pragma unroll
             for (int u = 0; u < U; ++u)
@@ -3114,30 +3126,48 @@ static void launch_attack(int kind, dim3 grid, hipStream_t stream, const ProbeSl
     if (kind == FLSIM_ATTACK_IPM)
         hipExtLaunchKernelGGL((k_attack<KPAD, FLSIM_ATTACK_IPM>), grid, dim3(256), 0, stream,
                               ps.start, ps.stop, 0, A);
-    else
+    else if (kind == FLSIM_ATTACK_ALIE)
         hipExtLaunchKernelGGL((k_attack<KPAD, FLSIM_ATTACK_ALIE>), grid, dim3(256), 0, stream,
                               ps.start, ps.stop, 0, A);
+    else if (kind == ATTACK_CRAFT_OPT + FLSIM_ATTACK_DIR_UNIT)
+        hipExtLaunchKernelGGL((k_attack<KPAD, ATTACK_CRAFT_OPT + FLSIM_ATTACK_DIR_UNIT>), grid,
+                              dim3(256), 0, stream, ps.start, ps.stop, 0, A);
+    else if (kind == ATTACK_CRAFT_OPT + FLSIM_ATTACK_DIR_STD)
+        hipExtLaunchKernelGGL((k_attack<KPAD, ATTACK_CRAFT_OPT + FLSIM_ATTACK_DIR_STD>), grid,
+                              dim3(256), 0, stream, ps.start, ps.stop, 0, A);
+    else
+        hipExtLaunchKernelGGL((k_attack<KPAD, ATTACK_CRAFT_OPT + FLSIM_ATTACK_DIR_SIGN>), grid,
+                              dim3(256), 0, stream, ps.start, ps.stop, 0, A);
 }
+
+static int check_attack_counts(int k, double strength, const int32_t* honest, const int32_t* byz,
+                               int* kh);
 
 // flsim_attack's fields, before any pointer is looked at; *kh: the entries with honest >= 1
 static int check_attack(const flsim_attack* a, int* kh) {
     FLSIM_REQUIRE(a, "null attack");
     FLSIM_REQUIRE(a->kind == FLSIM_ATTACK_IPM || a->kind == FLSIM_ATTACK_ALIE,
                   "Invalid attack kind %d (0: ipm, 1: alie)", a->kind);
-    FLSIM_REQUIRE(a->k >= 1 && a->k <= RULE_MAX_ARR, "attack over k = %d entries (1 .. %d)", a->k,
+    return check_attack_counts(a->k, a->strength, a->honest, a->byz, kh);
+}
+
+// ... what flsim_attack and flsim_attack_opt share after the kind: k, the strength, the counts
+static int check_attack_counts(int k, double strength, const int32_t* honest, const int32_t* byz,
+                               int* kh) {
+    FLSIM_REQUIRE(k >= 1 && k <= RULE_MAX_ARR, "attack over k = %d entries (1 .. %d)", k,
                   RULE_MAX_ARR);
-    FLSIM_REQUIRE(a->strength >= 0.0 && a->strength < (double)__builtin_inff(),
-                  "Invalid attack strength = %g: it must be finite and >= 0", a->strength);
+    FLSIM_REQUIRE(strength >= 0.0 && strength < (double)__builtin_inff(),
+                  "Invalid attack strength = %g: it must be finite and >= 0", strength);
     int nh = 0, nb = 0;
-    for (int j = 0; j < a->k; ++j) {
-        FLSIM_REQUIRE(a->honest[j] >= 0, "Invalid honest count %d of entry %d: it must be >= 0",
-                      a->honest[j], j);
-        FLSIM_REQUIRE(a->byz[j] >= 0, "Invalid Byzantine count %d of entry %d: it must be >= 0",
-                      a->byz[j], j);
-        FLSIM_REQUIRE(a->honest[j] > 0 || a->byz[j] > 0, "entry %d holds no worker: honest + byz "
+    for (int j = 0; j < k; ++j) {
+        FLSIM_REQUIRE(honest[j] >= 0, "Invalid honest count %d of entry %d: it must be >= 0",
+                      honest[j], j);
+        FLSIM_REQUIRE(byz[j] >= 0, "Invalid Byzantine count %d of entry %d: it must be >= 0",
+                      byz[j], j);
+        FLSIM_REQUIRE(honest[j] > 0 || byz[j] > 0, "entry %d holds no worker: honest + byz "
                       "must be >= 1", j);
-        nh += a->honest[j] > 0;
-        nb += a->byz[j] > 0;
+        nh += honest[j] > 0;
+        nb += byz[j] > 0;
     }
     FLSIM_REQUIRE(nh >= 1, "ValueError: no entry holds an honest worker: the attacker has nothing "
                   "to observe");
@@ -3147,18 +3177,17 @@ static int check_attack(const flsim_attack* a, int* kh) {
 }
 
 // ... and the pointers: every entry is read or written
-static int check_attack_pointers(const flsim_attack* a, const float* b_out, long P) {
-    for (int j = 0; j < a->k; ++j) {
-        FLSIM_REQUIRE(a->entries[j], "null entry %d", j);
-        FLSIM_REQUIRE(((uintptr_t)a->entries[j] & 15) == 0, "entry %d must be 16-byte aligned", j);
+static int check_attack_pointers(float* const* entries, int k, const float* b_out, long P) {
+    for (int j = 0; j < k; ++j) {
+        FLSIM_REQUIRE(entries[j], "null entry %d", j);
+        FLSIM_REQUIRE(((uintptr_t)entries[j] & 15) == 0, "entry %d must be 16-byte aligned", j);
     }
     FLSIM_REQUIRE(((uintptr_t)b_out & 15) == 0, "b_out must be 16-byte aligned");
     FLSIM_REQUIRE(P > 0 && P < (1L << 31), "P = %ld out of range", P);
-    for (int j = 0; j < a->k; ++j) {
+    for (int j = 0; j < k; ++j) {
         for (int q = 0; q < j; ++q)
-            FLSIM_REQUIRE(!overlaps(a->entries[q], a->entries[j], P), "entries %d and %d overlap",
-                          q, j);
-        FLSIM_REQUIRE(!overlaps(a->entries[j], b_out, P), "entry %d overlaps b_out", j);
+            FLSIM_REQUIRE(!overlaps(entries[q], entries[j], P), "entries %d and %d overlap", q, j);
+        FLSIM_REQUIRE(!overlaps(entries[j], b_out, P), "entry %d overlaps b_out", j);
     }
     return 0;
 }
@@ -3179,6 +3208,208 @@ static void attack_eval_host(const flsim_attack* a, int kh, float* b_out, long P
         for (int j = 0; j < RULE_MAX_ARR; ++j) x[j] = ((hm >> j) & 1) ? a->entries[j][e] : 0.f;
         const float b = attack_craft<RULE_MAX_ARR, KIND>(x, hon, hm, a->k, (double)kh,
                                                          a->strength);
+        if (b_out) b_out[e] = b;
+        for (int j = 0; j < a->k; ++j)
+            if (a->byz[j] > 0)
+                a->entries[j][e] = attack_mix(x[j], (hm >> j) & 1, b, (float)a->byz[j]);
+    }
+}
+
+// ================================================================================================
+// The optimised attacks Min-Max and Min-Sum: the stats launch, the pairwise-distance stage over the
+// honest entries, the finish (the matrix, the sums, gamma), then k_attack's mix (include/flsim.h:
+// flsim_attack_opt; csrc/attack_opt.h: the geometry, the element code and the scalar solve shared
+// with the host)
+// ================================================================================================
+struct AttackOptStatsArgs {
+    const float* ent[RULE_MAX_ARR];     // the kh honest entries, compacted in index order
+    int32_t honest[RULE_MAX_ARR];
+    double* partials;                   // [2 * kh + 1][blocks], slot-major
+    long P;
+    int kh, ntiles;
+};
+static_assert(sizeof(AttackOptStatsArgs) <= 4096, "kernel argument block");
+
+// One streaming pass, the shape of k_attack and k_geomed_dist: thread t of the block's 256 owns
+// the elements u * 256 + t, u < U, of a tile and a block grid-strides over the tiles; the table
+// (the address loaded, (double)honest) is built in LDS by wave 0 and read by broadcast; all loads
+// of a thread's elements are issued before any arithmetic; a padding entry loads entry 0 and an
+// element past P loads element 0, and both are dropped.  Per element attack_opt_stats_elem
+// (csrc/attack_opt.h) forms y_j, mu, p and the 2 * kh + 1 products and adds them to the thread's
+// sums: tiles in the block's order, u ascending.  Then every sum is added over the wave by a
+// butterfly and over the four waves as (w0 + w1) + (w2 + w3), as dist_reduce does, and thread s
+// stores slot s.
+template <int KPAD, int DIR>
+__global__ void __launch_bounds__(256) k_attack_opt_stats(AttackOptStatsArgs A) {
+#pragma clang fp contract(off)
+    constexpr int U = attack_opt_unroll(KPAD), E = attack_opt_tile_elems(KPAD);
+    constexpr int GRP = KPAD < 8 ? KPAD : 8;
+    __shared__ unsigned long long s_ent[KPAD];
+    __shared__ double s_hon[KPAD];
+    __shared__ double red[4][2 * KPAD + 1];
+    {
+        const int j = threadIdx.x;
+        if (j < KPAD) {
+            const bool in = j < A.kh;
+            s_ent[j] = (unsigned long long)(uintptr_t)(in ? A.ent[j] : A.ent[0]);
+            s_hon[j] = in ? (double)A.honest[j] : 1.0;
+        }
+        __syncthreads();
+    }
+    double a[KPAD], c[KPAD], q = 0.0;
+#pragma unroll
+    for (int j = 0; j < KPAD; ++j) a[j] = c[j] = 0.0;
+    for (int tl = blockIdx.x; tl < A.ntiles; tl += gridDim.x) {
+        // the table is read, and k made scalar, again in every tile (k_attack)
+        asm volatile("" ::: "memory");
+        int k = A.kh;
+        asm volatile("" : "+v"(k));
+        k = __builtin_amdgcn_readfirstlane(k);
+        const long e0 = (long)tl * E + threadIdx.x;
+        bool inb[U];
+        long off[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            inb[u] = e0 + u * 256 < A.P;
+            off[u] = inb[u] ? e0 + u * 256 : 0;
+        }
+        float x[U][KPAD];
+#pragma unroll
+        for (int j0 = 0; j0 < KPAD; j0 += GRP) {
+            if (j0 < k) {
+#pragma unroll
+                for (int j = j0; j < j0 + GRP; ++j) {
+                    const GeomedGlobalF32 src = (GeomedGlobalF32)s_ent[j];
+#pragma unroll
+                    for (int u = 0; u < U; ++u)
+                        x[u][j] = __builtin_nontemporal_load(src + off[u]);
+                }
+            } else {
+#pragma unroll
+                for (int j = j0; j < j0 + GRP; ++j)
+#pragma unroll
+                    for (int u = 0; u < U; ++u) x[u][j] = 0.f;
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+            attack_opt_stats_elem<KPAD, DIR>(x[u], s_hon, k, (double)A.kh, inb[u], a, c, q);
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    auto wave_sum = [&](double v, int slot) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+        if (lane == 0) red[wave][slot] = v;
+    };
+#pragma unroll
+    for (int j = 0; j < KPAD; ++j) {
+        if (j < A.kh) {
+            wave_sum(a[j], j);
+            wave_sum(c[j], KPAD + j);
+        }
+    }
+    wave_sum(q, 2 * KPAD);
+    __syncthreads();
+    const int t = threadIdx.x, kh = A.kh;
+    if (t < 2 * kh + 1) {
+        const int slot = t < kh ? t : t < 2 * kh ? KPAD + (t - kh) : 2 * KPAD;
+        A.partials[(long)t * gridDim.x + blockIdx.x] =
+            (red[0][slot] + red[1][slot]) + (red[2][slot] + red[3][slot]);
+    }
+}
+
+struct AttackOptFinArgs {               // (entry_sums reads partials, nblocks and k)
+    const double* partials;             // the stats launch's, [k = 2 * kh + 1][nblocks]
+    int nblocks, k;
+};
+
+// One block of KRUM_FIN_THREADS: pair_matrix (the pairwise-distance stage, Krum's matrix), then
+// the stats partials by entry_sums (the distance-to-iterate stage's fixed order), then
+// attack_opt_gamma (csrc/attack_opt.h) on the matrix and the sums in LDS: thread i takes row i,
+// thread 0 the scalar code.  coef = gamma * strength goes to the last word of the partials: the
+// mix launch reads it from there (k_attack's argument block has no room for a second scalar).
+__global__ void __launch_bounds__(KRUM_FIN_THREADS)
+k_attack_opt_finish(const double* partials, int nblocks, int nb, int kh, AttackOptFinArgs S,
+                    int kind, double strength, double* dist, double* stats, double* gamma,
+                    double* coef) {
+    static_assert(KRUM_FIN_THREADS == GEOMED_FIN_THREADS, "entry_sums' block");
+    __shared__ double sd[RULE_MAX_ARR * RULE_MAX_ARR];
+    __shared__ double ss[2 * RULE_MAX_ARR + 1];
+    __shared__ double rmax[RULE_MAX_ARR], rsum[RULE_MAX_ARR];
+    pair_matrix(partials, nblocks, nb, kh, sd, dist);
+    entry_sums(S, ss);
+    __syncthreads();
+    const int t = threadIdx.x;
+    if (t < kh) {
+        stats[t] = ss[t];
+        stats[RULE_MAX_ARR + t] = ss[kh + t];
+    }
+    if (t == 0) stats[2 * RULE_MAX_ARR] = ss[2 * kh];
+    const double g = attack_opt_gamma(kind, ss, ss + kh, ss[2 * kh], sd, kh, rmax, rsum, t,
+                                      KRUM_FIN_THREADS, [] { __syncthreads(); });
+    if (t == 0) {
+        gamma[0] = g;
+        coef[0] = g * strength;         // the mix's scalar: one multiply, here
+    }
+}
+
+// flsim_attack_opt's fields, before any pointer is looked at; *kh: the entries with honest >= 1
+static int check_attack_opt(const flsim_attack_opt* a, int* kh) {
+    FLSIM_REQUIRE(a, "null attack");
+    FLSIM_REQUIRE(a->kind == FLSIM_ATTACK_MINMAX || a->kind == FLSIM_ATTACK_MINSUM,
+                  "Invalid attack kind %d (2: minmax, 3: minsum)", a->kind);
+    FLSIM_REQUIRE(a->dir == FLSIM_ATTACK_DIR_UNIT || a->dir == FLSIM_ATTACK_DIR_STD ||
+                  a->dir == FLSIM_ATTACK_DIR_SIGN,
+                  "Invalid attack direction %d (0: unit, 1: std, 2: sign)", a->dir);
+    return check_attack_counts(a->k, a->strength, a->honest, a->byz, kh);
+}
+
+// with_dir: FLSIM_ATTACK_DIR_* as a constant
+template <class F>
+static void with_dir(int dir, F&& f) {
+    if (dir == FLSIM_ATTACK_DIR_UNIT) f(IntC<FLSIM_ATTACK_DIR_UNIT>{});
+    else if (dir == FLSIM_ATTACK_DIR_STD) f(IntC<FLSIM_ATTACK_DIR_STD>{});
+    else f(IntC<FLSIM_ATTACK_DIR_SIGN>{});
+}
+
+// host (testing): given the distances (the pairwise stage's host twin over the honest entries'
+// fp32 means), the sums by csrc/attack_opt.h's element code in element order, gamma by its
+// scalar code, then the mix over host pointers
+template <int DIR>
+static void attack_opt_eval_host(const flsim_attack_opt* a, int kh, double* stats, double* gamma,
+                                 const double* dist, float* b_out, long P) {
+    constexpr int K = RULE_MAX_ARR;
+    const float* hent[K];
+    double hcd[K], hon[K];
+    uint64_t hm = 0;
+    for (int j = 0, i = 0; j < K; ++j) {
+        hon[j] = hcd[j] = 1.0;
+        if (j < a->k && a->honest[j] > 0) {
+            hm |= 1ull << j;
+            hon[j] = (double)a->honest[j];
+            hent[i] = a->entries[j];
+            hcd[i++] = (double)a->honest[j];
+        }
+    }
+    double sa[K], sc[K], q = 0.0, rmax[K], rsum[K];
+    for (int j = 0; j < K; ++j) sa[j] = sc[j] = 0.0;
+    for (long e = 0; e < P; ++e) {
+        float x[K];
+        for (int i = 0; i < K; ++i) x[i] = i < kh ? hent[i][e] : 0.f;
+        attack_opt_stats_elem<K, DIR>(x, hcd, kh, (double)kh, true, sa, sc, q);
+    }
+    for (int i = 0; i < FLSIM_ATTACK_OPT_STATS; ++i) stats[i] = 0.0;
+    for (int i = 0; i < kh; ++i) {
+        stats[i] = sa[i];
+        stats[K + i] = sc[i];
+    }
+    stats[2 * K] = q;
+    gamma[0] = attack_opt_gamma((int)a->kind, sa, sc, q, dist, kh, rmax, rsum, 0, 1, [] {});
+    const double coef = gamma[0] * a->strength;
+    for (long e = 0; e < P; ++e) {
+        float x[K];
+        for (int j = 0; j < K; ++j) x[j] = ((hm >> j) & 1) ? a->entries[j][e] : 0.f;
+        const float b = attack_opt_craft<K, DIR>(x, hon, hm, a->k, (double)kh, coef);
         if (b_out) b_out[e] = b;
         for (int j = 0; j < a->k; ++j)
             if (a->byz[j] > 0)
@@ -4414,7 +4645,7 @@ long flsim_attack_tile_elems(int k) {
 int flsim_attack_entries(const flsim_attack* a, float* b_out, long P, hipStream_t stream) {
     int kh = 0;
     RC(check_attack(a, &kh));
-    RC(check_attack_pointers(a, b_out, P));
+    RC(check_attack_pointers(a->entries, a->k, b_out, P));
     AttackArgs A{};
     int nread = 0, nwritten = 0;
     for (int j = 0; j < a->k; ++j) {
@@ -4446,11 +4677,151 @@ int flsim_attack_entries(const flsim_attack* a, float* b_out, long P, hipStream_
 int flsim_attack_eval_host(const flsim_attack* a, float* b_out, long P) {
     int kh = 0;
     RC(check_attack(a, &kh));
-    RC(check_attack_pointers(a, b_out, P));
+    RC(check_attack_pointers(a->entries, a->k, b_out, P));
     if (a->kind == FLSIM_ATTACK_IPM)
         attack_eval_host<FLSIM_ATTACK_IPM>(a, kh, b_out, P);
     else
         attack_eval_host<FLSIM_ATTACK_ALIE>(a, kh, b_out, P);
+    return 0;
+}
+
+// ---- the optimised attacks Min-Max / Min-Sum mixed into the bucket sums (include/flsim.h) ---------
+long flsim_attack_opt_partials(long P, int k) {
+    if (k < 1 || k > RULE_MAX_ARR || P < 1 || P >= (1L << 31)) return 0;
+    long n = 0;
+    for (int kh = 1; kh <= k; ++kh) {
+        const long m = pair_partials(P, kh) + attack_opt_stats_partials(P, kh) + 1;
+        n = m > n ? m : n;
+    }
+    return n;
+}
+
+long flsim_attack_opt_tile_elems(int kh) {
+    if (kh < 1 || kh > RULE_MAX_ARR) return 0;
+    return attack_opt_tile_elems(attack_opt_kpad(kh));
+}
+
+// Four launches on `stream`: k_attack_opt_stats -> the second part of s->partials; k_krum_dist
+// over the honest entries -> the first part (Krum's launch and geometry); k_attack_opt_finish ->
+// s->dist, s->stats, s->gamma and gamma * strength in the last word of the partials; k_attack's
+// mix, which reads that word.  (The stats launch goes first:
+// the pairwise stage issues its finish right after its distance launch, and the two streaming
+// launches do not depend on each other.)
+int flsim_attack_opt_entries(const flsim_attack_opt* a, const flsim_attack_opt_scratch* s,
+                             float* b_out, long P, hipStream_t stream) {
+    int kh = 0;
+    RC(check_attack_opt(a, &kh));
+    RC(check_attack_pointers(a->entries, a->k, b_out, P));
+    static const char name[] = "attack";
+    const flsim_attack_opt_scratch none{};
+    if (!s) s = &none;
+    const int k = a->k;
+    const long n_pair = pair_partials(P, kh), n_stats = attack_opt_stats_partials(P, kh);
+    constexpr int NS = 4;
+    const Span sc[NS] = {{s->partials, 8 * (n_pair + n_stats + 1)},
+                         {s->dist, 8L * kh * kh},
+                         {s->stats, 8L * FLSIM_ATTACK_OPT_STATS},
+                         {s->gamma, 8}};
+    RC(check_scratch_pointers(name, sc, NS, s->n_partials, n_pair + n_stats + 1));
+    // the entries (read or written) and b_out against the scratch, then the scratch against itself
+    StepBuffers B{};
+    B.P = P;
+    for (int c = 0; c < NS; ++c)
+        FLSIM_REQUIRE(!overlaps(sc[c].ptr, sc[c].bytes, b_out, 4 * P),
+                      "b_out overlaps the %s scratch", name);
+    EntryTable all{}, T{};
+    int distinct = 0;
+    int32_t ones[RULE_MAX_ARR], hcnt[RULE_MAX_ARR];
+    const float* hent[RULE_MAX_ARR];
+    for (int j = 0, i = 0; j < k; ++j) {
+        ones[j] = 1;
+        if (a->honest[j] > 0) {
+            hent[i] = a->entries[j];
+            hcnt[i++] = a->honest[j];
+        }
+    }
+    RC(fill_entries(B, a->entries, ones, k, name, sc, NS, nullptr, &all, &distinct));
+    RC(check_scratch(B, name, sc, NS, nullptr));
+    RC(fill_entries(B, hent, hcnt, kh, name, nullptr, 0, nullptr, &T, &distinct));
+    double* const stats_part = s->partials + n_pair;
+    const int spad = attack_opt_kpad(kh);
+    const long sblocks = attack_opt_blocks(P, spad);
+    {
+        AttackOptStatsArgs S{};
+        for (int i = 0; i < kh; ++i) {
+            S.ent[i] = hent[i];
+            S.honest[i] = hcnt[i];
+        }
+        S.partials = stats_part;
+        S.P = P;
+        S.kh = kh;
+        S.ntiles = (int)attack_opt_tiles(P, spad);
+        const ProbeSlot ps = probe_begin();
+        const dim3 grid((unsigned)sblocks);
+        with_kpad<4>(spad, [&](auto kp) {
+            with_dir(a->dir, [&](auto d) {
+                hipExtLaunchKernelGGL(
+                    (k_attack_opt_stats<decltype(kp)::value, decltype(d)::value>), grid, dim3(256),
+                    0, stream, ps.start, ps.stop, 0, S);
+            });
+        });
+        FLSIM_LAUNCH_CHECK();
+        // algorithmic HBM bytes: the honest entries read once
+        if (probe_end(ps, K_ATTACK, 4.0 * (double)P * kh)) return 2;
+    }
+    const AttackOptFinArgs F{stats_part, (int)sblocks, 2 * kh + 1};
+    RC(launch_pair_dist(T, s->partials, P, kh, K_ATTACK, distinct, K_ATTACK,
+                        8.0 * (double)sblocks * (2 * kh + 1) + 8.0 * (2 * kh + 2), stream,
+                        [&](const ProbeSlot& ps, const double* part, int nblocks, int nb) {
+                            hipExtLaunchKernelGGL(k_attack_opt_finish, dim3(1),
+                                                  dim3(KRUM_FIN_THREADS), 0, stream, ps.start,
+                                                  ps.stop, 0, part, nblocks, nb, kh, F,
+                                                  (int)a->kind, a->strength, s->dist, s->stats,
+                                                  s->gamma, stats_part + n_stats);
+                        }));
+    AttackArgs A{};
+    int nwritten = 0;
+    for (int j = 0; j < k; ++j) {
+        A.ent[j] = a->entries[j];
+        A.honest[j] = a->honest[j];
+        A.byz[j] = a->byz[j];
+        nwritten += a->byz[j] > 0;
+    }
+    A.b_out = b_out;
+    A.coef = stats_part + n_stats;
+    A.P = P;
+    A.k = k;
+    A.kh = kh;
+    const int kpad = attack_kpad(k);
+    A.ntiles = (int)attack_tiles(P, kpad);
+    const dim3 grid((unsigned)attack_blocks(P, kpad));
+    const ProbeSlot ps = probe_begin();
+    with_kpad<4>(kpad, [&](auto kp) {
+        launch_attack<decltype(kp)::value>(ATTACK_CRAFT_OPT + a->dir, grid, stream, ps, A);
+    });
+    FLSIM_LAUNCH_CHECK();
+    if (probe_end(ps, K_ATTACK, 4.0 * (double)P * (kh + nwritten + (b_out ? 1 : 0)))) return 2;
+    return 0;
+}
+
+// host (testing): the same checks about a, the entries, b_out and P, then attack_opt_eval_host
+int flsim_attack_opt_eval_host(const flsim_attack_opt* a, double* dist, double* stats,
+                               double* gamma, float* b_out, long P) {
+    int kh = 0;
+    RC(check_attack_opt(a, &kh));
+    RC(check_attack_pointers(a->entries, a->k, b_out, P));
+    FLSIM_REQUIRE(dist && stats && gamma, "null pointer");
+    const float* hent[RULE_MAX_ARR];
+    int32_t hcnt[RULE_MAX_ARR];
+    for (int j = 0, i = 0; j < a->k; ++j)
+        if (a->honest[j] > 0) {
+            hent[i] = a->entries[j];
+            hcnt[i++] = a->honest[j];
+        }
+    pair_dist_host([&](int j, long e) { return bucket_mean(hent, hcnt, j, e); }, kh, P, dist);
+    with_dir(a->dir, [&](auto d) {
+        attack_opt_eval_host<decltype(d)::value>(a, kh, stats, gamma, dist, b_out, P);
+    });
     return 0;
 }
 

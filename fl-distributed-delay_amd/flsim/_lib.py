@@ -60,6 +60,8 @@ EXPORTS = [
     "flsim_cclip_partials", "flsim_cclip_tile_elems", "flsim_cclip_optim_step",
     "flsim_cclip_eval_host",
     "flsim_nnm_partials", "flsim_nnm_tile_elems", "flsim_nnm_entries", "flsim_nnm_eval_host",
+    "flsim_attack_opt_partials", "flsim_attack_opt_tile_elems", "flsim_attack_opt_entries",
+    "flsim_attack_opt_eval_host",
 ]
 COMM_ID_BYTES = 128      # FLSIM_COMM_ID_BYTES
 
@@ -173,6 +175,27 @@ class FlsimAttack(ctypes.Structure):
     _fields_ = [("kind", ctypes.c_int32), ("k", ctypes.c_int32), ("strength", ctypes.c_double),
                 ("entries", ctypes.c_void_p * MAX_ARRAYS), ("honest", ctypes.c_int32 * MAX_ARRAYS),
                 ("byz", ctypes.c_int32 * MAX_ARRAYS)]
+
+
+# FLSIM_ATTACK_MINMAX / _MINSUM, FLSIM_ATTACK_DIR_UNIT / _STD / _SIGN
+OPT_ATTACK_KINDS = {"minmax": 2, "minsum": 3}
+OPT_ATTACK_DIRS = {"unit": 0, "std": 1, "sign": 2}
+ATTACK_OPT_STATS = 2 * MAX_ARRAYS + 1      # FLSIM_ATTACK_OPT_STATS
+
+
+class FlsimAttackOpt(ctypes.Structure):
+    """flsim_attack_opt (include/flsim.h): Min-Max / Min-Sum over k bucket sums, their honest and
+    Byzantine worker counts."""
+    _fields_ = [("kind", ctypes.c_int32), ("dir", ctypes.c_int32), ("k", ctypes.c_int32),
+                ("strength", ctypes.c_double),
+                ("entries", ctypes.c_void_p * MAX_ARRAYS), ("honest", ctypes.c_int32 * MAX_ARRAYS),
+                ("byz", ctypes.c_int32 * MAX_ARRAYS)]
+
+
+class FlsimAttackOptScratch(ctypes.Structure):
+    """flsim_attack_opt_scratch (include/flsim.h): the caller's scratch and outputs of an attack."""
+    _fields_ = [("partials", ctypes.c_void_p), ("n_partials", ctypes.c_long),
+                ("dist", ctypes.c_void_p), ("stats", ctypes.c_void_p), ("gamma", ctypes.c_void_p)]
 
 
 class FlsimNnm(ctypes.Structure):
@@ -349,6 +372,12 @@ def lib():
     L.flsim_nnm_tile_elems.argtypes = [ctypes.c_int]
     L.flsim_nnm_entries.argtypes = [vp, vp, ctypes.c_long, vp]
     L.flsim_nnm_eval_host.argtypes = [vp, ctypes.c_long, vp, vp, vp]
+    L.flsim_attack_opt_partials.restype = ctypes.c_long
+    L.flsim_attack_opt_partials.argtypes = [ctypes.c_long, ctypes.c_int]
+    L.flsim_attack_opt_tile_elems.restype = ctypes.c_long
+    L.flsim_attack_opt_tile_elems.argtypes = [ctypes.c_int]
+    L.flsim_attack_opt_entries.argtypes = [vp, vp, vp, ctypes.c_long, vp]
+    L.flsim_attack_opt_eval_host.argtypes = [vp, vp, vp, vp, vp, ctypes.c_long]
     L.flsim_cascade_program.argtypes = [ctypes.c_int, vp, vp, ctypes.c_int, vp, ctypes.c_int, vp]
     L.flsim_cascade_eval_host.argtypes = [vp, vp, vp, vp, ctypes.c_int, vp, ctypes.c_long, vp]
     L.flsim_probe_enable.argtypes = [ctypes.c_int]

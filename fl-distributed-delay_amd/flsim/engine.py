@@ -20,7 +20,9 @@ import torch
 
 import math
 
-from ._lib import (ATTACK_KINDS, MAX_ARRAYS, OPT_KINDS, ROBUST_KINDS, FlsimAttack, FlsimBulyan,
+from ._lib import (ATTACK_KINDS, ATTACK_OPT_STATS, MAX_ARRAYS, OPT_ATTACK_DIRS, OPT_ATTACK_KINDS,
+                   OPT_KINDS, ROBUST_KINDS, FlsimAttack, FlsimAttackOpt, FlsimAttackOptScratch,
+                   FlsimBulyan,
                    FlsimBulyanScratch, FlsimCclip,
                    FlsimCclipScratch, FlsimClip, FlsimGeomed, FlsimGeomedScratch, FlsimKrum,
                    FlsimKrumScratch, FlsimNnm, FlsimNnmScratch, FlsimOptim,
@@ -499,8 +501,11 @@ class NetEngine:
     def attack_entries(self, attack, b_out=None):
         """Simulated Byzantine workers (an Attack over bucket sums) over this network's P
         parameters: the crafted vector is mixed into the entries in place; b_out as
-        attack_entries."""
-        attack_entries(attack, b_out, self.P)
+        attack_entries.  An OptAttack (Min-Max / Min-Sum) takes opt_attack_entries."""
+        if isinstance(attack, OptAttack):
+            opt_attack_entries(attack, b_out, self.P)
+        else:
+            attack_entries(attack, b_out, self.P)
 
     def nnm_entries(self, nnm):
         """Nearest-neighbour mixing (an NNM over bucket sums) over this network's P parameters:
@@ -1232,6 +1237,64 @@ def attack_entries(attack, b_out=None, P=None):
         P = int(next(e for e in attack.entries if e is not None).numel())
     a = attack.c_struct()
     check(lib().flsim_attack_entries(ctypes.byref(a), ptr(b_out), int(P), stream_ptr()))
+
+
+class OptAttack(Attack):
+    """The optimised attacks over bucket sums (flsim_attack_opt, include/flsim.h; Shejwalkar and
+    Houmansadr 2021): kind "minmax" or "minsum", every Byzantine worker sends mu + gamma * strength
+    * p with p the direction `dir` ("unit": -mu, "std": -sigma, "sign": -sign(mu)) and gamma solved
+    on the device from the honest entries.  entries, honest and byz as Attack.  The object owns
+    its scratch per (device, P, k), allocated at the first call and shared by the objects of a
+    run; after a call gamma ([1] fp64), stats_a and stats_c ([kh] fp64), stats_q ([1]) and dist
+    ([kh, kh] fp64, kh the entries with honest >= 1) are device tensors, read with no
+    synchronisation beyond the stream's order; the next call overwrites them.  flsim/robust.py
+    (opt_attack_flat) is the text."""
+    _scratch = {}       # (device, P, k) -> buffers
+    _scratch_struct, _partials = FlsimAttackOptScratch, "flsim_attack_opt_partials"
+
+    def __init__(self, kind, dir, strength, entries, honest, byz):
+        super().__init__(kind, strength, entries, honest, byz)
+        self.dir = dir
+        self.kh = sum(1 for h in self.honest if h >= 1)
+        self.dist = self.stats = self.gamma = None
+
+    def c_struct(self):
+        a = FlsimAttackOpt()
+        a.kind = OPT_ATTACK_KINDS.get(self.kind, -1)
+        a.dir = OPT_ATTACK_DIRS.get(self.dir, -1)
+        a.strength = self.strength
+        return self._fill_entries(a, honest=self.honest, byz=self.byz)
+
+    def _scratch_rows(self, k):
+        kh = max(self.kh, 1)
+        return (), (("dist", "dist", torch.float64, k * k + 2, (kh, kh)),
+                    ("stats", "stats", torch.float64, ATTACK_OPT_STATS + 1, (ATTACK_OPT_STATS,)),
+                    ("gamma", "gamma", torch.float64, 2, (1,)))
+
+    @property
+    def stats_a(self):
+        return self.stats[:self.kh]
+
+    @property
+    def stats_c(self):
+        return self.stats[MAX_ARRAYS:MAX_ARRAYS + self.kh]
+
+    @property
+    def stats_q(self):
+        return self.stats[2 * MAX_ARRAYS:]
+
+
+def opt_attack_entries(attack, b_out=None, P=None):
+    """Solve the OptAttack's gamma on the device and mix the crafted vector into its entries in
+    place, in four launches (flsim_attack_opt_entries); b_out (optional, [P] fp32) receives the
+    vector itself; attack.gamma, .stats and .dist then hold the solve."""
+    ref = next((e for e in attack.entries if e is not None), None)
+    if P is None:
+        P = int(ref.numel())
+    a = attack.c_struct()
+    s = attack.c_scratch(ref.device if ref is not None else "cpu", P)
+    check(lib().flsim_attack_opt_entries(ctypes.byref(a), ctypes.byref(s), ptr(b_out), int(P),
+                                         stream_ptr()))
 
 
 class NNM(_BucketRule):

@@ -756,16 +756,168 @@ def alie_z(n, f):
     return statistics.NormalDist().inv_cdf((n - s) / n)
 
 
+# ---- the optimised attacks Min-Max and Min-Sum (Shejwalkar and Houmansadr, NDSS 2021,
+# "Manipulating the Byzantine"): b = mu + gamma * p, gamma the largest coefficient at which b stays
+# no farther from any honest entry than the honest entries are from each other (Min-Max: the
+# largest squared distance; Min-Sum: the largest sum of squared distances).  The inputs, y_j, mu,
+# var and the mix are attack_vector's and attack_flat's.  The yardstick of flsim_attack_opt_entries
+# (include/flsim.h) and of its host twin: dist, a_i and q within 2 (P + 2) 2^-53 relative, c_i
+# within that times sqrt(a_i q) absolute, gamma bit for bit opt_gamma of the device's own a, c, q,
+# dist, b and the entries equal as numbers to the text evaluated with the device's gamma.
+OPT_ATTACK_KINDS = ("minmax", "minsum")
+OPT_ATTACK_DIRS = ("unit", "std", "sign")
+
+
+def _elemsum(v):
+    """The sum of a 1-d fp64 tensor as sequential adds in element order (a 1-d cumsum on the CPU
+    is that loop)."""
+    return torch.cumsum(v, 0)[-1]
+
+
+def opt_attack_parts(sums, honest, dirn):
+    """-> (y, mu, p): y_j and mu as attack_vector forms them; the perturbation direction p is
+    -mu ("unit": unnormalised, the solved gamma absorbs 1 / |mu|), -sqrt(var) ("std") or
+    -sign(mu) ("sign": sign(0) = 0, a NaN stays a NaN)."""
+    y = [sums[j].double() / honest[j] for j in range(len(sums)) if honest[j] >= 1]
+    kh = len(y)
+    mu = _seqsum(y) / kh
+    if dirn == "unit":
+        p = -mu
+    elif dirn == "std":
+        var = _seqsum([(t - mu) * (t - mu) for t in y]) / kh
+        p = -_sqrt_rn(var)
+    else:
+        one = torch.ones_like(mu)
+        p = torch.where(mu > 0, -one, torch.where(mu < 0, one, -mu))
+    return y, mu, p
+
+
+def opt_dist(sums, honest):
+    """The pairwise-distance stage's matrix (krum_select's d: fp64, NaN -> +inf; nnm_neighbours'
+    zero diagonal) over the fp32 means of the honest entries alone."""
+    hs = [j for j in range(len(sums)) if honest[j] >= 1]
+    cols = torch.stack(bucket_means([sums[j] for j in hs], [honest[j] for j in hs]))
+    return nnm_neighbours(cols, 0)[0]
+
+
+def opt_gamma(kind, a, c, q, dist):
+    """The largest gamma of the budget, in closed form, as scalar Python floats: a, c lists of kh
+    floats, q a float, dist kh lists of kh floats.  Every constraint |e_i + gamma p|^2 <= r is the
+    convex quadratic q gamma^2 + 2 c_i gamma + a_i <= r, which holds at gamma = 0."""
+    import math
+    kh = len(a)
+    if q == 0:
+        return 0.0
+
+    def root(c_, q_, r):
+        if r < 0:
+            r = 0.0
+        return (math.sqrt(c_ * c_ + q_ * r) - c_) / q_
+    if kind == "minmax":
+        D = dist[0][0]
+        for row in dist:
+            for v in row:
+                D = v if v > D else D
+        gs = [root(c[i], q, D - a[i]) for i in range(kh)]
+        if any(g != g for g in gs):
+            return float("nan")
+        gamma = gs[0]
+        for g in gs[1:]:
+            if g < gamma:
+                gamma = g
+        return gamma
+    S = A = C = None
+    for i in range(kh):
+        s = dist[i][0]
+        for v in dist[i][1:]:
+            s = s + v
+        S = s if S is None or s > S else S
+        A = a[i] if A is None else A + a[i]
+        C = c[i] if C is None else C + c[i]
+    return root(C, kh * q, S - A)
+
+
+def check_opt_attack(kind, dirn, strength, honest, byz):
+    """The cases the library refuses (ValueError), in its order.  Returns (kind, dir, strength)."""
+    if kind not in OPT_ATTACK_KINDS:
+        raise ValueError(f"Invalid attack kind {kind!r} (supported: {OPT_ATTACK_KINDS})")
+    if dirn not in OPT_ATTACK_DIRS:
+        raise ValueError(f"Invalid attack direction {dirn!r} (supported: {OPT_ATTACK_DIRS})")
+    return (kind, dirn, check_attack("ipm", strength, honest, byz)[1])
+
+
+def opt_attack_flat(sums, honest, byz, kind, dirn="std", strength=1.0, use_gamma=None):
+    """-> (entries, counts, b, gamma, a, c, q, dist): the entries and counts as attack_flat mixes
+    them, b = (mu + p * (gamma * strength)).float(); gamma a Python float; a, c fp64 [kh], q an
+    fp64 scalar, dist fp64 [kh, kh].  use_gamma (a float): b and the entries are evaluated with it
+    in place of the solved gamma, which is still what is returned -- the form in which the device's
+    b is checked, since its gamma is solved from its own sums."""
+    kind, dirn, strength = check_opt_attack(kind, dirn, strength, honest, byz)
+    y, mu, p = opt_attack_parts(sums, honest, dirn)
+    a = torch.stack([_elemsum((mu - t) * (mu - t)) for t in y])
+    c = torch.stack([_elemsum((mu - t) * p) for t in y])
+    q = _elemsum(p * p)
+    dist = opt_dist(sums, honest)
+    gamma = opt_gamma(kind, a.tolist(), c.tolist(), q.item(), dist.tolist())
+    entries, counts, b = _opt_mix(sums, honest, byz, mu, p, strength,
+                                  gamma if use_gamma is None else use_gamma)
+    return entries, counts, b, gamma, a, c, q, dist
+
+
+def opt_attack_mix(sums, honest, byz, dirn, strength, gamma):
+    """The crafted vector and the mix for a given gamma (a Python float) -> (entries, counts, b)."""
+    _, mu, p = opt_attack_parts(sums, honest, dirn)
+    return _opt_mix(sums, honest, byz, mu, p, strength, gamma)
+
+
+def _opt_mix(sums, honest, byz, mu, p, strength, gamma):
+    """One multiply for the scalar, a multiply and an add per element, one fp64 -> fp32 rounding,
+    then attack_flat's mix."""
+    coef = torch.tensor(float(gamma), dtype=torch.float64) * \
+        torch.tensor(float(strength), dtype=torch.float64)
+    b = (mu + p * coef).float()
+    entries = []
+    for j in range(len(sums)):
+        if byz[j] == 0:
+            entries.append(sums[j])
+            continue
+        t = b * torch.tensor(float(byz[j]), dtype=torch.float32)
+        entries.append(sums[j] + t if honest[j] >= 1 else t)
+    return entries, [int(h) + int(n) for h, n in zip(honest, byz)], b
+
+
+def _parse_opt_attack(spec):
+    import math
+    if len(spec) > 3:
+        raise ValueError(f"attack {spec!r} (supported: '{spec[0]}', ('{spec[0]}', dir), "
+                         f"('{spec[0]}', dir, strength))")
+    dirn = "std" if len(spec) < 2 or spec[1] is None else spec[1]
+    if dirn not in OPT_ATTACK_DIRS:
+        raise ValueError(f"attack {spec!r}: the direction must be one of {OPT_ATTACK_DIRS}")
+    if len(spec) < 3 or spec[2] is None:
+        return spec[0], dirn, 1.0
+    try:
+        strength = float(spec[2])
+    except (TypeError, ValueError):
+        raise ValueError(f"attack {spec!r}: the strength must be a number") from None
+    if not (math.isfinite(strength) and strength >= 0):
+        raise ValueError(f"attack {spec!r}: the strength must be finite and >= 0")
+    return spec[0], dirn, strength
+
+
 def parse_attack(spec):
     """FLSimulation's attack argument -> None or (kind, strength): None, "ipm" (eps = 1),
     ("ipm", eps), "alie" (strength None: alie_z of every epoch's fast-worker and Byzantine counts)
-    or ("alie", z)."""
+    or ("alie", z); or (kind, dir, strength) for "minmax" / "minsum", ("minmax", dir) and
+    ("minmax", dir, strength): dir one of OPT_ATTACK_DIRS (default "std"), strength default 1."""
     import math
     if spec is None or spec == "none":
         return None
     if isinstance(spec, str):
         spec = (spec,)
     spec = tuple(spec)
+    if spec and spec[0] in OPT_ATTACK_KINDS:
+        return _parse_opt_attack(spec)
     if not spec or spec[0] not in ATTACK_KINDS or len(spec) > 2:
         raise ValueError(f"attack {spec!r} (supported: None, 'ipm', ('ipm', eps), 'alie', "
                          "('alie', z))")

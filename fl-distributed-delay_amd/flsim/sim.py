@@ -40,6 +40,11 @@ omniscient attack on the epoch's fresh bucket entries (flsim/robust.py: attack_f
 robust_rule, ("trimmed_mean", 0) being the undefended mean over buckets).  They compute nothing:
 one launch mixes the crafted vector into the bucket sums before the robust step reads them.
 attack_log() returns every epoch's (kind, strength used, Byzantine workers present).
+attack may also be "minmax" or "minsum", ("minmax", dir) or ("minmax", dir, strength) with dir
+"unit", "std" (default) or "sign": the optimised attacks of Shejwalkar and Houmansadr 2021
+(flsim/robust.py: opt_attack_flat), whose coefficient gamma is solved on the device from the
+epoch's honest entries in four launches; strength (default 1) scales it.  attack_gamma_log()
+returns every attacked epoch's gamma as a device tensor.
 
 nnm (None or f >= 0; needs robust_rule) puts nearest-neighbour mixing (NNM, Allouah et al. 2023;
 flsim/robust.py: nnm_flat) in front of the robust rule: after the attack, every entry of the epoch
@@ -59,8 +64,8 @@ import torch
 from .data import DevicePool, make_test_pool
 from .engine import (PN1_SIZES, Clip, Optim, ProgramStager, Rule, engine_class, optim_defaults,
                      padded, split_views, staleness_weight)
-from .robust import (BULYAN_KIND, CCLIP_KIND, GEOMED_KIND, KRUM_KINDS, alie_z, check_bulyan,
-                     check_krum, check_nnm, parse_attack, parse_rule)
+from .robust import (BULYAN_KIND, CCLIP_KIND, GEOMED_KIND, KRUM_KINDS, OPT_ATTACK_KINDS, alie_z,
+                     check_bulyan, check_krum, check_nnm, parse_attack, parse_rule)
 from .schedule import Schedule, reference_delays
 
 SEMANTICS = ("reference", "torch1", "independent")
@@ -134,6 +139,9 @@ class FLSimulation:
         self.last_attack = None         # with keep_entries: (b, honest, byz) of the last attack
         self.last_honest = None         # ... and the fresh entries' honest sums before it
         self.attack_entries_log = []    # per epoch: (kind, strength used, Byzantine present)
+        # Min-Max / Min-Sum: (kind, dir, strength); gamma per attacked epoch, a cloned device tensor
+        self.attack_gamma_entries = []
+        self.last_attack_opt = None     # with keep_entries: (gamma, a, c, q, dist) of the last one
         if byz_placement not in ("spread", "block"):
             raise ValueError(f"byz_placement {byz_placement!r} (supported: 'spread', 'block')")
         if self.attack is not None and self.robust is None:
@@ -893,8 +901,8 @@ class FLSimulation:
         and the counts become honest + Byzantine.  An epoch whose fast set holds no Byzantine
         worker (throttling) runs none; one with no honest fast worker raises the library's
         ValueError."""
-        from .engine import Attack
-        kind, strength = self.attack
+        from .engine import Attack, OptAttack
+        kind, strength = self.attack[0], self.attack[-1]
         present = int(sum(byz))
         if present == 0:
             self.attack_entries_log.append((kind, None, 0))
@@ -906,8 +914,17 @@ class FLSimulation:
             b = torch.empty(self.P, device=self.device)
             self.last_honest = [e[:self.P].clone() if h else None
                                 for e, h in zip(entries, counts)]
-        self.engine.attack_entries(Attack(kind, strength, [e[:self.P] for e in entries],
-                                          counts, byz), b_out=b)
+        if kind in OPT_ATTACK_KINDS:            # Min-Max / Min-Sum: gamma is solved on the device
+            at = OptAttack(kind, self.attack[1], strength, [e[:self.P] for e in entries], counts,
+                           byz)
+            self.engine.attack_entries(at, b_out=b)
+            self.attack_gamma_entries.append(at.gamma.detach().clone())     # (no sync)
+            if self.keep_entries:
+                self.last_attack_opt = tuple(x.detach().clone() for x in (
+                    at.gamma, at.stats_a, at.stats_c, at.stats_q, at.dist))
+        else:
+            self.engine.attack_entries(Attack(kind, strength, [e[:self.P] for e in entries],
+                                              counts, byz), b_out=b)
         if self.keep_entries:
             self.last_attack = (b, list(counts), list(byz))
         for j, nb in enumerate(byz):
@@ -938,6 +955,11 @@ class FLSimulation:
         workers among the epoch's fast set) as Python values; (kind, None, 0) for an epoch whose
         fast set held no Byzantine worker.  Never synchronises."""
         return list(self.attack_entries_log)
+
+    def attack_gamma_log(self):
+        """Per attacked epoch of a run under "minmax" / "minsum" (else []) the solved gamma as a
+        cloned device tensor ([1] fp64).  Never synchronises."""
+        return list(self.attack_gamma_entries)
 
     def _log_norm(self):
         """Keep this epoch's norm: a clone of the device scalar, read back only by grad_norms()."""

@@ -33,6 +33,12 @@ Baruch et al. 2019; default X = the paper's z for the epoch's worker counts), mu
 coordinate-wise mean and standard deviation of the honest buckets' means.  --attack_strength is not
 --byz_f, which stays the count Krum tolerates.  'Attack' per epoch logs (kind, strength, Byzantine
 workers present).
+--attack {minmax,minsum} with --attack_dir {unit,std,sign} are the optimised attacks of Shejwalkar and
+Houmansadr 2021: each Byzantine worker sends mu + X * gamma * p, p = -mu, -sigma (default) or
+-sign(mu), with gamma solved on the GPU in every epoch as the largest coefficient that keeps the
+crafted vector no farther from any honest bucket than the honest buckets are from each other
+(minmax: the largest squared distance; minsum: the largest sum of squared distances); X defaults to
+1, the paper's attack.  'Attack' then logs (kind, direction, strength, Byzantine workers present).
 --nnm F (needs --robust_rule) mixes the entries before the rule (nearest-neighbour mixing, Allouah
 et al. 2023): after the attack, every entry is replaced by the mean of its k - F nearest entries,
 itself included, and the rule reads the mixed entries with count 1 each -- so --geomed_weights
@@ -147,16 +153,21 @@ def parse(argv=None):
     p.add_argument('--buckets', type=int, default=8, metavar='B',
                    help="--robust_rule: contiguous buckets the epoch's fast workers are averaged "
                         'in before the rule (default 8)')
-    p.add_argument('--attack', default='none', choices=['none', 'ipm', 'alie'],
-                   help='simulated Byzantine workers: inner-product manipulation (-X * mu) or "A '
-                        'Little Is Enough" (mu - X * sigma) mixed into the bucket entries (needs '
+    p.add_argument('--attack', default='none', choices=['none', 'ipm', 'alie', 'minmax', 'minsum'],
+                   help='simulated Byzantine workers: inner-product manipulation (-X * mu), "A '
+                        'Little Is Enough" (mu - X * sigma), or Min-Max / Min-Sum (mu + X * gamma '
+                        '* p, gamma solved per epoch) mixed into the bucket entries (needs '
                         '--robust_rule and --n_byz; default: none)')
+    p.add_argument('--attack_dir', default='std', choices=['unit', 'std', 'sign'],
+                   help='--attack minmax / minsum: the perturbation direction p = -mu, -sigma or '
+                        '-sign(mu) (default std)')
     p.add_argument('--n_byz', type=int, default=0, metavar='N',
                    help='--attack: how many of the fast (delay-0) workers are Byzantine, fewer '
                         'than all of them (default 0)')
     p.add_argument('--attack_strength', type=float, default=None, metavar='X',
-                   help="--attack: ipm's eps (default 1) or alie's z (default: the paper's z for "
-                        "the epoch's fast-worker and Byzantine counts); not --byz_f")
+                   help="--attack: ipm's eps (default 1), alie's z (default: the paper's z for "
+                        "the epoch's fast-worker and Byzantine counts) or the factor on minmax's "
+                        "/ minsum's gamma (default 1); not --byz_f")
     p.add_argument('--byz_placement', default='spread', choices=['spread', 'block'],
                    help='--attack: the Byzantine workers are spread evenly over the fast workers, '
                         'or are the first N of them, filling whole buckets (default spread)')
@@ -222,6 +233,9 @@ def attack_spec(args):
     """--attack / --attack_strength as FLSimulation's attack spec."""
     if args.attack == 'none':
         return None
+    if args.attack in ('minmax', 'minsum'):
+        return (args.attack, args.attack_dir) if args.attack_strength is None else \
+            (args.attack, args.attack_dir, args.attack_strength)
     return args.attack if args.attack_strength is None else (args.attack, args.attack_strength)
 
 
@@ -309,7 +323,10 @@ def main(argv=None):
         if args.robust_rule == 'bulyan':
             emit("Bulyan Selected", sim.selections()[-1], t)
         if args.attack != 'none':
-            emit("Attack", list(sim.attack_log()[-1]), t)
+            rec = list(sim.attack_log()[-1])
+            if args.attack in ('minmax', 'minsum'):
+                rec.insert(1, args.attack_dir)
+            emit("Attack", rec, t)
         if rank == 0 and (t % 10 == 0 or t == args.n_epochs - 1):
             print(f"epoch {t} Avg. Loss {loss:.5f}", flush=True)
         if args.save_model and t % 100 == 0 and t > 0 and rank == 0:   # main.py:192-194

@@ -916,6 +916,81 @@ int flsim_attack_entries(const flsim_attack* a, float* b_out /* nullable, [P] */
 int flsim_attack_eval_host(const flsim_attack* a, float* b_out, long P);
 
 /* ---------------------------------------------------------------------------------------------
+ * The optimised attacks Min-Max and Min-Sum (Shejwalkar and Houmansadr, NDSS 2021, "Manipulating
+ * the Byzantine"): every Byzantine worker sends b = mu + gamma * p, p a perturbation direction and
+ * gamma the largest coefficient at which b stays no farther (squared 2-norm over the whole model)
+ * from any honest entry than the honest entries are from each other (Min-Max: the largest
+ * distance; Min-Sum: the largest row sum of distances).  The inputs, the honest parts' means y_j
+ * and mu, the mix and the read / write contract are flsim_attack's.  The text (flsim/robust.py:
+ * opt_attack_flat, opt_gamma), with e_i = mu - y_i over the kh honest entries in index order:
+ *
+ *   p      = -mu ("unit": unnormalised, gamma absorbs 1 / |mu|), -_sqrt_rn(var) ("std": var as
+ *            ALIE's) or -sign(mu) ("sign": sign(0) = 0, a NaN stays)
+ *   a_i    = sum_e e_i * e_i,  c_i = sum_e e_i * p,  q = sum_e p * p     (fp64, element order)
+ *   dist   = the pairwise-distance stage's matrix (flsim_krum / flsim_nnm: NaN -> +inf, a zero
+ *            diagonal) over the fp32 means sums_j / honest_j of the honest entries alone
+ *   gamma  = 0 where q == 0; else
+ *     minmax: D = max dist, r_i = max(D - a_i, 0), gamma_i = (sqrt(c_i c_i + q r_i) - c_i) / q,
+ *             gamma = the smallest gamma_i (a NaN if any is one)
+ *     minsum: S = max_i sum_j dist[i][j], A = sum a_i, C = sum c_i, Q = kh q, r = max(S - A, 0),
+ *             gamma = (sqrt(C C + Q r) - C) / Q
+ *   b      = (float)(mu + p * (gamma * strength))
+ *
+ * the closed form of the paper's bisection (every constraint is a convex quadratic in gamma that
+ * holds at 0).  fp64, one rounding per operation, never an fma, IEEE division, correctly rounded
+ * sqrt.  Four launches on `stream`; no allocation, no host synchronisation, no atomics; the grids
+ * depend on (P, k) alone:
+ *   1. stats: one streaming pass over the honest entries; a thread forms y_j, mu, p and the
+ *      2 kh + 1 products of its elements and adds them in a fixed order; a block writes its sums
+ *      to s->partials.
+ *   2. distances: the launch of flsim_krum_optim_step over the honest entries (same kernel).
+ *   3. finish, one block: the distance matrix (Krum's order) -> s->dist; the stats partials in a
+ *      fixed order -> s->stats (a at [0, kh), c at [64, 64 + kh), q at [128]); gamma -> s->gamma,
+ *      and gamma * strength -> the last word of s->partials.
+ *   4. mix: flsim_attack's launch, which reads that word as a launch-uniform scalar.
+ * dist, a_i and q are within 2 (P + 2) 2^-53 relative of the text's, c_i within that times
+ * sqrt(a_i q) absolute; gamma is opt_gamma of the device's own a, c, q, dist bit for bit; b and
+ * the entries equal the text evaluated with the device's gamma "as numbers".  A NaN or an inf in
+ * an honest entry propagates as the text propagates it.
+ * Checked before any pointer, status 1: an unknown kind, then an unknown dir, then as flsim_attack.
+ * Then the entries, b_out and P as flsim_attack; a NULL or misaligned (16 bytes) scratch pointer;
+ * n_partials too small; an entry or b_out that overlaps the scratch; scratch buffers that overlap
+ * each other.
+ * ------------------------------------------------------------------------------------------- */
+#define FLSIM_ATTACK_MINMAX 2
+#define FLSIM_ATTACK_MINSUM 3
+#define FLSIM_ATTACK_DIR_UNIT 0
+#define FLSIM_ATTACK_DIR_STD 1
+#define FLSIM_ATTACK_DIR_SIGN 2
+#define FLSIM_ATTACK_OPT_STATS (2 * FLSIM_MAX_ARRAYS + 1)
+typedef struct flsim_attack_opt {
+    int32_t kind, dir, k;                 /* FLSIM_ATTACK_MINMAX / _MINSUM; FLSIM_ATTACK_DIR_* */
+    double  strength;                     /* scales gamma: 1 is the paper's attack; finite, >= 0 */
+    float*  entries[FLSIM_MAX_ARRAYS];    /* in/out bucket SUMS, updated in place */
+    int32_t honest[FLSIM_MAX_ARRAYS];     /* as flsim_attack */
+    int32_t byz[FLSIM_MAX_ARRAYS];
+} flsim_attack_opt;
+typedef struct flsim_attack_opt_scratch {  /* caller-provided, 16-byte aligned, never pre-initialised */
+    double* partials; long n_partials;     /* >= flsim_attack_opt_partials(P, k) */
+    double* dist;                          /* [k*k] out: the first kh*kh hold the kh x kh matrix */
+    double* stats;                         /* [FLSIM_ATTACK_OPT_STATS] out: a, c, q */
+    double* gamma;                         /* [1] out */
+} flsim_attack_opt_scratch;
+/* the doubles the stats and distance launches write, for any number of honest entries <= k
+ * (0: P or k out of range) */
+long flsim_attack_opt_partials(long P, int k);
+/* (tests) the STATS launch's tile over kh honest entries (0: out of range); the mix launch's is
+ * flsim_attack_tile_elems(k) */
+long flsim_attack_opt_tile_elems(int kh);
+int flsim_attack_opt_entries(const flsim_attack_opt* a, const flsim_attack_opt_scratch* s,
+                             float* b_out /* nullable, [P] */, long P, flsim_stream_t stream);
+/* host (testing): the same for host pointers by the same element and scalar code, the sums in
+ * element order; dist [kh*kh], stats [FLSIM_ATTACK_OPT_STATS], gamma [1]; refuses what the entry
+ * point refuses about a, the entries, b_out and P */
+int flsim_attack_opt_eval_host(const flsim_attack_opt* a, double* dist, double* stats,
+                               double* gamma, float* b_out, long P);
+
+/* ---------------------------------------------------------------------------------------------
  * Nearest-neighbour mixing (NNM; Allouah, Farhadkhani, Guerraoui, Gupta, Pinot and Stephan 2023,
  * "Fixing by Mixing"): a pre-aggregation stage in front of any robust rule.  Every entry is
  * replaced by the mean of its k - f nearest entries, itself included; the rule then reads the
