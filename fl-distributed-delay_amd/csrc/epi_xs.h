@@ -53,7 +53,13 @@ struct EpiBiasReluXs {
     __device__ float value(int, float v) const { return v; }
     __device__ void store_rows(const float* tile, int ld, int m0, int bm, int n0, int bn, int tid,
                                int nt) const {
-        const int rows = M - m0 < bm ? M - m0 : bm;
+        store_rows_by(tile, ld, [m0](int r) { return m0 + r; }, M - m0 < bm ? M - m0 : bm, n0, bn,
+                      tid, nt);
+    }
+    // the tile's first `rows` rows, tile row r being output row rowof(r) (gemm_core.h EpiClassRows)
+    template <class ROWOF>
+    __device__ void store_rows_by(const float* tile, int ld, ROWOF rowof, int rows, int n0, int bn,
+                                  int tid, int nt) const {
         const int n4 = bn / 4;
         for (int q = tid; q < rows * n4; q += nt) {
             const int r = q / n4, c = q - r * n4;
@@ -61,7 +67,7 @@ struct EpiBiasReluXs {
             const f32x4 b = *reinterpret_cast<const f32x4*>(bias + n0 + 4 * c);
             const f32x4 v = {fmaxf(t.x + b.x, 0.f), fmaxf(t.y + b.y, 0.f), fmaxf(t.z + b.z, 0.f),
                              fmaxf(t.w + b.w, 0.f)};
-            xs_store_f(Yhm, Yl, Yf, xs_unit<NC, HW, SM>((unsigned)(m0 + r), n0 / 4 + c), v);
+            xs_store_f(Yhm, Yl, Yf, xs_unit<NC, HW, SM>((unsigned)rowof(r), n0 / 4 + c), v);
         }
     }
 };
@@ -232,7 +238,13 @@ struct EpiPoolDropXs {
     float* df = nullptr;   // fp32 copy of d, same layout (split.h xs_store_f), or none
     __device__ float value(int, float v) const { return v; }
     __device__ void store_rows(const float* tile, int ld, int m0, int bm, int tid, int nt) const {
-        const int rows = M - m0 < bm ? M - m0 : bm;
+        store_rows_by(tile, ld, [m0](int r) { return m0 + r; }, M - m0 < bm ? M - m0 : bm, tid, nt);
+    }
+    // the tile's first `rows` rows, tile row r being window-order row rowof(r): a window's four
+    // rows stay together and in order (gemm_core.h EpiClassRows)
+    template <class ROWOF>
+    __device__ void store_rows_by(const float* tile, int ld, ROWOF rowof, int rows, int tid,
+                                  int nt) const {
         constexpr int C4 = C / 4;
         const int total = rows / 4 * C4;
         for (int u = tid; u < total; u += nt) {
@@ -245,7 +257,7 @@ struct EpiPoolDropXs {
                 x[r] = f32x4{fmaxf(t.x + b.x, 0.f), fmaxf(t.y + b.y, 0.f), fmaxf(t.z + b.z, 0.f),
                              fmaxf(t.w + b.w, 0.f)};
             }
-            const int q = (m0 >> 2) + pl;                 // pooled pixel (s, ph, pw)
+            const int q = rowof(4 * pl) >> 2;             // pooled pixel (s, ph, pw)
             const int pw = q % PW;
             const int ph = (q / PW) % PH;
             const int s = q / (PW * PH);

@@ -18,10 +18,11 @@
 #include <type_traits>
 
 #include "common.h"
+#include "rowmap.h"
 
 namespace flsim {
 
-constexpr int GK = 16;  // K depth per LDS stage
+constexpr int GK = 16; // K depth per LDS stage
 
 __device__ __forceinline__ int kc_swz(int row) { return (4 - ((row >> 2) & 3)) & 3; }
 
@@ -124,6 +125,33 @@ __device__ __forceinline__ void staged_store(const EPI& epi, const float* tile, 
     else
         epi.store_rows(tile, ld, m0, bm, tid, nt);
 }
+
+// An epilogue wrapped in EpiClassRows makes its GEMM run in tap-class row order (rowmap.h): the
+// kernels that know the order (gemm_dx6_kernel, gemm_x6_kernel) take the block's tile, its k
+// sequence and its rows' canonical numbers from rm, and a staged epilogue is asked for
+// store_rows_by(tile, ld, rowof, rows, ...), rowof(r) the canonical row of tile row r, instead
+// of store_rows(tile, ld, m0, bm, ...).  The grid is rm.tiles blocks.
+template <class E, class = void>
+struct HasRowClasses : std::false_type {};
+template <class E>
+struct HasRowClasses<E, std::void_t<decltype(E::ROW_CLASSES)>> : std::bool_constant<E::ROW_CLASSES> {};
+
+template <class E>
+struct EpiClassRows : E {
+    static constexpr bool ROW_CLASSES = true;
+    RowClasses rm;
+    // rowm: the canonical rows of the bm tile rows passed, of which the first `valid` are real
+    // (valid may be <= 0 or > bm: the rows the class has left at this point of the tile)
+    __device__ void store_class_rows(const float* tile, int ld, const int* rowm, int valid, int bm,
+                                     int n0, int bn, int tid, int nt) const {
+        const int rows = valid < bm ? (valid > 0 ? valid : 0) : bm;
+        auto rowof = [rowm](int r) { return rowm[r]; };
+        if constexpr (IsPartial<E>::value)
+            E::store_rows_by(tile, ld, rowof, rows, n0, bn, tid, nt);
+        else
+            E::store_rows_by(tile, ld, rowof, rows, tid, nt);
+    }
+};
 
 // Epilogues with PRE = true load the per-fragment inputs of a fragment row first
 // (pre4(m, n, z) -> f32x4), then store its fragments (apply4p(m, n, z, acc, pre))

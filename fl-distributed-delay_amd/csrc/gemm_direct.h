@@ -49,11 +49,17 @@ struct Im2colDirect {
 
     // r0: the wave's first row; fragment f covers rows r0 + 16 f + (lane & 15)
     __device__ void setup(int r0, int lane) {
+        setup_by(lane, [&](int f) { return r0 + 16 * f + (lane & 15); });
+    }
+    // the row map as a policy: rowof(f) is the canonical row of this lane's row of fragment f
+    // (the identity above; a tap-class order's table, rowmap.h; any row >= M is a pad row)
+    template <class ROWOF>
+    __device__ void setup_by(int lane, ROWOF&& rowof) {
         const int q = lane >> 4;
         buf.init(X, XL, (unsigned long)((M + ROWS_PER_IMG - 1) / ROWS_PER_IMG) * IH * IW * CI * 4);
 #pragma unroll
         for (int f = 0; f < FM; ++f) {
-            const int m = r0 + 16 * f + (lane & 15);
+            const int m = rowof(f);
             long base = 0;
             int msk = 0;
             if (m < M) {

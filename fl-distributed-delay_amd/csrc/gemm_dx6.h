@@ -16,6 +16,7 @@
 #pragma once
 #include "gemm_direct.h"
 #include "gemm_x6.h"
+#include "rowmap.h"
 
 namespace flsim {
 
@@ -109,10 +110,30 @@ gemm_dx6_kernel(AD ad, BL bl, EPI epi, int ksteps, int tiles_m, int tiles_n) {
     const int tn = L % tiles_n;
     const int tm = L / tiles_n;
     const int m0 = tm * BM;
-    const int n0 = tn * BN;
+    // tap-class row order (rowmap.h): the block's tile, its rows' canonical numbers in LDS, and
+    // the class's k sequence, one cursor for the A loads and one for the B loads
+    constexpr bool CLS = HasRowClasses<EPI>::value;
+    __shared__ int rowm[CLS ? BM : 1];
+    RowTile rt{};
+    RowKSeq ka{}, kb{};
+    if constexpr (CLS) {
+        rt = epi.rm.locate(b);
+        for (int rr = tid; rr < BM; rr += 64 * WAVES) rowm[rr] = epi.rm.row(rt.cls, rt.v0 + rr);
+        ka.init(epi.rm.c[rt.cls], ksteps / 9);
+        kb = ka;
+        ksteps = epi.rm.ksteps(rt.cls, ksteps / 9);
+        __syncthreads();
+    }
+    const int n0 = CLS ? 0 : tn * BN;
 
-    ad.setup(m0 + wave * WROWS, lane);
+    if constexpr (CLS)
+        ad.setup_by(lane, [&](int f) { return rowm[wave * WROWS + 16 * f + (lane & 15)]; });
+    else
+        ad.setup(m0 + wave * WROWS, lane);
     bl.setup(n0, tid);
+    // the k-step of the next A / B load: k (canonical order) or the class's next one
+    auto a_ks = [&](int k) { if constexpr (CLS) return ka.next(); else return k; };
+    auto b_ks = [&](int k) { if constexpr (CLS) return kb.next(); else return k; };
 
     f32x4 acc[FM][FN];
 #pragma unroll
@@ -127,10 +148,10 @@ gemm_dx6_kernel(AD ad, BL bl, EPI epi, int ksteps, int tiles_m, int tiles_n) {
     typename BL::Unit rb[BL::UNITS];
     const int nst = ksteps / KB;
 #pragma unroll
-    for (int d = 0; d < DEPTH; ++d) ad.load(d, ra[d]);
+    for (int d = 0; d < DEPTH; ++d) ad.load(a_ks(d), ra[d]);
 #pragma unroll
     for (int kk = 0; kk < KB; ++kk) {
-        bl.load(kk, rb);
+        bl.load(b_ks(kk), rb);
         bl.store(lds + kk * BFL, rb);
     }
     __syncthreads();
@@ -145,8 +166,8 @@ gemm_dx6_kernel(AD ad, BL bl, EPI epi, int ksteps, int tiles_m, int tiles_n) {
         for (int kk = 0; kk < KB; ++kk) {
             const int ks = s * KB + kk;
             if (kk > 0) bl.store(Bn + (kk - 1) * BFL, rb);
-            bl.load(kn + kk, rb);
-            ad.load(ks + DEPTH, ra[(kk + DEPTH) % R]);
+            bl.load(b_ks(kn + kk), rb);
+            ad.load(a_ks(ks + DEPTH), ra[(kk + DEPTH) % R]);
             if constexpr (DX6_FENCES) __builtin_amdgcn_sched_barrier(0);
             const float* Bk = Bs + kk * BFL;
             f32x4 a0[FM], a1[FM];
@@ -196,15 +217,21 @@ gemm_dx6_kernel(AD ad, BL bl, EPI epi, int ksteps, int tiles_m, int tiles_n) {
             }
             __syncthreads();
             const int w_hi = (pass + 1) * WM_PASS < WAVES ? (pass + 1) * WM_PASS : WAVES;
-            staged_store(epi, lds, STAGE_LD, m0 + pass * WM_PASS * WROWS,
-                         (w_hi - pass * WM_PASS) * WROWS, n0, BN, tid, 64 * WAVES);
+            if constexpr (CLS)
+                epi.store_class_rows(lds, STAGE_LD, rowm + pass * WM_PASS * WROWS,
+                                     rt.valid - pass * WM_PASS * WROWS,
+                                     (w_hi - pass * WM_PASS) * WROWS, n0, BN, tid, 64 * WAVES);
+            else
+                staged_store(epi, lds, STAGE_LD, m0 + pass * WM_PASS * WROWS,
+                             (w_hi - pass * WM_PASS) * WROWS, n0, BN, tid, 64 * WAVES);
         }
     } else {
 #pragma unroll
         for (int i = 0; i < FM; ++i)
 #pragma unroll
             for (int j = 0; j < FN; ++j) {
-                const int m = m0 + wave * WROWS + 16 * i + 4 * (lane >> 4);
+                const int ml = wave * WROWS + 16 * i + 4 * (lane >> 4);
+                const int m = CLS ? rowm[ml] : m0 + ml;       // a window's 4 rows stay together
                 const int n = n0 + 16 * j + (lane & 15);
                 epi.apply4(m, n, 0, acc[i][j]);
             }

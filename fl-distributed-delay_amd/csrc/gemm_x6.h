@@ -279,11 +279,38 @@ gemm_x6_kernel(AL al, BL bl, EPI epi, int ksteps_total, int ksteps_per_split, in
     const int tz = L / (gx * gy);
     const int m0 = tm * BM;
     const int n0 = tn * BN;
-    const int ks0 = tz * ksteps_per_split;
+    int ks0 = tz * ksteps_per_split;
     int ks1 = ks0 + ksteps_per_split;
     if (ks1 > ksteps_total) ks1 = ksteps_total;
-
-    al.setup(m0, tid);
+    // tap-class row order (rowmap.h; one n-tile, no K split): the block's tile, its rows'
+    // canonical numbers in LDS, and the class's k sequence: ks counts the class's steps and kq
+    // gives the real k-step of each load.  The row numbers take the last BM words of the
+    // pipeline's own LDS (an array of their own would cost the 128-row tiles their second block
+    // per CU): filled here for the loader's setup, overwritten by the pipeline, and filled again
+    // for the epilogue, past the staged tile.
+    constexpr bool CLS = HasRowClasses<EPI>::value;
+    static_assert(!CLS || !STAGED || WM_PASS * WROWS * STAGE_LD + BM <= LDS_FL, "row numbers");
+    int* const rowm = reinterpret_cast<int*>(lds + LDS_FL - BM);
+    RowTile rt{};
+    RowKSeq kq{};
+    auto fill_rowm = [&]() {
+        if constexpr (CLS) {
+            for (int rr = tid; rr < BM; rr += 64 * WAVES_M * WAVES_N)
+                rowm[rr] = epi.rm.row(rt.cls, rt.v0 + rr);
+            __syncthreads();
+        }
+    };
+    if constexpr (CLS) {
+        rt = epi.rm.locate(b);
+        kq.init(epi.rm.c[rt.cls], ksteps_total / 9);
+        ks0 = 0;
+        ks1 = epi.rm.ksteps(rt.cls, ksteps_total / 9);
+        fill_rowm();
+        al.setup_by(tid, [&](int rr) { return rowm[rr]; });
+        __syncthreads();
+    } else {
+        al.setup(m0, tid);
+    }
     bl.setup(n0, tid);
 
     f32x4 acc[FM][FN];
@@ -306,14 +333,16 @@ gemm_x6_kernel(AL al, BL bl, EPI epi, int ksteps_total, int ksteps_per_split, in
         });
     };
 
+    // loads of k-step k (canonical order), or of the class's next k-step
+    auto load_ab = [&](int k) {
+        if constexpr (CLS) k = kq.next();
+        al.load(k, ra);
+        bl.load(k, rb);
+    };
     if (ks0 < ks1) {
-        al.load(ks0, ra);
-        bl.load(ks0, rb);
+        load_ab(ks0);
         stage(lds);
-        if (ks0 + 1 < ks1) {
-            al.load(ks0 + 1, ra);
-            bl.load(ks0 + 1, rb);
-        }
+        if (ks0 + 1 < ks1) load_ab(ks0 + 1);
     }
     __syncthreads();
     if constexpr (WAVES_M * WAVES_N == 8) {
@@ -353,15 +382,10 @@ gemm_x6_kernel(AL al, BL bl, EPI epi, int ksteps_total, int ksteps_per_split, in
                 // MFMAs, below): the last k-step stages into the buffer nobody reads again, and
                 // the loads past the split re-read its last k-step
                 stage(lds + (cur ^ 1) * BUF);
-                const int kl = ks + 2 < ks1 ? ks + 2 : ks1 - 1;
-                al.load(kl, ra);
-                bl.load(kl, rb);
+                load_ab(ks + 2 < ks1 ? ks + 2 : ks1 - 1);
             } else if (ks + 1 < ks1) {
                 stage(lds + (cur ^ 1) * BUF);
-                if (ks + 2 < ks1) {
-                    al.load(ks + 2, ra);
-                    bl.load(ks + 2, rb);
-                }
+                if (ks + 2 < ks1) load_ab(ks + 2);
             }
             const float* A = lds + cur * BUF;
             const float* B = A + TA::FL;
@@ -441,6 +465,7 @@ gemm_x6_kernel(AL al, BL bl, EPI epi, int ksteps_total, int ksteps_per_split, in
         }
     }
 
+    if constexpr (CLS) fill_rowm();     // the loop's last barrier is behind every wave
     if constexpr (AMF) {
         // every column of the ones product is the row sum: lanes of column 0 store it
         if (bwave && (lane & 15) == 0) {
@@ -474,8 +499,15 @@ gemm_x6_kernel(AL al, BL bl, EPI epi, int ksteps_total, int ksteps_per_split, in
             }
             __syncthreads();
             const int wm_hi = (pass + 1) * WM_PASS < WAVES_M ? (pass + 1) * WM_PASS : WAVES_M;
-            staged_store(epi, lds, STAGE_LD, m0 + pass * WM_PASS * WROWS,
-                         (wm_hi - pass * WM_PASS) * WROWS, n0, BN, tid, 64 * WAVES_M * WAVES_N);
+            if constexpr (CLS)
+                epi.store_class_rows(lds, STAGE_LD, rowm + pass * WM_PASS * WROWS,
+                                     rt.valid - pass * WM_PASS * WROWS,
+                                     (wm_hi - pass * WM_PASS) * WROWS, n0, BN, tid,
+                                     64 * WAVES_M * WAVES_N);
+            else
+                staged_store(epi, lds, STAGE_LD, m0 + pass * WM_PASS * WROWS,
+                             (wm_hi - pass * WM_PASS) * WROWS, n0, BN, tid,
+                             64 * WAVES_M * WAVES_N);
         }
     } else if constexpr (HasPre<EPI>::value) {
 #pragma unroll
@@ -493,9 +525,10 @@ gemm_x6_kernel(AL al, BL bl, EPI epi, int ksteps_total, int ksteps_per_split, in
         for (int i = 0; i < FM; ++i)
 #pragma unroll
             for (int j = 0; j < FN; ++j) {
-                const int m = m0 + wm * 16 * FM + 16 * i + 4 * (lane >> 4);
+                const int ml = wm * 16 * FM + 16 * i + 4 * (lane >> 4);
+                const int m = CLS ? rowm[ml] : m0 + ml;       // a window's 4 rows stay together
                 const int n = n0 + wn * 16 * FN + 16 * j + (lane & 15);
-                epi.apply4(m, n, tz, acc[i][j]);
+                epi.apply4(m, n, CLS ? 0 : tz, acc[i][j]);
             }
     }
 }

@@ -172,6 +172,12 @@ struct Im2colKC {
     static_assert(FLSIM_BUFLOAD || !SRC::SPLIT, "split operands use buffer loads");
 
     __device__ void setup(int m0, int tid) {
+        setup_by(tid, [&](int r) { return m0 + r; });
+    }
+    // the row map as a policy: rowof(r) is the canonical row of tile row r < ROWS (the identity
+    // above; a tap-class order's table, rowmap.h; any row >= M is a pad row)
+    template <class ROWOF>
+    __device__ void setup_by(int tid, ROWOF&& rowof) {
         q = tid & 3;
         if constexpr (FLSIM_BUFLOAD)
             buf.init(X, XL, (unsigned long)((M + ROWS_PER_IMG - 1) / ROWS_PER_IMG) * IH * IW * CI * 4);
@@ -180,7 +186,7 @@ struct Im2colKC {
             const int u = tid + j * NT;
             const int r = u >> 2;
             row[j] = (short)r;
-            const int m = m0 + r;
+            const int m = u < TOTAL ? rowof(r) : M;
             base[j] = 0;
             tapmask[j] = 0;
             if (u < TOTAL && m < M) {

@@ -995,8 +995,11 @@ static int conv_wgrad_sz(const float* dz, const float* X, int S, int CO, int KP,
 // weights W [N][KP] on the direct-A kernel (gemm_dx6.h): WAVES waves of 16*FM rows, 16*FN columns
 // per n-tile, B staged KB k-steps a time (NPL planes), A loaded DEPTH k-steps ahead
 // (ASRC = XsSrcSM: X channel-slice-major, loaders.h)
+// CLS: rows in tap-class order (rowmap.h), each block running only its class's taps: a forward
+// with zero padding, one n-tile; bit-identical to the canonical order (the k-steps left out add
+// exact zeros and the others keep their order).  The probe gets the executed FLOPs.
 template <int IH, int IW, int CI, int PAD, int FM, int FN, int WAVES, int KB, int DEPTH, int NPL,
-          bool WIN, int OHX, class ASRC = XsSrc, class EPI>
+          bool WIN, int OHX, class ASRC = XsSrc, bool CLS = false, class EPI>
 static int conv_dx6(XsT X, int S, XsT W, int N, int KP, const EPI& epi, hipStream_t st, int kid,
                     int kreal) {
     static_assert(ASRC::SPLIT, "split input");
@@ -1014,6 +1017,21 @@ static int conv_dx6(XsT X, int S, XsT W, int N, int KP, const EPI& epi, hipStrea
     bl.ld = KP;
     bl.NR = N;
     const int tm = ceil_div(ad.M, BM), tn = ceil_div(N, BN);
+    if constexpr (CLS) {
+        static_assert(OHX == 0 && CI % 48 == 0 && KB == 3,
+                      "tap classes: every class's k-steps a multiple of KB");
+        FLSIM_REQUIRE(tn == 1 && KP == 9 * CI, "tap classes: N %d, KP %d", N, KP);
+        EpiClassRows<EPI> ce;
+        static_cast<EPI&>(ce) = epi;
+        FLSIM_REQUIRE(row_classes_build(ce.rm, IH, IW, PAD, WIN, S, BM), "tap classes: %d x %d",
+                      IH, IW);
+        const ProbeSlot ps = probe_begin();
+        hipExtLaunchKernelGGL((gemm_dx6_kernel<FM, FN, WAVES, KB, DEPTH, AD, BL, EpiClassRows<EPI>>),
+                              dim3(ce.rm.tiles), dim3(64 * WAVES), 0, st, ps.start, ps.stop, 0, ad,
+                              bl, ce, KP / GK, tm, tn);
+        FLSIM_LAUNCH_CHECK();
+        return probe_end(ps, kid, 2.0 * row_classes_row_taps(ce.rm) * CI * N);
+    }
     const ProbeSlot ps = probe_begin();
     hipExtLaunchKernelGGL((gemm_dx6_kernel<FM, FN, WAVES, KB, DEPTH, AD, BL, EPI>),
                           dim3(tm * tn), dim3(64 * WAVES), 0, st, ps.start, ps.stop, 0, ad, bl,
@@ -1024,8 +1042,9 @@ static int conv_dx6(XsT X, int S, XsT W, int N, int KP, const EPI& epi, hipStrea
 
 // the same GEMM on gemm_x6_kernel with both operands staged through LDS (bit-identical to
 // conv_dx6: same split, same MFMA order per output): the tiles for small chunks
+// (CLS: rows in tap-class order, as conv_dx6)
 template <int IH, int IW, int CI, int PAD, int FM, int FN, int WM, int WN, bool WIN, int OHX,
-          class EPI>
+          bool CLS = false, class EPI>
 static int conv_xs(XsT X, int S, XsT W, int N, int KP, const EPI& epi, hipStream_t st, int kid,
                    int kreal) {
     constexpr int NT = 64 * WM * WN;
@@ -1041,6 +1060,20 @@ static int conv_xs(XsT X, int S, XsT W, int N, int KP, const EPI& epi, hipStream
     bl.PL = W.l;
     bl.ld = KP;
     bl.NR = N;
+    if constexpr (CLS) {
+        static_assert(OHX == 0 && CI % 16 == 0, "tap classes: a forward over whole slices");
+        FLSIM_REQUIRE(N <= BN && KP == 9 * CI, "tap classes: N %d, KP %d", N, KP);
+        EpiClassRows<EPI> ce;
+        static_cast<EPI&>(ce) = epi;
+        FLSIM_REQUIRE(row_classes_build(ce.rm, IH, IW, PAD, WIN, S, BM), "tap classes: %d x %d",
+                      IH, IW);
+        const ProbeSlot ps = probe_begin();
+        hipExtLaunchKernelGGL((gemm_x6_kernel<FM, FN, WM, WN, AL, BL, EpiClassRows<EPI>>),
+                              dim3(ce.rm.tiles), dim3(NT), 0, st, ps.start, ps.stop, 0, al, bl, ce,
+                              KP / GK, KP / GK, ceil_div(al.M, BM), 1);
+        FLSIM_LAUNCH_CHECK();
+        return probe_end(ps, kid, 2.0 * row_classes_row_taps(ce.rm) * CI * N);
+    }
     return launch_gemm<FM, FN, WM, WN, true>(al, bl, epi, al.M, N, KP / GK, 1, st, kid,
                                              2.0 * al.M * N * kreal);
 }

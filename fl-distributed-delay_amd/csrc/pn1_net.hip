@@ -341,11 +341,55 @@ constexpr int DX_FM = FLSIM_DX_FM, DX_FMS = 1, DX_KB = 3, DX_DEPTH = 2, DX_NPL =
 // and 8 % slower on the facade loop, 748 / 746 against 814 / 804 worker-steps/s, E A E A on one box,
 // profiles/r06/facade/facade_tiny_ab: more blocks each staging the same B panel.  Not kept.)
 
-template <int IH, int IW, int CI, int PAD, int FN, bool WIN, int OHX, int FM = DX_FM,
+// The conv2-6 forwards in tap-class row order (rowmap.h; DESIGN 8b "forward tap classes"): every
+// convolution is 3x3 with padding 2, so the outputs near the border see one or two taps per
+// dimension inside the input; rows grouped by tap class let a block skip the all-padding k-steps
+// as a block.  Per layer, 1: class order, 0: canonical order (both give the same bits).
+// Measured per 16,384-sample launch, canonical against class order, two runs each on one box
+// (profiles/fwd_classes): conv4 6.02 / 6.10 -> 5.55 / 5.58 ms, conv5 4.30 / 4.33 -> 3.62 / 3.63,
+// conv6 8.64 / 8.72 -> 8.30 / 8.34.  conv2 and conv3 stay canonical: in class order they ran
+// 6.02 / 6.05 -> 6.28 / 6.29 and 3.03 / 3.04 -> 3.38 / 3.38 ms with 0.927 and 0.810 of the
+// k-steps.  Their K is short (27 k-steps) and their traffic large for it (conv2 reads 5.4 GB of
+// a1, conv3 writes 3.8 GB of a3); in class order an image's border outputs run in other blocks,
+// much later, than its interior, which re-reads its input (supposed cause, not measured).
+#ifndef FLSIM_FWC2
+#define FLSIM_FWC2 0
+#endif
+#ifndef FLSIM_FWC3
+#define FLSIM_FWC3 0
+#endif
+#ifndef FLSIM_FWC4
+#define FLSIM_FWC4 1
+#endif
+#ifndef FLSIM_FWC5
+#define FLSIM_FWC5 1
+#endif
+#ifndef FLSIM_FWC6
+#define FLSIM_FWC6 1
+#endif
+
+// debug: FLSIM_DEBUG_FWD_ROWS=canonical runs every forward in canonical row order, so that a test
+// can compare the two orders in one process (tests/test_gpu_fwd_classes.py).  Read per call, as
+// FLSIM_DEBUG_BWD_STOP is; not a tuning knob.
+static bool fwd_rows_canonical() {
+    const char* e = getenv("FLSIM_DEBUG_FWD_ROWS");
+    return e && !strcmp(e, "canonical");
+}
+
+template <bool CLS, int IH, int IW, int CI, int PAD, int FN, bool WIN, int OHX, int FM = DX_FM,
           int WAVES = 8, int FMS = (FM == DX_FM ? DX_FMS : FM / 2), class EPI>
 static int dx6(XsT X, int S, XsT W, int N, int KP, const EPI& epi, hipStream_t st, int kid,
                int kreal) {
     // the inputs of conv2-4 (a1, d1, a3) are channel-slice-major (XsSrcSM)
+    if constexpr (CLS) {
+        if (!fwd_rows_canonical()) {
+            if (S <= small_chunk_samples())
+                return conv_dx6<IH, IW, CI, PAD, FMS, FN, WAVES, DX_KB, DX_DEPTH, DX_NPL, WIN, OHX,
+                                XsSrcSM, true>(X, S, W, N, KP, epi, st, kid, kreal);
+            return conv_dx6<IH, IW, CI, PAD, FM, FN, WAVES, DX_KB, DX_DEPTH, DX_NPL, WIN, OHX,
+                            XsSrcSM, true>(X, S, W, N, KP, epi, st, kid, kreal);
+        }
+    }
     if (S <= small_chunk_samples())
         return conv_dx6<IH, IW, CI, PAD, FMS, FN, WAVES, DX_KB, DX_DEPTH, DX_NPL, WIN, OHX,
                         XsSrcSM>(X, S, W, N, KP, epi, st, kid, kreal);
@@ -358,10 +402,19 @@ static int dx6(XsT X, int S, XsT W, int N, int KP, const EPI& epi, hipStream_t s
 // (N = 192: conv5/6 forward, conv6 data gradient; N = 96 data gradients of conv4/5) run faster
 // this way (profiles/r04/lab/lab_xs_r04b.txt: conv6 data gradient 8.8 vs 10.7 ms, forward
 // 11.1 vs 12.0)
-template <int IH, int IW, int CI, int PAD, int FM, int FN, int WM, int WN, bool WIN, int OHX,
-          class EPI>
+template <bool CLS, int IH, int IW, int CI, int PAD, int FM, int FN, int WM, int WN, bool WIN,
+          int OHX, class EPI>
 static int xs(XsT X, int S, XsT W, int N, int KP, const EPI& epi, hipStream_t st, int kid,
               int kreal) {
+    if constexpr (CLS) {
+        if (!fwd_rows_canonical()) {
+            if (S <= small_chunk_samples())
+                return conv_xs<IH, IW, CI, PAD, FM / 2, FN, WM, WN, WIN, OHX, true>(
+                    X, S, W, N, KP, epi, st, kid, kreal);
+            return conv_xs<IH, IW, CI, PAD, FM, FN, WM, WN, WIN, OHX, true>(X, S, W, N, KP, epi, st,
+                                                                            kid, kreal);
+        }
+    }
     if (S <= small_chunk_samples())
         return conv_xs<IH, IW, CI, PAD, FM / 2, FN, WM, WN, WIN, OHX>(X, S, W, N, KP, epi, st, kid,
                                                                      kreal);
@@ -375,26 +428,26 @@ static int forward(const GradState& g, const WS& w, const float* theta, int S,
     // conv1 + ReLU (models.py:29), a1 written split
     RC(conv1_fwd(w.x0, theta + P_OFF[0], theta + P_OFF[1], a1, w.a1f, S, st));
     // conv2 + ReLU + pool1 + dropout1 (models.py:30-32), one fused launch -> d1 (split)
-    RC((dx6<34, 34, 48, 2, 3, true, 0, 4, 4, 2>(a1, S, g.wfx[1], 48, 432,
+    RC((dx6<FLSIM_FWC2, 34, 34, 48, 2, 3, true, 0, 4, 4, 2>(a1, S, g.wfx[1], 48, 432,
         EpiPoolDropXs<18, 18, 48, true>{d1.hm, d1.l, w.i1, theta + P_OFF[3], workers, seed, SITE_DROP1,
                                   THR_P25, SCALE_P25, dropout, S * 18 * 18 * 4, w.d1f}, st,
         K_FWD2, 432)));
     // conv3 + ReLU (models.py:33) -> a3 (split)
-    RC((dx6<18, 18, 48, 2, 6, false, 0>(d1, S, g.wfx[2], 96, 432,
+    RC((dx6<FLSIM_FWC3, 18, 18, 48, 2, 6, false, 0>(d1, S, g.wfx[2], 96, 432,
         EpiBiasReluXs<96, true, 400>{a3.hm, a3.l, theta + P_OFF[5], S * 20 * 20, w.a3f}, st, K_FWD3,
         432)));
     // conv4 + ReLU + pool2 + dropout1 (models.py:34-36) -> d2 (split)
-    RC((dx6<20, 20, 96, 2, 6, true, 0>(a3, S, g.wfx[3], 96, 864,
+    RC((dx6<FLSIM_FWC4, 20, 20, 96, 2, 6, true, 0>(a3, S, g.wfx[3], 96, 864,
         EpiPoolDropXs<11, 11, 96>{d2.hm, d2.l, w.i2, theta + P_OFF[7], workers, seed, SITE_DROP2,
                                   THR_P25, SCALE_P25, dropout, S * 11 * 11 * 4, w.d2f}, st,
         K_FWD4, 864)));
     // conv5 + ReLU (models.py:37) -> a5 (split)
-    RC((xs<11, 11, 96, 2, 4, 6, 4, 2, false, 0>(d2, S, g.wfx[4], 192, 864,
+    RC((xs<FLSIM_FWC5, 11, 11, 96, 2, 4, 6, 4, 2, false, 0>(d2, S, g.wfx[4], 192, 864,
         EpiBiasReluXs<192>{a5.hm, a5.l, theta + P_OFF[9], S * 13 * 13, w.a5f}, st, K_FWD5, 864)));
     // conv6 + ReLU + pool3 + dropout1 (models.py:38-40), written fp32 in torch's flatten order
     // (models.py:41) so linear1 keeps the torch weight layout; the floor-mode border row/column
     // of the 15x15 output (dropped by the pool) is never computed
-    RC((xs<13, 13, 192, 2, 4, 6, 4, 2, true, 0>(a5, S, g.wfx[5], 192, 1728,
+    RC((xs<FLSIM_FWC6, 13, 13, 192, 2, 4, 6, 4, 2, true, 0>(a5, S, g.wfx[5], 192, 1728,
         EpiPoolDrop<7, 7, 192, true>{w.d3, w.i3, theta + P_OFF[11], workers, seed, SITE_DROP3,
                                      THR_P25, SCALE_P25, dropout, S * 7 * 7 * 4}, st, K_FWD6,
         1728)));
